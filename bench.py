@@ -1,7 +1,12 @@
 #!/usr/bin/env python
 """bench.py -- KGWAS hot path on MI355X: full fast-mode KG minibatch training.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+    A plain run sets up, warms up, times the K steps, writes the last timed step's outputs if --dump-outputs is given and prints
+    the line; every extra measurement listed below runs only with --full.
+    --dump-outputs DIR: after the timed steps, what the last one handed its caller -- loss.npy (float64) and the model it trained,
+    param.<reference name>.npy (float32) -- at most 64 MB in all (above that a fixed, seeded sample of every array).  The inputs
+    (graph, features, labels, initial weights, batch order) depend on the arguments only, so two builds compare output for output.
     (N > 1: either under a launcher -- python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ... --
      or plainly: without WORLD_SIZE in the environment bench.py starts its N ranks itself, one per GPU over RCCL; on a box with
      fewer than N GPUs the ranks share devices over gloo -- a dry run of the code path, flagged in the line, not a measurement)
@@ -22,7 +27,7 @@ rank trains on its own 512-seed batches) or strong (one 512-seed batch per step 
 KGWAS.train does); --parallelism seed (default: graph replicated, gradient buckets all-reduced over RCCL,
 the first one under the second half of the backward) or shard (SNP rows sharded, partial-softmax exchange).
 
-Extra keys, all measured by this run:
+Extra keys, measured by this run with --full only (null / empty in a plain run):
   roofline     layer-1 forward aggregate kernel: HIP-event time of the launch; L2-side traffic of the same
                launch shape from three `rocprofv3 --pmc` passes this script starts over tools/pmc_probe.py
                (FETCH_SIZE / WRITE_SIZE / TCC hit-miss + MFMA counters; calibrated in the pass on a 1 GiB
@@ -42,6 +47,7 @@ Extra keys, all measured by this run:
 import argparse
 import json
 import os
+import re
 import sys
 import time
 
@@ -63,6 +69,35 @@ def algorithmic_bytes_fwd(n_edges, z_rows):
 def algorithmic_bytes_bwd(n_edges, z_rows, n_src):
     """B_b = E*(8C+24) + (N_d + N_s)*(4C+8)."""
     return 1048 * n_edges + 520 * (z_rows + n_src)
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(outdir, arrays, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: {name: tensor or array} as <outdir>/<name>.npy, float64 kept, everything else float32.  Above ``limit`` bytes
+    in all, every array is cut to the same share of its elements, drawn by a fixed seed from its flattened values (the same shapes
+    draw the same elements: two builds still compare element for element).  Returns {file name: shape written}."""
+    out = {}
+    for name, a in arrays.items():
+        if torch.is_tensor(a):
+            a = a.detach().cpu()
+            a = (a if a.dtype == torch.float64 else a.float()).numpy()
+        a = np.asarray(a)
+        out[name] = a.astype(np.float64 if a.dtype == np.float64 else np.float32)
+    total = sum(a.nbytes for a in out.values())
+    room = limit - 256 * len(out)                                 # (the .npy headers)
+    if total > room:
+        for name, a in out.items():
+            k = min(a.size, max(1, int(a.size * room / total) - 1))
+            out[name] = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, k, replace=False))]
+    os.makedirs(outdir, exist_ok=True)
+    written = {}
+    for name, a in out.items():
+        fn = re.sub(r'[^A-Za-z0-9._-]', '_', name) + '.npy'
+        np.save(os.path.join(outdir, fn), a)
+        written[fn] = list(a.shape)
+    return written
 
 
 def cpu_baseline(data, batch_size, budget_s=55.0, warmup=3, max_steps=20):
@@ -296,7 +331,7 @@ def run_in_step_trace(args, outdir, timeout_s=420):
     return out, None
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=40)
@@ -323,7 +358,20 @@ def main():
     ap.add_argument('--as-rank', default=None, metavar='R/P',
                     help='emulate rank R of a P-GPU job on ONE GPU: its share of the seeds / of the SNP range, every collective a '
                          'no-op of the right size ("fake" process group); prints that rank\'s compute time per step')
-    args = ap.parse_args()
+    ap.add_argument('--full', action='store_true',
+                    help='also run the extra measurements (CPU baseline, per-kernel timing and roofline with its rocprofv3 passes, in-step '
+                         'kernel trace, sampler-overlap check, measured epoch); the --no-* options above then skip single ones')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='write what the last timed step computed (loss, trained parameters) as DIR/<name>.npy, at most 64 MB')
+    args = ap.parse_args(argv)
+    if not args.full:
+        # a plain run: set-up, warm-up, the timed steps, --dump-outputs and the line -- nothing the headline does not need
+        args.no_cpu_baseline = args.no_kernel_timing = args.no_pmc = args.no_in_step = args.no_epoch = True
+    return args
+
+
+def main():
+    args = parse_args()
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ and args.as_rank is None:
         raise SystemExit(self_launch(args))
 
@@ -423,10 +471,11 @@ def main():
         opt = torch.optim.Adam(run.model.parameters(), lr=1e-4, weight_decay=5e-4)
         it = iter(NeighborLoader(data.data, [-1, -1], ('SNP', mine), batch_size=bs_rank, drop_last=True, device=dev))
         stats_e = [0, 0]
+        eager_loss = [None]
 
         def do_step(i):
             batch = next(it)
-            run.train_step(batch, opt, ld_w, world)
+            eager_loss[0] = run.train_step(batch, opt, ld_w, world)
             stats_e[0] += sum(batch.n_edges_per_layer)
             stats_e[1] += 2 * batch.n_edges_sampled
         mode = 'eager launches'
@@ -500,10 +549,21 @@ def main():
         edges_kernel, edges_ref = stats_e
     if shard and rank != 0:
         seeds = 0                             # (every rank works on the same batches: count the seeds once)
+    # what the last timed step handed its caller: its loss (SNP-sharded: this rank's share) and the model it trained -- before any
+    # --full measurement below trains further
+    if args.dump_outputs and (rank == 0 or emulated is not None):
+        if gs is not None:
+            loss_last = gs.loss[(args.warmup + args.steps - 1) % 2]
+        else:
+            loss_last = st_.last_loss if shard else eager_loss[0]
+        arrays = {'loss': loss_last.detach().double().reshape(1)}
+        arrays.update(('param.' + k, v) for k, v in run.model.named_reference_tensors().items() if torch.is_tensor(v))
+        written = dump_outputs(args.dump_outputs, arrays)
+        print(f'bench.py: {len(written)} arrays written to {args.dump_outputs}', file=sys.stderr)
     # did the next batch's sampler really run beside the step (two streams on one hardware queue would serialise silently)?
     # measured, after the timed region: n steps with it, n without, n sampler replays alone (every rank takes part)
     overlap = None
-    if os.environ.get('KGW_BENCH_OVERLAP_CHECK', '1') == '1':
+    if args.full and os.environ.get('KGW_BENCH_OVERLAP_CHECK', '1') == '1':
         if gs is not None:
             overlap = gs.measure_overlap(min(args.steps, 20))
         elif shard and st_.use_graph:

@@ -16,12 +16,12 @@ SMALL = ['--scale', '0.01', '--steps', '3', '--warmup', '2', '--no-pmc', '--no-c
          '--batch-size', '64']
 
 
-def _bench(*extra, env=None, timeout=900):
+def _bench(*extra, env=None, timeout=900, small=SMALL):
     e = dict(os.environ)
     for k in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT'):
         e.pop(k, None)
     e.update(env or {})
-    p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), *SMALL, *extra], cwd=ROOT, env=e, stdout=subprocess.PIPE,
+    p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), *small, *extra], cwd=ROOT, env=e, stdout=subprocess.PIPE,
                        stderr=subprocess.PIPE, text=True, timeout=timeout)
     assert p.returncode == 0, p.stderr[-4000:]
     lines = [l for l in p.stdout.splitlines() if l.strip()]
@@ -30,13 +30,39 @@ def _bench(*extra, env=None, timeout=900):
 
 
 def test_bench_one_gpu_line_has_the_contract_keys():
-    out = _bench('--gpus', '1')
+    out = _bench('--gpus', '1', '--full')
     for k in ('metric', 'value', 'unit', 'n_gpus', 'steps', 'warmup', 'ms_per_step', 'higher_is_better', 'scaling', 'vs_baseline',
               'dtype', 'data', 'config', 'roofline', 'cpu_baseline'):
         assert k in out, k
     assert out['n_gpus'] == 1 and out['steps'] == 3 and out['value'] > 0
     ov = out['config']['sampler_overlap']
     assert ov is not None and 'overlap_ratio' in ov          # the line says whether the side sampler really ran beside the step
+
+
+def test_bench_plain_run_times_the_steps_and_dumps_the_last_one(tmp_path):
+    """Without --full: the timed steps and the line only.  --dump-outputs writes the last timed step's loss and the trained
+    parameters; the same arguments give the same inputs, so two runs write the same arrays (up to the rounding of atomics)."""
+    import numpy as np
+    plain = [a for a in SMALL if not a.startswith('--no-')]
+    outs = []
+    for d in ('a', 'b'):
+        out = _bench('--gpus', '1', '--steps', '4', '--dump-outputs', str(tmp_path / d), small=plain)
+        for k in ('metric', 'value', 'unit', 'higher_is_better', 'dtype', 'ms_per_step'):
+            assert k in out, k
+        assert out['steps'] == 4 and out['value'] > 0 and out['ms_per_step'] > 0 and out['dtype'] == 'f32'
+        assert out['roofline'] is None and out['cpu_baseline'] is None and not out['breakdown']
+        assert out['config']['sampler_overlap'] is None and out['config']['epoch_measured'] is None
+        outs.append(tmp_path / d)
+    files = sorted(os.listdir(outs[0]))
+    assert 'loss.npy' in files and len([f for f in files if f.startswith('param.')]) > 10
+    assert sum(os.path.getsize(outs[0] / f) for f in files) <= 64 << 20
+    assert sorted(os.listdir(outs[1])) == files
+    loss = np.load(outs[0] / 'loss.npy')
+    assert loss.dtype == np.float64 and loss.shape == (1,) and np.isfinite(loss).all() and loss[0] > 0
+    for f in files:
+        a, b = np.load(outs[0] / f), np.load(outs[1] / f)
+        assert a.dtype in (np.float32, np.float64) and a.shape == b.shape and np.isfinite(a).all(), f
+        np.testing.assert_allclose(a, b, rtol=1e-5, atol=1e-6, err_msg=f)
 
 
 @pytest.mark.parametrize('extra', [[], ['--scaling', 'strong'], ['--parallelism', 'shard']], ids=['weak-seed', 'strong-seed', 'shard'])

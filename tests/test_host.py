@@ -239,6 +239,42 @@ def test_bench_starts_its_own_ranks_when_no_launcher_did(monkeypatch):
     assert seen['env']['HSA_ENABLE_IPC_MODE_LEGACY'] == '0'
 
 
+def test_bench_plain_run_leaves_every_extra_measurement_to_full():
+    import bench
+    plain = bench.parse_args(['--gpus', '1', '--steps', '7', '--warmup', '2'])
+    assert plain.steps == 7 and plain.warmup == 2 and not plain.full and plain.dump_outputs is None
+    assert plain.no_cpu_baseline and plain.no_kernel_timing and plain.no_pmc and plain.no_in_step and plain.no_epoch
+    full = bench.parse_args(['--gpus', '1', '--steps', '7', '--warmup', '2', '--full', '--dump-outputs', 'out'])
+    assert full.full and full.dump_outputs == 'out'
+    assert not (full.no_cpu_baseline or full.no_kernel_timing or full.no_pmc or full.no_in_step or full.no_epoch)
+    assert bench.parse_args(['--full', '--no-pmc']).no_pmc and not bench.parse_args(['--full', '--no-pmc']).no_epoch
+
+
+def test_bench_dump_outputs_float_arrays_under_the_limit(tmp_path):
+    """--dump-outputs: float64 stays float64, everything else becomes float32; above the limit every array is cut to the same
+    seeded sample, so two dumps of the same shapes hold the same elements."""
+    import bench
+    g = torch.Generator().manual_seed(0)
+    arrays = {'loss': torch.tensor([0.25], dtype=torch.float64), 'param.w': torch.rand(300, 40, generator=g),
+              'param.convs.0.convs.SNP__A B__Gene.att': torch.rand(7, generator=g, dtype=torch.float64).to(torch.float16)}
+    w = bench.dump_outputs(str(tmp_path / 'a'), arrays)
+    assert w == {'loss.npy': [1], 'param.w.npy': [300, 40], 'param.convs.0.convs.SNP__A_B__Gene.att.npy': [7]}
+    assert np.load(tmp_path / 'a' / 'loss.npy').dtype == np.float64
+    pw = np.load(tmp_path / 'a' / 'param.w.npy')
+    assert pw.dtype == np.float32 and np.array_equal(pw, arrays['param.w'].numpy())
+    assert np.load(tmp_path / 'a' / 'param.convs.0.convs.SNP__A_B__Gene.att.npy').dtype == np.float32
+    limit = 16384
+    for d in ('b', 'c'):
+        bench.dump_outputs(str(tmp_path / d), arrays, limit=limit)
+    files = sorted(os.listdir(tmp_path / 'b'))
+    assert files == sorted(w) and sum(os.path.getsize(tmp_path / 'b' / f) for f in files) <= limit
+    for f in files:
+        b, c = np.load(tmp_path / 'b' / f), np.load(tmp_path / 'c' / f)
+        assert np.array_equal(b, c) and b.size >= 1
+    sw = np.load(tmp_path / 'b' / 'param.w.npy')
+    assert 0 < sw.size < 12000 and np.isin(sw, pw).all()
+
+
 def test_gene_shard_scope_is_not_process_global_state():
     """ops.GENE_SHARD used to be set by a trainer and never cleared.  It is now active only inside a trainer's own
     forward passes, bound to ONE (X, W), and a probe records the layer without any collective."""

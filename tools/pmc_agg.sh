@@ -5,7 +5,7 @@ out=gpurun_out/pmc
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp; cd ${GRAFT_REPO_ROOT:-.}
 for c in FETCH_SIZE WRITE_SIZE; do
-  rocprofv3 --pmc $c --kernel-trace --output-format csv -d $out -o $c -- python bench.py --steps 4 --warmup 2 --no-cpu-baseline --no-kernel-timing > $out/$c.json 2> $out/$c.err
+  rocprofv3 --pmc $c --kernel-trace --output-format csv -d $out -o $c -- python bench.py --full --steps 4 --warmup 2 --no-cpu-baseline --no-kernel-timing > $out/$c.json 2> $out/$c.err
 done
 ls $out | head -20
 python - "$out" <<'PY'

@@ -3,7 +3,7 @@
 out=gpurun_out/pmc_sq
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp; cd ${GRAFT_REPO_ROOT:-.}
-rocprofv3 --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAVES --kernel-trace --output-format csv -d $out -o sq -- python bench.py --steps 4 --warmup 2 --no-cpu-baseline --no-kernel-timing --no-pmc --no-epoch > $out/sq.json 2> $out/sq.err
+rocprofv3 --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAVES --kernel-trace --output-format csv -d $out -o sq -- python bench.py --full --steps 4 --warmup 2 --no-cpu-baseline --no-kernel-timing --no-pmc --no-epoch > $out/sq.json 2> $out/sq.err
 python - "$out" <<'PY'
 import csv, sys, collections
 out = sys.argv[1]

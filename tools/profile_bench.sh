@@ -5,7 +5,7 @@ tag=${1:-run}; shift
 out=gpurun_out/prof_$tag
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp; cd ${GRAFT_REPO_ROOT:-.}
-rocprofv3 --kernel-trace --stats --output-format csv -d $out -o r -- python bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-pmc --no-epoch --no-kernel-timing "$@" > $out/bench.json 2> $out/err.log
+rocprofv3 --kernel-trace --stats --output-format csv -d $out -o r -- python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-pmc --no-epoch --no-kernel-timing "$@" > $out/bench.json 2> $out/err.log
 python - "$out" <<'PY'
 import csv, sys, json
 out = sys.argv[1]

@@ -1,7 +1,7 @@
 """One steady-state training step from a rocprofv3 kernel trace: the launches between two consecutive k_adam kernels, in start
 order, per hardware queue, with the idle gap before each.  usage: python tools/step_timeline.py <dir with r_kernel_trace.csv> [k]
 (k: which step from the end, default 2; k = "sampled": the last step that has the side sampler's launches -- more than 10 launches
-on a second queue -- beside it; bench.py ends with steps WITHOUT the sampler, its overlap check)."""
+on a second queue -- beside it; bench.py --full ends with steps WITHOUT the sampler, its overlap check)."""
 import csv, sys, glob, collections
 d = sys.argv[1]
 back = sys.argv[2] if len(sys.argv) > 2 else '2'
