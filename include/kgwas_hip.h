@@ -483,8 +483,12 @@ int kgw_mlp2_bwd_first_packed(const float* dH2, int64_t ldd, const float* W2, in
  * k < k_valid only, B[k >= k_valid] = 0: a gene count / feature width that is not a multiple of 32 is padded HERE and in a
  * zero-padded resident A, never by falling back to a library product).  A is split in
  * the kernel.  lda == 0: A is stored in 32 x 32 tiles, [ceil(M / 32)][K / 32][32][32] floats (rows past M present, any value) --
- * the layout for a resident copy, every 4 KB a wavefront reads per step is contiguous.  K % 32 == 0, lda % 4 == 0, 16-byte
- * aligned pointers, else KGW_E_UNSUPPORTED.  workspace:
+ * the layout for a resident copy, every 4 KB a wavefront reads per step is contiguous.  lda < 0: A is the OPERAND IMAGE, per
+ * 32-row tile t and 32-k chunk c 1 024 floats at A[t * (-lda) + c * 1024], float4 q * 64 + l (q < 4, l < 64) holding row
+ * 32 t + l % 32, k = 32 c + 16 (q / 2) + 8 (l / 32) + 4 (q % 2) + 0..3 (rows past M present, any value; -lda a multiple of
+ * 1 024 and >= K * 32) -- loaded straight into the kernel's operand registers; same results, bit for bit, as row-major A.
+ * Also for kgw_gemm3_partial and kgw_gemm3_riders.  K % 32 == 0, lda % 4 == 0, 16-byte aligned pointers, else
+ * KGW_E_UNSUPPORTED.  workspace:
  * kgw_gemm3_workspace_floats(M, K) floats (partial products of the K ranges, added in index order: deterministic).      */
 int64_t kgw_gemm3_packed_bytes(int64_t K);
 int64_t kgw_gemm3_workspace_floats(int64_t M, int64_t K);

@@ -21,10 +21,16 @@
 // Shape of the kernel.  Work item = (256-row tile of A, K range); 8 wavefronts (two per SIMD, one block per CU), each owns
 // 32 rows x 128 columns (four 32x32x16 accumulators) and all share the B tile (128-row blocks, two per CU, read B from L2
 // twice as often: 153 vs 143 us).  K advances in chunks of 32:
-//   A: a wavefront loads its 32 x 32 fp32 block coalesced (8 rows x 128 B per instruction, non-temporal), two chunks ahead,
-//      writes it to a wavefront-PRIVATE 4 KB LDS tile (XOR-swizzled 16-byte slots: ds_write_b128 and ds_read_b128 conflict
-//      free) and reads it back in MFMA operand layout (lane = row, 8 consecutive k) -- no block barrier on this path; the
-//      three-way split is 44 VALU instructions per 24 MFMAs, done on the operand registers;
+//   A, resident copies (the benchmark's two products): the OPERAND IMAGE (lda < 0, ops.gemm3_image) -- per 32-row tile and
+//      chunk 4 KB in the order of the MFMA operand registers, loaded 1 KB contiguous per instruction (non-temporal), two
+//      chunks ahead, straight into the registers the split reads: no LDS for A at all.  Measured in the step (MI355X,
+//      rocprofv3, 2 launches per step): 146.8 -> 135.9 us per launch on average against the LDS route below (now: forward
+//      with rider blocks 148, weight gradient 122 median), step 1.008 -> 0.980 ms; MFMA busy 0.42 -> 0.46 of the SIMD cycles;
+//   A, row-major or 32 x 32-tiled: a wavefront loads its 32 x 32 fp32 block coalesced (8 rows x 128 B per instruction,
+//      non-temporal), two chunks ahead, writes it to a wavefront-PRIVATE 4 KB LDS tile (XOR-swizzled 16-byte slots:
+//      ds_write_b128 and ds_read_b128 conflict free) and reads it back in MFMA operand layout (lane = row, 8 consecutive k)
+//      -- no block barrier on this path;
+//   the three-way split of A is 44 VALU instructions per 24 MFMAs, done on the operand registers;
 //   B: split once per call by kgw_gemm3_pack_* into the LDS image itself ([chunk][k16 step][piece][column tile][lane] x 16 B,
 //      lane-linear: a straight copy, conflict-free ds_read_b128), double buffered, one barrier per chunk.
 // Partial products go to a workspace [split][M][128]; kgw_gemm3 ends with a fixed-order reduction (+ bias, ReLU, or a
@@ -81,7 +87,8 @@ __global__ void __launch_bounds__(256) k_g3_pack(const float* __restrict__ S, lo
 
 // ---- the product ---------------------------------------------------------------------------------------------------------------
 struct G3Args {
-    const float* A; long lda; int M, K;          // lda == 0: A in 32 x 32 tiles, [ceil(M / 32)][K / 32][32][32]
+    const float* A; long lda; int M, K;          // lda == 0: A in 32 x 32 tiles, [ceil(M / 32)][K / 32][32][32]; lda < 0: the
+                                                 // operand image (ops.gemm3_image), -lda floats from one 32-row tile to the next
     const uint4* Bp;
     float* ws;
     int nsplit, n_tiles, per_xcd, flip;
@@ -102,15 +109,18 @@ struct G3Args {
 // the operand reads of chunk c).  MT = 32-row tiles per wavefront (1: 128-row blocks, two per CU; 2 was measured too -- 256-row
 // blocks, one per CU, each B operand feeding two MFMAs: 157-180 us against 153 -- and is not instantiated).
 struct G3KArgs { G3Args a; G3Riders R; };     // ONE kernel argument: the riders' tables are read where they lie, in the kernarg segment
-
-template <int MT, int NW = 4>
+//
+// IMG (lda < 0): A is read from its operand image -- per 32-row tile and chunk 4 KB, float4 q * 64 + lane = the float4 that
+// lane needs for half q & 1 of k16 step q >> 1 -- straight into the registers the split reads: 1 KB contiguous per load
+// instruction, no LDS tile, no ds_write, no swizzle.  Same products in the same order as the row-major route: same bits.
+template <int MT, int NW = 4, bool IMG = false>
 __global__ void __launch_bounds__(64 * NW, (8 / NW) / MT) k_g3_gemm(G3KArgs ka_) {
     const G3Args& a = ka_.a;
     constexpr int NT = 64 * NW, NB = G3_CH_U4 / NT;   // threads, B staging registers (uint4) per thread
     constexpr int NQ = 4 * MT;                 // A load instructions per chunk (8 rows x 128 B each)
     constexpr int AT = 256 * MT;               // 16-byte slots per wavefront-private A tile
     __shared__ g3_u4 smB0[G3_CH_U4], smB1[G3_CH_U4];
-    __shared__ g3_f4 smA0[NW * AT], smA1[NW * AT];
+    __shared__ g3_f4 smA0[IMG ? 1 : NW * AT], smA1[IMG ? 1 : NW * AT];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     // block -> work item: workgroups go round-robin to the 8 XCDs (blockIdx % 8), and XCD x takes the contiguous range
     // [x per_xcd, (x + 1) per_xcd) of the items in (K range, row tile) order -- one or two K ranges per XCD, so the packed B
@@ -135,9 +145,19 @@ __global__ void __launch_bounds__(64 * NW, (8 / NW) / MT) k_g3_gemm(G3KArgs ka_)
 
     // A addressing: instruction q covers rows 8 q .. 8 q + 7 of the wavefront's rows, 128 contiguous bytes each; 16-byte
     // slot s of row r lives at slot s ^ ((r >> 1) & 7) of its 128-byte LDS row
-    const long cstep = a.lda ? 32 : 1024;      // floats between consecutive chunks of a row
+    const long cstep = a.lda > 0 ? 32 : 1024;  // floats between consecutive chunks of a row
     const float* ap[NQ];
     int aw[NQ];
+    if (IMG) {
+        // (a wavefront past the last row tile reads the last tile: its rows are not stored)
+        int t = row0 >> 5;
+        t = t < ((a.M - 1) >> 5) ? t : ((a.M - 1) >> 5);
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) {
+            ap[q] = a.A + (long)t * -a.lda + (long)c0 * 1024 + (q * 64 + lane) * 4;
+            aw[q] = 0;
+        }
+    } else
 #pragma unroll
     for (int q = 0; q < NQ; ++q) {
         const int r = 8 * q + (lane >> 3);
@@ -212,6 +232,38 @@ __global__ void __launch_bounds__(64 * NW, (8 / NW) / MT) k_g3_gemm(G3KArgs ka_)
         }
     };
 
+    // IMG: r holds A of the chunk (MT == 1: float4 2 j + h is half h of k16 step j).  Both steps are split first, then r
+    // leaves for chunk cn -- two chunks ahead -- while the MFMAs run on the pieces.
+    auto compute_img = [&](g3_f4 (&r)[NQ], const g3_u4* B_, int cn) {
+        const g3_u4* B = B_ + lane;
+        g3_bf8 ap_[2][3];
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const g3_f4 u = r[2 * j], v = r[2 * j + 1];
+            const float x[8] = {u[0], u[1], u[2], u[3], v[0], v[1], v[2], v[3]};
+            uint4 p1, p2, p3;
+            kgw_split3x8(x, p1, p2, p3);
+            ap_[j][0] = __builtin_bit_cast(g3_bf8, p1);
+            ap_[j][1] = __builtin_bit_cast(g3_bf8, p2);
+            ap_[j][2] = __builtin_bit_cast(g3_bf8, p3);
+        }
+        load_a(r, cn);
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            g3_bf8 b[3][4];
+#pragma unroll
+            for (int p = 0; p < 3; ++p)
+#pragma unroll
+                for (int nt = 0; nt < 4; ++nt) b[p][nt] = __builtin_bit_cast(g3_bf8, B[((j * 3 + p) * 4 + nt) * 64]);
+            constexpr int TA[6] = {0, 2, 1, 0, 1, 0}, TB[6] = {2, 0, 1, 1, 0, 0};
+#pragma unroll
+            for (int t = 0; t < 6; ++t)
+#pragma unroll
+                for (int nt = 0; nt < 4; ++nt)
+                    acc[0][nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ap_[j][TA[t]], b[TB[t]][nt], acc[0][nt], 0, 0, 0);
+        }
+    };
+
     // steady state without branches: chunk indices past the end are clamped (a redundant load of the last chunk into a
     // buffer nobody reads), so the load counters stay exact.  Iteration c: A of chunk c + 2 leaves for registers, chunk
     // c + 1 (registers since iteration c - 1) goes to the other LDS buffers, chunk c is multiplied.
@@ -224,29 +276,54 @@ __global__ void __launch_bounds__(64 * NW, (8 / NW) / MT) k_g3_gemm(G3KArgs ka_)
                 for (int i = 0; i < 16; ++i) acc[mt][nt][i] = -acc[mt][nt][i];
     };
     const int last = nc - 1;
-    load_a(ra, 0);
-    load_b(0);
-    store_a(ra, smA0);
-    store_b(smB0);
-    load_a(ra, min(1, last));
-    load_b(min(1, last));
-    __syncthreads();
-    for (int c = 0; c < nc; c += 2) {
-        load_a(rb, min(c + 2, last));
-        store_a(ra, smA1);
-        store_b(smB1);
-        load_b(min(c + 2, last));
-        if (a.flip && c && !((c0 + c) & (a.flip - 1))) flip();  // (wavefront-uniform; at c == 0 the accumulator is zero)
-        compute(smA0, smB0);
-        __syncthreads();
-        if (c + 1 >= nc) break;
-        load_a(ra, min(c + 3, last));
-        store_a(rb, smA0);
+    if constexpr (IMG) {
+        static_assert(MT == 1, "the operand image holds 32-row tiles");
+        // iteration c: B of chunk c + 1 goes to the other LDS buffer, chunk c is multiplied from ra / rb, which then load
+        // chunk c + 2
+        load_a(ra, 0);
+        load_b(0);
         store_b(smB0);
-        load_b(min(c + 3, last));
-        if (a.flip && !((c0 + c + 1) & (a.flip - 1))) flip();
-        compute(smA1, smB1);
+        load_a(rb, min(1, last));
+        load_b(min(1, last));
         __syncthreads();
+        for (int c = 0; c < nc; c += 2) {
+            store_b(smB1);
+            load_b(min(c + 2, last));
+            if (a.flip && c && !((c0 + c) & (a.flip - 1))) flip();
+            compute_img(ra, smB0, min(c + 2, last));
+            __syncthreads();
+            if (c + 1 >= nc) break;
+            store_b(smB0);
+            load_b(min(c + 3, last));
+            if (a.flip && !((c0 + c + 1) & (a.flip - 1))) flip();
+            compute_img(rb, smB1, min(c + 3, last));
+            __syncthreads();
+        }
+    } else {                                   // row-major / tiled A: through the wavefront-private LDS tiles
+        load_a(ra, 0);
+        load_b(0);
+        store_a(ra, smA0);
+        store_b(smB0);
+        load_a(ra, min(1, last));
+        load_b(min(1, last));
+        __syncthreads();
+        for (int c = 0; c < nc; c += 2) {
+            load_a(rb, min(c + 2, last));
+            store_a(ra, smA1);
+            store_b(smB1);
+            load_b(min(c + 2, last));
+            if (a.flip && c && !((c0 + c) & (a.flip - 1))) flip();  // (wavefront-uniform; at c == 0 the accumulator is zero)
+            compute(smA0, smB0);
+            __syncthreads();
+            if (c + 1 >= nc) break;
+            load_a(ra, min(c + 3, last));
+            store_a(rb, smA0);
+            store_b(smB0);
+            load_b(min(c + 3, last));
+            if (a.flip && !((c0 + c + 1) & (a.flip - 1))) flip();
+            compute(smA1, smB1);
+            __syncthreads();
+        }
     }
 
     // accumulator register r of a 32x32 tile: row 8 (r / 4) + 4 g + r % 4, column lane & 31
@@ -341,6 +418,26 @@ static int g3_splits(int64_t M, int64_t K) {
     return (int)s;
 }
 
+// A operand checks shared by the entry points: lda > 0 row-major (a multiple of 4), 0 tiled, < 0 the operand image (a tile
+// stride of whole 4 KB chunks, at least K / 32 of them)
+static bool g3_a_ok(const float* A, int64_t lda, int64_t K) {
+    if ((uintptr_t)A & 15) return false;
+    if (lda < 0) return !(-lda % 1024) && -lda >= K / 32 * 1024;
+    return !(lda & 3);
+}
+
+// one launch of the product: the A route picks the instantiation
+static void g3_gemm_launch(const G3Args& a, const G3Riders& R, int n_riders, hipStream_t st) {
+    const int grid = a.per_xcd * 8 + n_riders;
+    if (g3_nw() == 8) {
+        if (a.lda < 0) k_g3_gemm<1, 8, true><<<grid, 512, 0, st>>>(G3KArgs{a, R});
+        else k_g3_gemm<1, 8><<<grid, 512, 0, st>>>(G3KArgs{a, R});
+    } else {
+        if (a.lda < 0) k_g3_gemm<1, 4, true><<<grid, 256, 0, st>>>(G3KArgs{a, R});
+        else k_g3_gemm<1, 4><<<grid, 256, 0, st>>>(G3KArgs{a, R});
+    }
+}
+
 extern "C" int64_t kgw_gemm3_packed_bytes(int64_t K) { return K > 0 && K % 32 == 0 ? (K / 32) * G3_CH_U4 * 16 : 0; }
 
 extern "C" int64_t kgw_gemm3_workspace_floats(int64_t M, int64_t K) {
@@ -369,7 +466,7 @@ extern "C" int kgw_gemm3_partial(const float* A, int64_t lda, int64_t M, int64_t
                                  int64_t workspace_floats, float* out, int64_t ldo, KgwGradSrc* src, kgw_stream_t stream_) {
     if (!A || !packed || !workspace || !out || !src) return KGW_E_NULL;
     if (M <= 0 || K <= 0 || M > (1 << 30) || K > (1 << 30)) return KGW_E_RANGE;
-    if (K % 32 || M % 32 || ldo != M || lda < 0 || (lda & 3) || ((uintptr_t)A & 15) || ((uintptr_t)packed & 15) || ((uintptr_t)workspace & 15))
+    if (K % 32 || M % 32 || ldo != M || !g3_a_ok(A, lda, K) || ((uintptr_t)packed & 15) || ((uintptr_t)workspace & 15))
         return KGW_E_UNSUPPORTED;
     const int ns = g3_splits(M, K);
     if (workspace_floats < (int64_t)ns * M * 128) return KGW_E_RANGE;
@@ -378,8 +475,7 @@ extern "C" int kgw_gemm3_partial(const float* A, int64_t lda, int64_t M, int64_t
     const int per_xcd = (tiles * ns + 7) / 8;
     G3Args a{A, (long)lda, (int)M, (int)K, (const uint4*)packed, workspace, ns, tiles, per_xcd, g3_flip()};
     const G3Riders none{};
-    if (g3_nw() == 8) k_g3_gemm<1, 8><<<per_xcd * 8, 512, 0, (hipStream_t)stream_>>>(G3KArgs{a, none});
-    else k_g3_gemm<1, 4><<<per_xcd * 8, 256, 0, (hipStream_t)stream_>>>(G3KArgs{a, none});
+    g3_gemm_launch(a, none, 0, (hipStream_t)stream_);
     KGW_LAUNCH_CHECK();
     *src = KgwGradSrc{};
     src->ws = workspace; src->kind = KGW_GRAD_G3T; src->nblk = ns; src->M = (int32_t)M; src->N = 128;
@@ -414,7 +510,7 @@ static int gemm3_launch(const float* A, int64_t lda, int64_t M, int64_t K, const
     if (!A || !packed || !workspace || !out) return KGW_E_NULL;
     if (out_rows_real && (!row_map || out_rows_n < 0 || out_rows_n > M)) return KGW_E_RANGE;   // (the padding is at most M rows)
     if (M <= 0 || K <= 0 || M > (1 << 30) || K > (1 << 30)) return KGW_E_RANGE;
-    if (K % 32 || lda < 0 || (lda & 3) || ((uintptr_t)A & 15) || ((uintptr_t)packed & 15) || ((uintptr_t)workspace & 15)) return KGW_E_UNSUPPORTED;
+    if (K % 32 || !g3_a_ok(A, lda, K) || ((uintptr_t)packed & 15) || ((uintptr_t)workspace & 15)) return KGW_E_UNSUPPORTED;
     if (!transpose_out && ((ldo & 3) || ((uintptr_t)out & 15) || (bias && ((uintptr_t)bias & 15)))) return KGW_E_UNSUPPORTED;
     if (transpose_out && (bias || relu || row_map)) return KGW_E_UNSUPPORTED;
     if (row_map && (!out_rows || (ld_rows & 3) || ((uintptr_t)out_rows & 15))) return KGW_E_UNSUPPORTED;
@@ -425,8 +521,7 @@ static int gemm3_launch(const float* A, int64_t lda, int64_t M, int64_t K, const
     hipStream_t st = (hipStream_t)stream_;
     const int per_xcd = (tiles * ns + 7) / 8;
     G3Args a{A, (long)lda, (int)M, (int)K, (const uint4*)packed, workspace, ns, tiles, per_xcd, g3_flip()};
-    if (g3_nw() == 8) k_g3_gemm<1, 8><<<per_xcd * 8 + R.n_blocks, 512, 0, st>>>(G3KArgs{a, R});
-    else k_g3_gemm<1, 4><<<per_xcd * 8 + R.n_blocks, 256, 0, st>>>(G3KArgs{a, R});
+    g3_gemm_launch(a, R, R.n_blocks, st);
     KGW_LAUNCH_CHECK();
     if (transpose_out) k_g3_reduce_t<<<dim3((unsigned)((M + 31) / 32), 4), 256, 0, st>>>(workspace, ns, (long)M, out, (long)ldo);
     else k_g3_reduce<<<(int)((M * 32 + 255) / 256), 256, 0, st>>>(workspace, ns, (long)M, bias, relu, out, (long)ldo, row_map, out_rows, (long)ld_rows,

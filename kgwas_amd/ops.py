@@ -957,15 +957,32 @@ def gemm3_tile(A: torch.Tensor) -> torch.Tensor:
     return A.view(Mp // 32, 32, K // 32, 32).permute(0, 2, 1, 3).contiguous()
 
 
+def gemm3_image(A: torch.Tensor) -> torch.Tensor:
+    """A [M, K] -> its kgw_gemm3 operand image [ceil(M / 32), ceil(K / 32), 1024] (rows past M and columns past K zero): per 32-row
+    tile and chunk of 32 k, float4 q * 64 + lane holds row 32 t + lane % 32, k = 32 c + 16 (q // 2) + 8 (lane // 32) + 4 (q % 2)
+    + 0..3 -- what load instruction q of that lane puts into the registers the kernel splits, with no LDS round trip.  A
+    row range [32 i, ...) is the slice [i:] of the tiles, a K range [32 c0, 32 c1) the slice [:, c0:c1]."""
+    M, K = A.shape
+    Mp, Kp = (M + 31) // 32 * 32, (K + 31) // 32 * 32
+    if Mp != M or Kp != K:
+        A = torch.nn.functional.pad(A, (0, Kp - K, 0, Mp - M))
+    A = A.contiguous()
+    #        tile     m   chunk    j  g  h  e         ->   tile, chunk, j, h, g, m, e
+    return A.view(Mp // 32, 32, Kp // 32, 2, 2, 2, 4).permute(0, 2, 3, 5, 4, 1, 6).reshape(Mp // 32, Kp // 32, 1024)
+
+
 def gemm3(A: torch.Tensor, packed: torch.Tensor, bias=None, relu: bool = False, transpose_out: bool = False, out=None, tiled_rows: int = 0,
-          row_map=None, out_rows=None, out_rows_real=None, defer: bool = False):
+          row_map=None, out_rows=None, out_rows_real=None, defer: bool = False, image_rows: int = 0):
     """act(A [M, K] @ B [K, 128] + bias) -> [M, 128], or its transpose [128, M] (``transpose_out``): the tall resident product
     of the first gene Linear on the bf16 matrix pipe with fp32 error (three exact bf16 pieces per operand, kgw_gemm3).
-    ``tiled_rows`` = M when A is a gemm3_tile() copy.  ``row_map`` [M] int32 + ``out_rows``: row m also goes to
+    ``tiled_rows`` = M when A is a gemm3_tile() copy, ``image_rows`` = M when A is (a slice of) a gemm3_image().  ``row_map`` [M] int32 + ``out_rows``: row m also goes to
     out_rows[row_map[m]] where row_map[m] >= 0 (the batch's rows of a resident layer output, no gather launch);
     ``out_rows_real`` (device int32): how many rows of ``out_rows`` are the batch's -- the rest (padding of a static layout) is
     zeroed by the same launch."""
-    if tiled_rows:
+    if image_rows:
+        M, K, lda = image_rows, A.shape[1] * 32, -A.stride(0)
+        assert A.dim() == 3 and A.shape[2] == 1024 and A.stride(2) == 1 and A.stride(1) == 1024 and A.shape[0] * 32 >= M
+    elif tiled_rows:
         M, K, lda = tiled_rows, A.shape[1] * 32, 0
         assert A.dim() == 4 and A.shape[2:] == (32, 32) and A.is_contiguous() and A.shape[0] * 32 >= M
     else:
@@ -1012,28 +1029,24 @@ _RESIDENT_T = {}
 
 
 def _resident_copies(X: torch.Tensor):
-    """(A operand of the forward, X^T) for a resident feature matrix, built once per matrix (and again if it is modified in
-    place: the tensor's version counter is part of the key).  X^T [K, Np] is the A operand of the weight-gradient product on
-    kgw_gemm3 (a second resident copy, 0.4 GB for the 5 120-wide gene features; row-major like X -- the 32 x 32-tiled layout the
-    kernel also takes, gemm3_tile, measured the same in isolation and in the step), its N node columns padded with zeros to a
-    multiple of 32 (the product's reduction runs over the nodes; the real KG's gene count need not be one -- SURVEY 8d gives
-    20 032 only as a lower bound -- and zero columns against zero rows of the packed dz leave dW exact).  The forward reads X
-    itself when its width is a multiple of 32 (5 120), else a copy padded with zero columns (57 742 -> 57 760, mode='full')."""
+    """(image of X, image of X^T) for a resident feature matrix [N, K]: the kgw_gemm3 operand images (gemm3_image) of the
+    forward's A and of the weight-gradient product's A, built once per matrix (and again if it is modified in place: the
+    tensor's version counter is part of the key).  Two resident copies, 0.4 GB each for the 5 120-wide gene features; the
+    kernel reads them straight into its operand registers.  Zero padding: X's K columns to a multiple of 32 (57 742 -> 57 760,
+    mode='full'), X^T's N node columns to a multiple of 32 (the product's reduction runs over the nodes; the real KG's gene
+    count need not be one -- SURVEY 8d gives 20 032 only as a lower bound -- and zero columns against zero rows of the packed
+    dz leave dW exact), the rows of both to whole 32-row tiles.  Row counts: N and K; K widths: shape[1] * 32."""
     key = (X.data_ptr(), tuple(X.shape), X.device, X._version)
     ent = _RESIDENT_T.get(key)
     if ent is not None and ent[0]() is not None:         # the tensor the copies were made from is alive: same memory, same features
-        return (X if ent[1][0] is None else ent[1][0]), ent[1][1]
+        return ent[1]
     if torch.cuda.is_current_stream_capturing():
         raise RuntimeError('resident copies requested inside a graph capture: run one eager step first')
     for k in [k for k, e in _RESIDENT_T.items() if e[0]() is None or (k[0] == key[0] and k[3] != key[3])]:
         del _RESIDENT_T[k]                               # copies of matrices that are gone (their address may be reused) or changed
-    N, K = X.shape
-    Kp, Np = (K + 31) // 32 * 32, (N + 31) // 32 * 32
-    direct = Kp == K and X.stride(0) % 4 == 0 and X.data_ptr() % 16 == 0
-    xt = X.t().contiguous() if Np == N else torch.nn.functional.pad(X.t(), (0, Np - N))
-    t = (None if direct else torch.nn.functional.pad(X, (0, Kp - K)), xt)      # (no strong reference to X itself)
+    t = (gemm3_image(X), gemm3_image(X.t()))             # (no strong reference to X itself)
     _RESIDENT_T[key] = (weakref.ref(X), t)
-    return (X if t[0] is None else t[0]), t[1]
+    return t
 
 
 def _resident_ok(X: torch.Tensor, W: torch.Tensor) -> bool:
@@ -1115,9 +1128,10 @@ class GeneLayerShard:
         self.last = (X, W, b)
         lo, hi = self.rows()
         if hi > lo:
-            Xf = _resident_copies(X)[0]
-            Kp = Xf.shape[1]
-            gemm3(Xf[lo:hi], gemm3_pack(W, Kp, False, k_valid=W.shape[1]), bias=b, relu=True, out=self.h_all[lo:hi])
+            Xi = _resident_copies(X)[0]                        # (lo: a multiple of 32, a whole tile of the image)
+            Kp = Xi.shape[1] * 32
+            gemm3(Xi[lo // 32:(hi + 31) // 32], gemm3_pack(W, Kp, False, k_valid=W.shape[1]), bias=b, relu=True, out=self.h_all[lo:hi],
+                  image_rows=hi - lo)
 
     def gather(self):
         import torch.distributed as dist
@@ -1146,13 +1160,14 @@ class GeneLayerShard:
     def weight_grad_partial(self, X, out=None):
         """[128, K] partial of the weight gradient from the rows this rank owns (zeros if it owns none)."""
         lo, hi = self.rows()
-        Xt = _resident_copies(X)[1]                                # [K, Np]
-        kin = min(self.chunk, Xt.shape[1] - lo)
+        Xt = _resident_copies(X)[1]                                # image of X^T [K, Np]: chunk c = nodes [32 c, 32 c + 32)
+        kin = min(self.chunk, Xt.shape[1] * 32 - lo)
         if out is None:
             out = torch.empty(KGW_C, X.shape[1], device=X.device)
         if hi <= lo or kin <= 0:
             return out.zero_()
-        return gemm3(Xt[:, lo:lo + kin], gemm3_pack(self.dz_mine[:hi - lo], kin, True, k_valid=hi - lo), transpose_out=True, out=out)
+        return gemm3(Xt[:, lo // 32:(lo + kin) // 32], gemm3_pack(self.dz_mine[:hi - lo], kin, True, k_valid=hi - lo), transpose_out=True,
+                     out=out, image_rows=X.shape[1])
 
 
 def gene_layer_split_pays(world: int, width: int) -> bool:
@@ -1204,12 +1219,12 @@ def resident_first_linear(X, W, b, g2l=None, rows_out=None, gs=None, rows_real=N
                 gs.forward_partial(X, W, b)
                 gs.gather()
             return gs.h_all[:X.shape[0]], False            # (staged: the trainer ran forward_partial + gather for this step)
-        Xf = _resident_copies(X)[0]                      # built outside any graph capture, on the first eager step
-        Kp = Xf.shape[1]
+        Xi = _resident_copies(X)[0]                      # built outside any graph capture, on the first eager step
+        Kp = Xi.shape[1] * 32
         fused = g2l is not None and rows_out is not None and rows_out.numel() > 0
         # (a width that is not a multiple of 32: the packing kernel reads the weight's real columns and pads with zeros)
-        h = gemm3(Xf, gemm3_pack(W, Kp, False, k_valid=W.shape[1]), bias=b, relu=True, row_map=g2l if fused else None,
-                  out_rows=rows_out if fused else None, out_rows_real=rows_real if fused else None)
+        h = gemm3(Xi, gemm3_pack(W, Kp, False, k_valid=W.shape[1]), bias=b, relu=True, row_map=g2l if fused else None,
+                  out_rows=rows_out if fused else None, out_rows_real=rows_real if fused else None, image_rows=X.shape[0])
         return h, fused
     return linear(X, W, b, relu=True, fixed_shape=True), False
 
@@ -1241,8 +1256,8 @@ def resident_first_weight_grad(dz, X, W, gs=None):
                 return None
             gs.scatter()
             return gs.weight_grad_partial(X)
-        Xt = _resident_copies(X)[1]                      # [K, Np], Np = the node count rounded up to 32, zero columns past it
-        return gemm3(Xt, gemm3_pack(dz, Xt.shape[1], True, k_valid=X.shape[0]), transpose_out=True, defer=True)
+        Xt = _resident_copies(X)[1]                      # image of X^T [K, Np], Np = the node count rounded up to 32, zero columns past it
+        return gemm3(Xt, gemm3_pack(dz, Xt.shape[1] * 32, True, k_valid=X.shape[0]), transpose_out=True, defer=True, image_rows=X.shape[1])
     if LIBRARY_GEMM.own_first and 0 < dz.shape[0] and X.dtype == torch.float32:
         return tn_gemm(dz, X)
     LIBRARY_GEMM.note('resident_first_weight_grad', dz.shape[0], dz.shape[1], X.shape[1])
@@ -1627,8 +1642,8 @@ class _ResidentMLP2(torch.autograd.Function):
         if _PACK_FUSED and ctx.shard is None and _resident_ok(X, W1):
             # the masked dh1 rows leave the kernel as kgw_gemm3's B operand image (the weight gradient's): no fp32 rows, no
             # kgw_gemm3_pack launch
-            Xt = _resident_copies(X)[1]                  # [K, Np], Np = the node count rounded up to 32
-            packed = torch.empty(int(L.kgw_gemm3_packed_bytes(Xt.shape[1])), dtype=torch.uint8, device=h.device)
+            Xt = _resident_copies(X)[1]                  # image of X^T [K, Np], Np = the node count rounded up to 32
+            packed = torch.empty(int(L.kgw_gemm3_packed_bytes(Xt.shape[1] * 32)), dtype=torch.uint8, device=h.device)
             src = (_lib.KgwGradSrc * 2)()
             rc = L.kgw_mlp2_bwd_first_packed(_p(dh2), dh2.stride(0), _p(W2), W2.stride(0), _p(h), h.stride(0), None, 0, 0, N, None, 0,
                                              _p(db1), _p(ws), nws, _p(g2l), None, 0, _p(packed), int(L.kgw_gemm3_flip()),
@@ -1637,7 +1652,7 @@ class _ResidentMLP2(torch.autograd.Function):
                 _lib.check(rc, 'kgw_mlp2_bwd_first_packed')
                 if sink is not None:
                     sink.add(db1, src[1], ws)
-                dW1 = gemm3(Xt, packed, transpose_out=True, defer=True)
+                dW1 = gemm3(Xt, packed, transpose_out=True, defer=True, image_rows=X.shape[1])
                 dW2, db2 = linear_weight_grad(dh2, h1g)
                 return None, dW1, db1, dW2, db2, None, None, None, None
         dz = _dz_buffer(h, ctx.shard)
