@@ -99,3 +99,22 @@ def fold_fc_output_reference(pack, U, V, T3, c3, src_m, dst_m):
     Vf = torch.zeros_like(V).index_copy(0, ids, Vp)
     kf = torch.zeros(NR, device=U.device, dtype=U.dtype).index_copy(0, ids, kap)
     return Uf, Vf, kf, Wp, gam
+
+
+def segment_alpha_sums(batch, layer, alpha):
+    """Sum of the per-local-edge ``alpha`` over every non-empty segment (destination row of one relation) the aggregate of
+    ``layer`` computes: the live relations' segments of the destination hops the layer aggregates (float64)."""
+    dg, m = batch.dg, batch.meta
+    n_hops = min(dg.num_layers - layer, dg.n_hops - 1) + 1
+    seg_ptr = batch.buf.seg_ptr[:int(m.seg_end[dg.n_hops - 1]) + 1].cpu().long()
+    a = torch.as_tensor(alpha).detach().cpu().double()
+    csum = torch.cat([torch.zeros(1, dtype=torch.float64), a.cumsum(0)])
+    out = [torch.zeros(0, dtype=torch.float64)]
+    for h in range(n_hops):
+        for r in range(dg.schema.NR):
+            if not dg.kg.rel_live[layer - 1][r]:
+                continue
+            p = seg_ptr[int(m.seg_off[h][r]):int(m.seg_off[h][r + 1]) + 1]
+            nz = p[1:] > p[:-1]
+            out.append((csum[p[1:]] - csum[p[:-1]])[nz])
+    return torch.cat(out)

@@ -8,7 +8,7 @@ import pytest
 import torch
 
 from oracle.pyg_semantics import segment_softmax
-from tests.helpers import assert_close
+from tests.helpers import assert_close, segment_alpha_sums
 
 pytestmark = pytest.mark.gpu
 
@@ -88,6 +88,8 @@ def test_aggregate_forward_backward(small_kg, edge_case_graph, graph, layer):
     # softmax rows sum to one wherever a row has edges
     alpha = ops.edge_alpha(batch, layer, stat, e_edge)
     assert torch.isfinite(alpha).all() and float(alpha.min()) >= 0.0
+    sums = segment_alpha_sums(batch, layer, alpha)
+    assert sums.numel() > 0 and float((sums - 1.0).abs().max()) <= 1e-5, float((sums - 1.0).abs().max())
 
 
 def test_temperature_and_slope(edge_case_graph):
