@@ -240,6 +240,43 @@ int kgw_sample_batch_parts(const KgwGraph* graph, const KgwBatchBuf* buf, const 
                            int32_t n_seeds, int32_t seed_type, int32_t full_graph, int32_t part_begin,
                            int32_t part_end, kgw_stream_t stream);
 
+/* Finite fan-out: PyG's NeighborLoader(num_neighbors=[k_1, ..., k_L]) (list form, without replacement).  An EXTENSION of the
+ * reference's loader, which trains with [-1] * L only (kgwas/kgwas.py:99-113).  fanout[h] (h = 0 .. n_hops-1; -1 or >= 1)
+ * applies to the expansion of the nodes first reached at hop h (hop 0 = the seeds), to every relation alike: a segment holds
+ * min(deg, fanout[h]) entries of its CSR row, in CSR order; -1 keeps the row.  A node is expanded once, at the hop that first
+ * reached it, so everything else about a batch (hop-pruned layers, chunk lists, src-major structures) keeps its meaning, and
+ * a call whose every fanout[h] is at least the largest degree writes the buffers of the plain call bit for bit.
+ *
+ * WHICH entries is a pure function of (sample seed, relation, destination, position) -- not of launch geometry, wavefront
+ * order or atomics -- so that anyone can restate it:
+ *      key(p) = kgwfan_key(sample_seed, relation id, GLOBAL destination id, position p in the row)           (below)
+ *      the segment = the fanout[h] entries with the smallest (key, position), i.e. position breaks ties
+ * (kgwfan_mix32 is a bijection of the 32-bit words, so the keys of one row are in fact pairwise distinct).
+ * sample_seed is a 64-bit word READ FROM DEVICE MEMORY (sample_seed_dev) when the kernels run: the call can be captured in a HIP
+ * graph once and replayed with another word for every batch.  The loader sets it to mix(loader seed, epoch, batch index).    */
+#ifdef __HIPCC__
+#define KGWFAN_INLINE static __host__ __device__ __forceinline__
+#else
+#define KGWFAN_INLINE static inline
+#endif
+KGWFAN_INLINE uint32_t kgwfan_mix32(uint32_t h) {            /* the 32-bit finaliser of MurmurHash3 (public domain) */
+    h ^= h >> 16; h *= 0x85ebca6bu; h ^= h >> 13; h *= 0xc2b2ae35u; h ^= h >> 16;
+    return h;
+}
+KGWFAN_INLINE uint32_t kgwfan_step(uint32_t h, uint32_t x) { return kgwfan_mix32((h ^ x) + 0x9e3779b9u); }
+KGWFAN_INLINE uint32_t kgwfan_row_hash(uint64_t sample_seed, int32_t rel, int32_t dst_global) {
+    uint32_t h = kgwfan_step(0u, (uint32_t)(sample_seed & 0xffffffffu));
+    h = kgwfan_step(h, (uint32_t)(sample_seed >> 32));
+    h = kgwfan_step(h, (uint32_t)rel);
+    return kgwfan_step(h, (uint32_t)dst_global);
+}
+KGWFAN_INLINE uint32_t kgwfan_key(uint64_t sample_seed, int32_t rel, int32_t dst_global, uint32_t position) {
+    return kgwfan_mix32(kgwfan_row_hash(sample_seed, rel, dst_global) ^ position);
+}
+int kgw_sample_batch_fanout(const KgwGraph* graph, const KgwBatchBuf* buf, const int64_t* seeds, int32_t n_seeds,
+                            int32_t seed_type, const int32_t* fanout /* [n_hops], host */, const uint64_t* sample_seed_dev,
+                            kgw_stream_t stream);
+
 /* Replaces: GATConv.edge_update + message + aggregate (kgwas/conv.py:200-228,182) and their
  * autograd for all relations of one layer.                                                    */
 int kgw_gat_aggregate_fwd(const KgwLayerArgs* args, kgw_stream_t stream);

@@ -135,7 +135,9 @@ __device__ __forceinline__ void hop_offsets(const SampArgs& A, int h, int* s_off
     }
 }
 
-__global__ void __launch_bounds__(KGW_BLK) k_seg_deg(SampArgs A, int h) {
+// FAN (finite fan-out, kgw_sample_batch_fanout): a segment holds min(deg, k) of the row's entries
+template <bool FAN>
+__global__ void __launch_bounds__(KGW_BLK) k_seg_deg(SampArgs A, int h, int k) {
     __shared__ int s_off[KGW_MAX_RELS + 1], s_cur[2];
     const KgwGraph& G = A.G;
     const KgwBatchMeta* M = A.B.meta;
@@ -149,6 +151,7 @@ __global__ void __launch_bounds__(KGW_BLK) k_seg_deg(SampArgs A, int h) {
         int g = A.B.n_id[G.node_base[d] + li];
         const int32_t* rp = G.g_rowptr + G.rowptr_off[r];
         int deg = rp[g + 1] - rp[g];
+        if (FAN) deg = min(deg, k);
         A.B.seg_deg[sg] = deg;
         A.B.seg_nch[sg] = (deg + KGW_CHUNK - 1) / KGW_CHUNK;
     }
@@ -276,7 +279,10 @@ __global__ void __launch_bounds__(KGW_BLK) k_scan_apply(const int32_t* in0, cons
 
 // (the bookkeeping of the finished scans -- edge_end / chunk_end of the hop, capacity checks -- rides in this launch: every
 //  block evaluates the checks for itself, block 0 publishes)
-__global__ void __launch_bounds__(KGW_BLK) k_fill_chunks(SampArgs A, int h) {
+// FAN: the chunks of a segment that was DRAWN (deg > k) carry gpos = -1: their global source ids stand in col_local (k_fan_select)
+// until k_relabel replaces them, not in g_col.  Segments that hold their whole row are described exactly as without a fan-out.
+template <bool FAN>
+__global__ void __launch_bounds__(KGW_BLK) k_fill_chunks(SampArgs A, int h, int k) {
     __shared__ int s_off[KGW_MAX_RELS + 1], s_err;
     const KgwGraph& G = A.G;
     KgwBatchMeta* M = A.B.meta;
@@ -305,6 +311,7 @@ __global__ void __launch_bounds__(KGW_BLK) k_fill_chunks(SampArgs A, int h) {
         const int g = A.B.n_id[G.node_base[d] + li];
         const int32_t* rp = G.g_rowptr + G.rowptr_off[r];
         int64_t gpos = G.col_off[r] + rp[g];
+        const bool drawn = FAN && rp[g + 1] - rp[g] > k;
         int e = A.B.seg_ptr[sg];
         const int e_end = e + A.B.seg_deg[sg];
         const int c0 = A.B.seg_chptr[sg];
@@ -313,8 +320,8 @@ __global__ void __launch_bounds__(KGW_BLK) k_fill_chunks(SampArgs A, int h) {
             ck.e0 = e;
             ck.e1 = min(e + KGW_CHUNK, e_end);
             ck.row = li; ck.rel = r; ck.first = c0; ck.nch = nch;
-            ck.gpos_lo = (int32_t)(gpos & 0xFFFFFFFFll);
-            ck.gpos_hi = (int32_t)(gpos >> 32);
+            ck.gpos_lo = drawn ? -1 : (int32_t)(gpos & 0xFFFFFFFFll);
+            ck.gpos_hi = drawn ? -1 : (int32_t)(gpos >> 32);
             A.B.chunks[c0 + c] = ck;
             e += KGW_CHUNK; gpos += KGW_CHUNK;
         }
@@ -339,6 +346,14 @@ __device__ __forceinline__ int64_t chunk_gpos(const KgwChunk& c) {
 // flight; beside a training step the launch has 1 024 wavefronts for ~8 k chunks, so the chain, not bandwidth, set its
 // 56 us.  Four chunks per wavefront-iteration put 8 column loads, then 8 table reads, in flight per lane.)
 constexpr int KGW_WALK = 4;
+// global source ids of a chunk: its stretch of g_col, or (FAN, a drawn segment) the ids k_fan_select left in col_local
+template <bool FAN>
+__device__ __forceinline__ const int32_t* chunk_col(const SampArgs& A, const KgwChunk& c) {
+    if (FAN && c.gpos_hi < 0) return A.B.col_local + c.e0;
+    return A.G.g_col + chunk_gpos(c);
+}
+
+template <bool FAN>
 __global__ void __launch_bounds__(KGW_BLK) k_mark(SampArgs A, int h) {
     const KgwGraph& G = A.G;
     const KgwBatchMeta* M = A.B.meta;
@@ -352,7 +367,7 @@ __global__ void __launch_bounds__(KGW_BLK) k_mark(SampArgs A, int h) {
         int g[KGW_WALK][KGW_CHUNK / 64];
 #pragma unroll
         for (int q = 0; q < KGW_WALK; ++q) {
-            const int32_t* col = G.g_col + chunk_gpos(ck[q]);
+            const int32_t* col = chunk_col<FAN>(A, ck[q]);
             const int n = (c + q < ce) ? ck[q].e1 - ck[q].e0 : 0;
 #pragma unroll
             for (int u = 0; u < KGW_CHUNK / 64; ++u) g[q][u] = (lane + 64 * u < n) ? col[lane + 64 * u] : -1;
@@ -371,6 +386,153 @@ __global__ void __launch_bounds__(KGW_BLK) k_mark(SampArgs A, int h) {
             for (int u = 0; u < KGW_CHUNK / 64; ++u)
                 if (g[q][u] >= 0 && cur[q][u] == -1) g2l[g[q][u]] = KGW_PENDING;   // benign race: every writer stores the same value
         }
+    }
+}
+
+// ---- finite fan-out: which min(deg, k) entries of a row a segment holds (kgw_sample_batch_fanout) ---------------------------------
+// The rule (include/kgwas_hip.h): entry p of the CSR row of relation r into destination g has the key kgwfan_key(seed, r, g, p);
+// the segment holds the k entries with the smallest (key, p), in CSR order.  The key of an entry is recomputed wherever it is
+// needed (one integer finaliser on (row hash ^ p): cheaper than keeping it), so a pass over a row reads no memory at all until the
+// chosen entries' column ids are fetched.  kgwfan_mix32 is a bijection and p < 2^32: the keys of one row are pairwise distinct, so
+// "the k smallest (key, p)" = "every key <= the k-th smallest key" and the tie-break never decides.
+//
+// k-th smallest key by a radix select, most significant digit first: 4 passes of 8 bits (a FIXED number of passes: nothing here
+// loops on data), each a 256-bin histogram in LDS (integer atomics) of the keys that agree with the digits found so far, then the
+// bin in which the running count reaches the rank still looked for.  Then one ordered compaction (ballot / popcount).
+//   W = 1: one wavefront owns the row (up to FAN_WAVE_MAX entries);
+//   W = 4: the block owns it (hub rows: 75 000 entries in the benchmark graph) -- one histogram for the four wavefronts; for the
+//          compaction each wavefront takes a contiguous quarter of the row, counts what it keeps and starts behind the others.
+// The result does not depend on W, on the launch geometry or on the order in which the atomics arrive (counts only).
+constexpr int FAN_WAVE_MAX = 4096;
+
+template <int W>
+__device__ __forceinline__ void fan_sync() {
+    if (W > 1) __syncthreads();
+    else { __threadfence_block(); __builtin_amdgcn_wave_barrier(); }     // (one wavefront: its LDS operations complete in order)
+}
+
+template <int W>
+__device__ void fan_select_row(const int32_t* __restrict__ col, int deg, int k, uint32_t hrow, int32_t* __restrict__ out,
+                               int* hist, int* s_cnt) {
+    constexpr int T = 64 * W;
+    const int lane = kgw_lane(), wv = W > 1 ? (int)(threadIdx.x >> 6) : 0;
+    const int t = W > 1 ? (int)threadIdx.x : lane;
+    uint32_t prefix = 0, pmask = 0;
+    int need = k;                    // the key looked for is the need-th smallest of those with (key & pmask) == prefix
+    for (int pass = 0; pass < 4; ++pass) {
+        const int sh = 24 - 8 * pass;
+        for (int i = t; i < 256; i += T) hist[i] = 0;
+        fan_sync<W>();
+        for (int p = t; p < deg; p += T) {
+            const uint32_t key = kgwfan_mix32(hrow ^ (uint32_t)p);
+            if ((key & pmask) == prefix) atomicAdd(&hist[(key >> sh) & 255u], 1);
+        }
+        fan_sync<W>();
+        // (every wavefront for itself: 4 bins per lane, inclusive scan over the lanes, the one lane whose bins hold the rank)
+        int c[4], mine = 0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) { c[j] = hist[4 * lane + j]; mine += c[j]; }
+        int incl = mine;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const int o = __shfl_up(incl, d, 64);
+            incl += lane >= d ? o : 0;
+        }
+        const bool hit = incl - mine < need && need <= incl;
+        int dig = 0, left = 1;
+        if (hit) {
+            int run = incl - mine;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                if (run < need && need <= run + c[j]) { dig = 4 * lane + j; left = need - run; }
+                run += c[j];
+            }
+        }
+        const unsigned long long hm = __ballot(hit);
+        const int from = hm ? __ffsll((long long)hm) - 1 : 0;
+        dig = __shfl(dig, from, 64);
+        need = __shfl(left, from, 64);
+        prefix |= (uint32_t)dig << sh;
+        pmask |= 255u << sh;
+        fan_sync<W>();               // (the histogram is cleared again by the next pass / the next row)
+    }
+    const uint32_t kth = prefix;     // the k-th smallest key of the row
+    const unsigned long long below = (1ull << lane) - 1ull;
+    int wb = 0, we = deg, base = 0;
+    if (W > 1) {
+        const int q = ((deg + W - 1) / W + 63) & ~63;
+        wb = min(deg, wv * q); we = min(deg, wb + q);
+        int cnt = 0;
+        for (int p0 = wb; p0 < we; p0 += 64) {
+            const int p = p0 + lane;
+            cnt += __popcll(__ballot(p < we && kgwfan_mix32(hrow ^ (uint32_t)p) <= kth));
+        }
+        if (lane == 0) s_cnt[wv] = cnt;
+        __syncthreads();
+        for (int w = 0; w < wv; ++w) base += s_cnt[w];
+    }
+    for (int p0 = wb; p0 < we; p0 += 64) {
+        const int p = p0 + lane;
+        const bool sel = p < we && kgwfan_mix32(hrow ^ (uint32_t)p) <= kth;
+        const unsigned long long bal = __ballot(sel);
+        const int rank = base + __popcll(bal & below);
+        if (sel && rank < k) out[rank] = col[p];          // (rank < k always holds: the guard keeps a store inside the segment whatever happens)
+        base += __popcll(bal);
+    }
+    if (W > 1) __syncthreads();      // (s_cnt is rewritten by the next row)
+}
+
+// Blocks walk the hop's segments in tiles of KGW_BLK, one lane per segment: segments that hold their whole row (deg <= k) cost
+// the degree lookup and nothing else.  Drawn rows of up to FAN_WAVE_MAX entries are done by the wavefront that found them, one
+// after the other; longer ones are listed in LDS and done by the whole block.  Writes the GLOBAL source ids of the chosen entries
+// into col_local[seg_ptr[sg] ...] (k_mark / k_relabel read them there, k_relabel leaves the local ids in their place).
+__global__ void __launch_bounds__(KGW_BLK) k_fan_select(SampArgs A, int h, int k, const uint64_t* __restrict__ seed_dev) {
+    __shared__ int s_off[KGW_MAX_RELS + 1];
+    __shared__ int s_hist[4][256];
+    __shared__ int s_hub[KGW_BLK], s_nhub, s_cnt[4];
+    const KgwGraph& G = A.G;
+    const KgwBatchMeta* M = A.B.meta;
+    if (M->error) return;                                  // (a hop past its capacities: k_fill_chunks wrote no chunks, nothing to fill)
+    if (threadIdx.x == 0) for (int r = 0; r <= G.n_rels; ++r) s_off[r] = M->seg_off[h][r];
+    const int begin = M->cur[0], end = M->cur[1];
+    const uint64_t seed = *seed_dev;
+    const int lane = kgw_lane(), wv = threadIdx.x >> 6;
+    for (int base = begin + blockIdx.x * KGW_BLK; base < end; base += gridDim.x * KGW_BLK) {      // (block-uniform trip count)
+        if (threadIdx.x == 0) s_nhub = 0;
+        __syncthreads();
+        const int sg = base + threadIdx.x;
+        int r = 0, g = 0, deg = 0, out = 0;
+        int64_t gpos = 0;
+        if (sg < end) {
+            r = find_rel(s_off, G.n_rels, sg);
+            const int d = G.rel_dst[r];
+            g = A.B.n_id[G.node_base[d] + M->node_off[d][h] + (sg - s_off[r])];
+            const int32_t* rp = G.g_rowptr + G.rowptr_off[r];
+            deg = rp[g + 1] - rp[g];
+            gpos = G.col_off[r] + rp[g];
+            out = A.B.seg_ptr[sg];
+        }
+        if (deg > FAN_WAVE_MAX && deg > k) s_hub[atomicAdd(&s_nhub, 1)] = sg;
+        unsigned long long todo = __ballot(deg > k && deg <= FAN_WAVE_MAX);
+        while (todo) {
+            const int j = __ffsll((long long)todo) - 1;
+            todo &= todo - 1;
+            const int rj = __shfl(r, j, 64), gj = __shfl(g, j, 64), dj = __shfl(deg, j, 64), oj = __shfl(out, j, 64);
+            const int64_t pj = ((int64_t)__shfl((int)(gpos >> 32), j, 64) << 32) | (uint32_t)__shfl((int)(gpos & 0xFFFFFFFFll), j, 64);
+            fan_select_row<1>(G.g_col + pj, dj, k, kgwfan_row_hash(seed, rj, gj), A.B.col_local + oj, s_hist[wv], nullptr);
+        }
+        __syncthreads();
+        const int nhub = s_nhub;
+        for (int i = 0; i < nhub; ++i) {
+            const int hs = s_hub[i];
+            const int rr = find_rel(s_off, G.n_rels, hs);
+            const int d = G.rel_dst[rr];
+            const int gg = A.B.n_id[G.node_base[d] + M->node_off[d][h] + (hs - s_off[rr])];
+            const int32_t* rp = G.g_rowptr + G.rowptr_off[rr];
+            fan_select_row<4>(G.g_col + G.col_off[rr] + rp[gg], rp[gg + 1] - rp[gg], k, kgwfan_row_hash(seed, rr, gg),
+                              A.B.col_local + A.B.seg_ptr[hs], s_hist[0], s_cnt);
+        }
+        __syncthreads();                                   // (s_nhub / s_hub are rewritten by the next tile)
     }
 }
 
@@ -422,6 +584,8 @@ __global__ void __launch_bounds__(KGW_BLK) k_assign(SampArgs A, const int32_t* t
 }
 
 // (block 0 also closes the hop: node counts of hop h + 1 from the compaction's tile prefix -- k_hop_end's one-thread launch)
+// (FAN, drawn segments: every lane reads the global id of its edge from col_local and writes the local id to the same element)
+template <bool FAN>
 __global__ void __launch_bounds__(KGW_BLK) k_relabel(SampArgs A, const int32_t* tile_pref, int h) {
     const KgwGraph& G = A.G;
     KgwBatchMeta* M = A.B.meta;
@@ -444,7 +608,7 @@ __global__ void __launch_bounds__(KGW_BLK) k_relabel(SampArgs A, const int32_t* 
         int g[KGW_WALK][KGW_CHUNK / 64];
 #pragma unroll
         for (int q = 0; q < KGW_WALK; ++q) {
-            const int32_t* col = G.g_col + chunk_gpos(ck[q]);
+            const int32_t* col = chunk_col<FAN>(A, ck[q]);
             const int n = (c + q < ce) ? ck[q].e1 - ck[q].e0 : 0;
 #pragma unroll
             for (int u = 0; u < KGW_CHUNK / 64; ++u) g[q][u] = (lane + 64 * u < n) ? col[lane + 64 * u] : -1;
@@ -949,9 +1113,11 @@ extern "C" int64_t kgw_sampler_scan_ints(int64_t seg_cap, int64_t node_slots, in
     return t > need ? t : need;
 }
 
-extern "C" int kgw_sample_batch_parts(const KgwGraph* graph, const KgwBatchBuf* buf, const int64_t* seeds,
-                                      int32_t n_seeds, int32_t seed_type, int32_t full_graph, int32_t part_begin,
-                                      int32_t part_end, kgw_stream_t stream_) {
+// ``fanout`` == nullptr: every hop takes whole rows (kgw_sample_batch_parts); else fanout[h] = entries kept per (row, relation)
+// at hop h, -1 = the whole row -- such a hop is issued with exactly the launches of the call without a fan-out.
+static int sample_parts(const KgwGraph* graph, const KgwBatchBuf* buf, const int64_t* seeds, int32_t n_seeds, int32_t seed_type,
+                        int32_t full_graph, int32_t part_begin, int32_t part_end, const int32_t* fanout,
+                        const uint64_t* sample_seed_dev, kgw_stream_t stream_) {
     if (!graph || !buf) return KGW_E_NULL;
     // grid of the sampler's grid-stride kernels: KgwBatchBuf.grid_blocks (a sampler replayed BESIDE a training step keeps
     // its launches small), else the whole-GPU default
@@ -981,8 +1147,27 @@ extern "C" int kgw_sample_batch_parts(const KgwGraph* graph, const KgwBatchBuf* 
     }
 
     for (int h = 0; h < graph->n_hops; ++h) {
+        const int fan_k = fanout ? fanout[h] : -1;
+        if (fan_k >= 0) {                 // a hop with a finite fan-out (never a whole-graph call)
+            if (2 * h >= part_begin && 2 * h <= part_end) {
+                k_seg_deg<true><<<SG, KGW_BLK, 0, st>>>(A, h, fan_k);
+                k_scan_block<2><<<1, 1024, 0, st>>>(buf->seg_deg, buf->seg_nch, buf->seg_ptr, buf->seg_chptr, buf->meta, 1);
+                k_fill_chunks<true><<<SG, KGW_BLK, 0, st>>>(A, h, fan_k);
+                k_fan_select<<<SG, KGW_BLK, 0, st>>>(A, h, fan_k, sample_seed_dev);
+                k_mark<true><<<SG, KGW_BLK, 0, st>>>(A, h);
+                KGW_LAUNCH_CHECK();
+            }
+            if (2 * h + 1 >= part_begin && 2 * h + 1 <= part_end) {
+                k_count_pending<<<SG, KGW_BLK, 0, st>>>(A, buf->scan_tmp, ntiles_nodes);
+                k_scan_top_fixed<<<1, KGW_BLK, 0, st>>>(buf->scan_tmp, ntiles_nodes);
+                k_assign<<<SG, KGW_BLK, 0, st>>>(A, buf->scan_tmp, ntiles_nodes, h);
+                k_relabel<true><<<SG, KGW_BLK, 0, st>>>(A, buf->scan_tmp, h);
+                KGW_LAUNCH_CHECK();
+            }
+            continue;
+        }
         if (2 * h >= part_begin && 2 * h <= part_end) {
-            k_seg_deg<<<SG, KGW_BLK, 0, st>>>(A, h);                       // (+ the hop's segment offsets)
+            k_seg_deg<false><<<SG, KGW_BLK, 0, st>>>(A, h, 0);             // (+ the hop's segment offsets)
             if (!full_graph) {
                 // a minibatch hop has a few 10 k segments: one block scans them (one launch instead of three)
                 k_scan_block<2><<<1, 1024, 0, st>>>(buf->seg_deg, buf->seg_nch, buf->seg_ptr, buf->seg_chptr, buf->meta, 1);
@@ -992,10 +1177,10 @@ extern "C" int kgw_sample_batch_parts(const KgwGraph* graph, const KgwBatchBuf* 
                 k_scan_apply<2><<<SG, KGW_BLK, 0, st>>>(buf->seg_deg, buf->seg_nch, buf->seg_ptr,
                                                               buf->seg_chptr, buf->meta, buf->scan_tmp);
             }
-            k_fill_chunks<<<SG, KGW_BLK, 0, st>>>(A, h);                   // (+ edge / chunk totals of the hop, capacity checks)
+            k_fill_chunks<false><<<SG, KGW_BLK, 0, st>>>(A, h, 0);         // (+ edge / chunk totals of the hop, capacity checks)
             KGW_LAUNCH_CHECK();
             if (!full_graph) {
-                k_mark<<<SG, KGW_BLK, 0, st>>>(A, h);
+                k_mark<false><<<SG, KGW_BLK, 0, st>>>(A, h);
                 KGW_LAUNCH_CHECK();
             }
         }
@@ -1008,7 +1193,7 @@ extern "C" int kgw_sample_batch_parts(const KgwGraph* graph, const KgwBatchBuf* 
                 // every node is already a seed: hop h+1 adds nothing
                 { int rc = fill_i32(buf->scan_tmp, 0, ntiles_nodes + 2, st, SG); if (rc) return rc; }
             }
-            k_relabel<<<SG, KGW_BLK, 0, st>>>(A, buf->scan_tmp, h);        // (+ node counts of hop h + 1)
+            k_relabel<false><<<SG, KGW_BLK, 0, st>>>(A, buf->scan_tmp, h); // (+ node counts of hop h + 1)
             KGW_LAUNCH_CHECK();
         }
     }
@@ -1070,6 +1255,27 @@ extern "C" int kgw_sample_batch_parts(const KgwGraph* graph, const KgwBatchBuf* 
         KGW_LAUNCH_CHECK();
     }
     return KGW_OK;
+}
+
+extern "C" int kgw_sample_batch_parts(const KgwGraph* graph, const KgwBatchBuf* buf, const int64_t* seeds,
+                                      int32_t n_seeds, int32_t seed_type, int32_t full_graph, int32_t part_begin,
+                                      int32_t part_end, kgw_stream_t stream_) {
+    return sample_parts(graph, buf, seeds, n_seeds, seed_type, full_graph, part_begin, part_end, nullptr, nullptr, stream_);
+}
+
+// Finite fan-out (PyG NeighborLoader(num_neighbors=[k_1, ..., k_L]); no counterpart in the reference, which trains with [-1] * L).
+extern "C" int kgw_sample_batch_fanout(const KgwGraph* graph, const KgwBatchBuf* buf, const int64_t* seeds, int32_t n_seeds,
+                                       int32_t seed_type, const int32_t* fanout, const uint64_t* sample_seed_dev,
+                                       kgw_stream_t stream_) {
+    if (!graph || !fanout) return KGW_E_NULL;
+    if (graph->n_hops < 1 || graph->n_hops > KGW_MAX_LAYERS) return KGW_E_RANGE;
+    bool finite = false;
+    for (int h = 0; h < graph->n_hops; ++h) {
+        if (fanout[h] == 0 || fanout[h] < -1) return KGW_E_RANGE;
+        finite |= fanout[h] > 0;
+    }
+    if (finite && !sample_seed_dev) return KGW_E_NULL;
+    return sample_parts(graph, buf, seeds, n_seeds, seed_type, 0, 0, 2 * graph->n_hops, fanout, sample_seed_dev, stream_);
 }
 
 extern "C" int kgw_sample_batch(const KgwGraph* graph, const KgwBatchBuf* buf, const int64_t* seeds,

@@ -18,7 +18,7 @@ import numpy as np
 import torch
 
 from . import _lib, ops
-from .sampler import BatchBuffers, NeighborLoader, SampledBatch, sample_into
+from .sampler import BatchBuffers, NeighborLoader, SampledBatch, check_num_neighbors, fanout_words, sample_into
 
 
 # Blocks per launch of a sampler that runs beside a step graph.  Round 6: 1 024 (256 until then).  What the side sampler costs the
@@ -140,15 +140,23 @@ class BatchCache:
 class GraphTrainStep:
     def __init__(self, run, input_nodes, batch_size: int, lr: float = 1e-4, weight_decay: float = 5e-4,
                  margin: float = 1.03, capture_optimizer: bool = True, overlap_sampling: bool = None,
-                 shard_gene_layer: bool = None, cache_batches: bool = False):
+                 shard_gene_layer: bool = None, cache_batches: bool = False, num_neighbors=None, sample_seed: int = 0):
+        """``num_neighbors`` (None = the reference's [-1] * L): PyG's list form of per-hop fan-outs.  With a finite fan-out the
+        batches are redrawn every epoch from (``sample_seed``, epoch, batch index) -- ``set_epoch`` names the epoch, a step past
+        the last batch moves on to the next one by itself -- the capacities of the static layout are bounds that hold for every
+        draw (NeighborLoader.measure_caps), and no batch is kept for later epochs (BatchCache off)."""
         self.run = run
         self.model = run.model
         self.batch_size = int(batch_size)
         dev = torch.device(run.device)
         self.input_type, ids = input_nodes
         L = run.gnn_num_layers
-        probe = NeighborLoader(run.data.data, [-1] * L, (self.input_type, ids), batch_size=self.batch_size,
-                               drop_last=True, device=dev, prefetch=False)
+        if num_neighbors is not None and len(num_neighbors) != L:
+            raise ValueError(f'num_neighbors needs one entry per layer ({L})')
+        self.fanout = check_num_neighbors(num_neighbors) if num_neighbors is not None else None
+        self.sample_seed, self.epoch = int(sample_seed), 0
+        probe = NeighborLoader(run.data.data, self.fanout if self.fanout is not None else [-1] * L, (self.input_type, ids),
+                               batch_size=self.batch_size, drop_last=True, device=dev, prefetch=False, seed=self.sample_seed)
         self.n_batches = len(probe)
         if self.n_batches == 0:
             raise ValueError('no full batch in input_nodes')
@@ -161,6 +169,9 @@ class GraphTrainStep:
         self.buf = self.bufs[0]
         self.meta = self.dg.static_meta()
         self.seeds = torch.zeros(self.batch_size, dtype=torch.int64, device=dev)        # seeds sampled by the side branch
+        # finite fan-out: the 64-bit sample seed the (captured) sampler reads, fed like ``seeds``; the words of an epoch's batches
+        self.sample_word = torch.zeros(1, dtype=torch.int64, device=dev) if self.fanout is not None else None
+        self._epoch_words = {}
         self.ld_w = run._ld_weight_vector()
         self.capture_optimizer = capture_optimizer
         self.world = 1
@@ -236,7 +247,7 @@ class GraphTrainStep:
         # ``cache_batches`` (KGWAS.train with more than one epoch; off for a bench line -- the headline samples live): the batches of
         # the first pass over the loader are kept and put back in later passes instead of being sampled again (BatchCache)
         self.cache = None
-        self._want_cache = bool(cache_batches) and os.environ.get('KGW_EPOCH_CACHE', '1') != '0'
+        self._want_cache = bool(cache_batches) and os.environ.get('KGW_EPOCH_CACHE', '1') != '0' and self.fanout is None
         # (parameter-only kernels on a parallel branch of the captured step: measured again in round 5 -- 1.397 ms against 1.081, and
         #  the branch's queue displaces the side sampler's, overlap ratio -0.14 -- HIP-graph branches are not a tool here; removed)
         self._capture()
@@ -277,7 +288,7 @@ class GraphTrainStep:
         if self.overlap:
             self._side.wait_stream(main)                               # fork
             with torch.cuda.stream(self._side):
-                sample_into(self.dg, self.bufs[1 - cur], self.seeds, self.seed_type, record=False)
+                self._sample(1 - cur)
         buf = self.bufs[cur]
         batch = SampledBatch(self.dg, buf, self.meta, self.input_type, bs, static=True)
         self.opt.zero_grad(set_to_none=True)
@@ -322,7 +333,7 @@ class GraphTrainStep:
                 if self.overlap:
                     main.wait_stream(self._side)                       # join
                 elif not self.twin:
-                    sample_into(self.dg, self.bufs[1 - cur], self.seeds, self.seed_type, record=False)
+                    self._sample(1 - cur)
                 return loss
         ticked = False
         if self.capture_optimizer:
@@ -346,7 +357,7 @@ class GraphTrainStep:
         if self.overlap:
             main.wait_stream(self._side)                               # join
         elif not self.twin:
-            sample_into(self.dg, self.bufs[1 - cur], self.seeds, self.seed_type, record=False)
+            self._sample(1 - cur)
         return loss
 
     def _late_params(self):
@@ -407,6 +418,31 @@ class GraphTrainStep:
             if self.split_backward:
                 self._step_body_b(k)
 
+    def _sample(self, which: int):
+        """Enqueue the sampler for ``self.seeds`` (and, with a finite fan-out, ``self.sample_word``) into bufs[which]."""
+        sample_into(self.dg, self.bufs[which], self.seeds, self.seed_type, record=False, fanout=self.fanout,
+                    sample_word=self.sample_word)
+
+    def set_epoch(self, epoch: int):
+        """Finite fan-out: the epoch the next ``step`` calls draw for."""
+        self.epoch = int(epoch)
+
+    def _key(self, i: int, epoch: int) -> int:
+        """What a buffer holds: batch i -- of epoch ``epoch`` when batches are redrawn every epoch."""
+        return i if self.fanout is None else epoch * self.n_batches + i
+
+    def _feed(self, i: int, epoch: int):
+        """Seeds (and sample seed) of batch i into the tensors the sampler reads, on the current stream."""
+        b = self.batch_size
+        self.seeds.copy_(self.ids[i * b:(i + 1) * b])
+        if self.fanout is not None:
+            if epoch not in self._epoch_words:
+                self._epoch_words = {e: w for e, w in self._epoch_words.items() if e >= epoch - 1}
+                w = fanout_words(self.sample_seed, epoch, self.n_batches, self.seeds.device)
+                w.record_stream(self._side)
+                self._epoch_words[epoch] = w
+            self.sample_word.copy_(self._epoch_words[epoch][i:i + 1])
+
     def _sample_now(self, which: int, i: int):
         b = self.batch_size
         if self.cache is not None:
@@ -414,11 +450,11 @@ class GraphTrainStep:
         if self.cache is not None and self.cache.filled[i]:
             self.cache.restore(which, i)
         else:
-            self.seeds.copy_(self.ids[i * b:(i + 1) * b])
-            sample_into(self.dg, self.bufs[which], self.seeds, self.seed_type, record=False)
+            self._feed(i, self.epoch)
+            self._sample(which)
             if self.cache is not None:
                 self.cache.save(which, i)
-        self._have[which] = i
+        self._have[which] = self._key(i, self.epoch)
 
     def _capture(self):
         # warm-up on a side stream (allocator pools, one-time kernel attributes, Adam state), then undo its effect
@@ -509,7 +545,7 @@ class GraphTrainStep:
             if self.twin:
                 gs = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(gs, stream=self._side):
-                    sample_into(self.dg, self.bufs[cur], self.seeds, self.seed_type, record=False)
+                    self._sample(cur)
                 self.sample_graphs[cur] = gs
         self._have = [-1, -1]
         if self._want_cache and self.twin:
@@ -524,9 +560,10 @@ class GraphTrainStep:
         cur = i % 2
         if self._image_params:
             self._refresh_images()               # (a weight changed by anything but this trainer's own optimiser launch: re-pack)
-        if self._have[cur] != i:                 # first call / non-sequential access: sample it now
+        if self._have[cur] != self._key(i, self.epoch):      # first call / non-sequential access: sample it now
             self._sample_now(cur, i)
         nxt = (i + 1) % self.n_batches
+        nxt_epoch = self.epoch + (1 if nxt == 0 else 0)      # (finite fan-out: the batch after the last one belongs to the next epoch)
         b = self.batch_size
         if self.gene_shard is not None:
             self._g_partial.replay()               # this rank's rows of the first gene layer, then everybody's
@@ -541,7 +578,7 @@ class GraphTrainStep:
                 if cache is not None and cache.filled[nxt]:
                     cache.restore(1 - cur, nxt)                     # (a later epoch: one copy launch instead of the sampler's ~25)
                 else:
-                    self.seeds.copy_(self.ids[nxt * b:(nxt + 1) * b])
+                    self._feed(nxt, nxt_epoch)
                     if not self._skip_resample:
                         self.sample_graphs[1 - cur].replay()
                         if cache is not None:
@@ -553,10 +590,12 @@ class GraphTrainStep:
             self._twin_pending[1 - cur] = True
             self._twin_pending[cur] = False
         else:
-            self.seeds.copy_(self.ids[nxt * b:(nxt + 1) * b])
+            self._feed(nxt, nxt_epoch)
             self.graphs[cur].replay()
-        self._have[1 - cur] = nxt
+        self._have[1 - cur] = self._key(nxt, nxt_epoch)
         self._have[cur] = -1
+        if self.fanout is not None and nxt == 0:
+            self.epoch = nxt_epoch               # (a pass is over: the next one draws anew unless set_epoch says otherwise)
         if not self.capture_optimizer:
             if self.split_backward:
                 from . import dist as kdist

@@ -80,7 +80,9 @@ class KGWAS:
         w[torch.from_numpy(ids)] = torch.from_numpy(np.asarray(self.data.ldsc_weight, dtype=np.float64))
         return w.to(self.device)
 
-    def make_loaders(self, batch_size, num_workers=0):
+    def make_loaders(self, batch_size, num_workers=0, num_neighbors=None):
+        """``num_neighbors`` (extra, None = the reference's [-1] * L): fan-outs of the TRAINING loader only; validation, test
+        and inference always take full neighbourhoods, as the reference does."""
         kwargs = {'batch_size': batch_size, 'num_workers': num_workers, 'drop_last': True, 'device': self.device}
         eval_kwargs = {'batch_size': 512, 'num_workers': num_workers, 'drop_last': False, 'device': self.device}
         L = self.gnn_num_layers
@@ -88,8 +90,8 @@ class KGWAS:
         tr_type, tr_ids = self.data.train_input_nodes
         tr_ids = kdist.shard_batches(np.asarray(tr_ids), batch_size, rank, world)
         tr_kwargs = dict(kwargs, batch_size=batch_size // world)      # each rank: its slice of every batch
-        self.train_loader = NeighborLoader(self.data.data, num_neighbors=[-1] * L, sampler=None,
-                                           input_nodes=(tr_type, tr_ids), **tr_kwargs)        # kgwas.py:99-101
+        self.train_loader = NeighborLoader(self.data.data, num_neighbors=[-1] * L if num_neighbors is None else num_neighbors,
+                                           sampler=None, input_nodes=(tr_type, tr_ids), seed=self.seed, **tr_kwargs)        # kgwas.py:99-101
         self.val_loader = NeighborLoader(self.data.data, num_neighbors=[-1] * L,
                                          input_nodes=self.data.val_input_nodes, **kwargs)     # :102-103
         self.test_loader = NeighborLoader(self.data.data, num_neighbors=[-1] * L,
@@ -155,13 +157,25 @@ class KGWAS:
         self.shard_bytes_moved = st.xchg.bytes_moved
 
     def train(self, batch_size=512, num_workers=0, lr=1e-4, weight_decay=5e-4, epoch=10, save_best_model=True,
-              save_name=None, data_to_cuda=False, use_graph=True, parallelism='seed'):
+              save_name=None, data_to_cuda=False, use_graph=True, parallelism='seed', num_neighbors=None):
         """Same signature and defaults as kgwas/kgwas.py:85-87.  ``use_graph`` (extra, default on): run the
         training step as one captured HIP graph (kgwas_amd/graph_step.py); off = eager launches, same math.
         ``parallelism`` (extra; matters under torch.distributed): 'seed' = every rank trains on its slice of each batch
         against a replicated graph (kgwas_amd/dist.py); 'shard' = SNP rows sharded by id range, Gene / GO replicated
-        (kgwas_amd/shard.py, BASELINE.json north_star)."""
+        (kgwas_amd/shard.py, BASELINE.json north_star).
+        ``num_neighbors`` (extra, default None = the reference's [-1] * L): PyG's list form [k_1, ..., k_L] for the TRAINING
+        loader -- at most k_h in-edges per (node, relation) at hop h, redrawn every epoch from (the run's seed, epoch, batch
+        index); evaluation and inference keep full neighbourhoods.  Not available with parallelism='shard'."""
         total_epoch = epoch
+        if num_neighbors is not None:
+            from .sampler import check_num_neighbors
+            if not isinstance(num_neighbors, dict) and len(num_neighbors) != self.gnn_num_layers:
+                raise ValueError(f'num_neighbors needs one entry per layer ({self.gnn_num_layers})')
+            if check_num_neighbors(num_neighbors) is None:
+                num_neighbors = None                                   # [-1] * L: the default path
+            elif parallelism == 'shard':
+                raise NotImplementedError("a finite fan-out is not available with parallelism='shard': the ranks would have "
+                                          "to agree on the draw of every replicated row")
         if save_name is None:
             save_name = self.exp_name
         self.save_name = save_name
@@ -170,7 +184,7 @@ class KGWAS:
         if parallelism != 'seed':
             raise ValueError(f"parallelism {parallelism!r}: 'seed' or 'shard'")
         print_sys('Creating data loader...')
-        self.make_loaders(batch_size, num_workers)
+        self.make_loaders(batch_size, num_workers, num_neighbors)
         rank, world = kdist.rank_world()
         if world > 1:
             kdist.broadcast_params(self.model)
@@ -184,7 +198,7 @@ class KGWAS:
                                         shard_gene_layer=None,
                                         # (the loader's batch order is fixed, kgwas.py:93-101: the batches sampled in epoch 1 are
                                         #  kept in HBM and put back in later epochs -- graph_step.BatchCache)
-                                        cache_batches=total_epoch > 1)
+                                        cache_batches=total_epoch > 1, num_neighbors=num_neighbors, sample_seed=self.seed)
             optimizer = graph_step.opt
         else:
             optimizer = torch.optim.Adam(self.model.parameters(), lr=lr, weight_decay=weight_decay)   # kgwas.py:116
@@ -194,6 +208,8 @@ class KGWAS:
         print_sys('Start Training...')
         for ep in range(total_epoch):
             self.model.train()
+            if num_neighbors is not None:                            # (a finite fan-out draws anew every epoch)
+                (graph_step if graph_step is not None else self.train_loader).set_epoch(ep)
             steps = range(graph_step.n_batches) if graph_step is not None else enumerate(self.train_loader)
             for item in steps:
                 if graph_step is not None:

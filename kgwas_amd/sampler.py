@@ -494,14 +494,59 @@ def gather_rows_multi(jobs) -> None:
 
 
 def sample_into(dg: DeviceGraph, buf: BatchBuffers, seeds: Optional[torch.Tensor], seed_type: int, stream=None,
-                record: bool = True):
+                record: bool = True, fanout: Optional[Sequence[int]] = None, sample_word: Optional[torch.Tensor] = None):
+    """``fanout`` (None = whole rows at every hop): entries kept per (row, relation) at each hop, with ``sample_word`` the
+    1-element int64 DEVICE tensor holding the draw's 64-bit seed (read by the kernels when they run)."""
     st = stream if stream is not None else torch.cuda.current_stream()
     n = 0 if seeds is None else int(seeds.numel())
-    rc = _lib.lib().kgw_sample_batch(C.byref(dg.kg), C.byref(buf.c), _ptr(seeds), n, seed_type,
-                                     1 if dg.full_graph else 0, C.c_void_p(st.cuda_stream))
-    _lib.check(rc, 'kgw_sample_batch')
+    if fanout is not None and any(int(k) != -1 for k in fanout):
+        if dg.full_graph:
+            raise ValueError('a whole-graph block structure has no fan-out')
+        assert sample_word is not None and sample_word.dtype == torch.int64 and sample_word.is_cuda
+        fo = (C.c_int32 * KGW_MAX_LAYERS)(*[int(k) for k in fanout])
+        rc = _lib.lib().kgw_sample_batch_fanout(C.byref(dg.kg), C.byref(buf.c), _ptr(seeds), n, seed_type, fo,
+                                                _ptr(sample_word), C.c_void_p(st.cuda_stream))
+        _lib.check(rc, 'kgw_sample_batch_fanout')
+    else:
+        rc = _lib.lib().kgw_sample_batch(C.byref(dg.kg), C.byref(buf.c), _ptr(seeds), n, seed_type,
+                                         1 if dg.full_graph else 0, C.c_void_p(st.cuda_stream))
+        _lib.check(rc, 'kgw_sample_batch')
     if record:
         buf.ready.record(st)
+
+
+_M64 = (1 << 64) - 1
+
+
+def _splitmix64(z: int) -> int:
+    z = (z + 0x9E3779B97F4A7C15) & _M64
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _M64
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _M64
+    return z ^ (z >> 31)
+
+
+def fanout_sample_word(seed: int, epoch: int, batch: int) -> int:
+    """The 64-bit sample seed of batch ``batch`` of epoch ``epoch`` of a loader made with ``seed``: three rounds of the
+    splitmix64 finaliser, one per word mixed in.  (The kernels' rule takes it from there: include/kgwas_hip.h.)"""
+    z = _splitmix64(int(seed) & _M64)
+    z = _splitmix64(z ^ (int(epoch) & _M64))
+    return _splitmix64(z ^ (int(batch) & _M64))
+
+
+def fanout_words(seed: int, epoch: int, n_batches: int, device) -> torch.Tensor:
+    """int64 device tensor [n_batches]: the sample seeds of an epoch's batches (two's-complement view of the 64-bit words)."""
+    w = np.array([fanout_sample_word(seed, epoch, i) for i in range(n_batches)], dtype=np.uint64).view(np.int64)
+    return torch.from_numpy(w.copy()).to(device)
+
+
+def check_num_neighbors(num_neighbors) -> Optional[list]:
+    """None for the reference's [-1] * L, else the list of per-hop fan-outs (each -1 or >= 1); refuses what is not built."""
+    if isinstance(num_neighbors, dict):
+        raise NotImplementedError('per-edge-type fan-outs (the dict form of num_neighbors) are not supported: give one list')
+    ks = [int(k) for k in num_neighbors]
+    if any(k == 0 or k < -1 for k in ks):
+        raise ValueError(f'num_neighbors {ks}: every entry is -1 (all neighbours) or >= 1')
+    return ks if any(k != -1 for k in ks) else None
 
 
 def finish_sample(dg: DeviceGraph, buf: BatchBuffers, input_type: str, batch_size: int) -> SampledBatch:
@@ -525,10 +570,14 @@ def sample_full_graph(data: HeteroGraph, num_layers: int, device) -> SampledBatc
 class NeighborLoader:
     def __init__(self, data: HeteroGraph, num_neighbors: Sequence[int], input_nodes, batch_size: int = 512,
                  drop_last: bool = False, num_workers: int = 0, shuffle: bool = False, sampler=None,
-                 device=None, prefetch: bool = True, **kwargs):
-        if any(int(k) != -1 for k in num_neighbors):
-            raise NotImplementedError('only full-neighbourhood sampling ([-1]*L) is supported, as used at '
-                                      'kgwas/kgwas.py:99-113')
+                 device=None, prefetch: bool = True, seed: int = 0, replace: bool = False, **kwargs):
+        """``num_neighbors``: [-1] * L as the reference (kgwas/kgwas.py:99-113), or PyG's list form [k_1, ..., k_L] (each -1 or
+        >= 1; k_h in-edges per (node, relation) at hop h, uniformly without replacement).  A finite fan-out is redrawn every
+        epoch from (``seed``, epoch, batch index): ``set_epoch(e)`` names the epoch of the next pass, else every pass after the
+        first advances it by one."""
+        self.fanout = check_num_neighbors(num_neighbors)
+        if replace:
+            raise NotImplementedError('sampling with replacement is not supported')
         if shuffle:
             raise NotImplementedError('the reference never shuffles (kgwas/kgwas.py:93-94)')
         self.data = data
@@ -546,6 +595,15 @@ class NeighborLoader:
         self.prefetch = prefetch
         self._bufs = None
         self._stream = None
+        self.seed = int(seed)
+        self.epoch = 0
+        self._epoch_set = True                       # (the next pass runs at self.epoch; later passes advance it themselves)
+        self._words = None
+
+    def set_epoch(self, epoch: int):
+        """Epoch of the next pass over the loader (a finite fan-out draws from (seed, epoch, batch index))."""
+        self.epoch = int(epoch)
+        self._epoch_set = True
 
     def __len__(self):
         n = self.ids.numel()
@@ -563,17 +621,30 @@ class NeighborLoader:
 
     def _launch(self, i: int, buf: BatchBuffers):
         seeds = self.ids[i * self.batch_size:(i + 1) * self.batch_size]
+        word = self._words[i:i + 1] if self.fanout is not None else None      # (resident: the kernels read it where it is)
         if self._stream is not None:
             if buf.released is not None:
                 self._stream.wait_event(buf.released)
-            sample_into(self.dg, buf, seeds, self.seed_type, self._stream)
+            sample_into(self.dg, buf, seeds, self.seed_type, self._stream, fanout=self.fanout, sample_word=word)
         else:
-            sample_into(self.dg, buf, seeds, self.seed_type)
+            sample_into(self.dg, buf, seeds, self.seed_type, fanout=self.fanout, sample_word=word)
         return int(seeds.numel())
 
     def measure_caps(self, margin: float = 1.03, round_to: int = 64) -> BatchCaps:
         """Dry pass over every batch of this loader (the batch order is fixed, kgwas.py:93-94): the largest
-        node / edge / chunk counts, plus a safety margin, become the capacities of a static layout."""
+        node / edge / chunk counts, plus a safety margin, become the capacities of a static layout.
+
+        A loader with a finite fan-out redraws its batches every epoch, so what one pass saw bounds nothing.  Its capacities are
+        bounds that hold for EVERY draw: the dry pass is made over the FULL neighbourhoods of the same seeds (whatever a draw
+        reaches within h hops, the full expansion reaches within h hops, with all its in-edges: every cumulative node, edge
+        and chunk count of a draw is at most the full one), and each is then lowered to the analytic bound where that is
+        smaller -- new nodes of a type at hop h+1 <= sum over the relations leaving the type of (rows of the relation's
+        destination type new at hop h) x k_h, edges of hop h <= the same sum over all relations, chunks likewise with
+        ceil(k_h / KGW_CHUNK) per segment, never more nodes than the type has."""
+        if self.fanout is not None:
+            full = NeighborLoader(self.data, [-1] * self.num_layers, (self.input_type, self.ids), batch_size=self.batch_size,
+                                  drop_last=self.drop_last, device=self.device, prefetch=False)
+            return self._fanout_caps(full.measure_caps(margin, round_to), round_to)
         dg = self.dg
         sc, L = dg.schema, dg.num_layers
         node_off = np.zeros((sc.NT, L + 2), dtype=np.int64)
@@ -605,11 +676,52 @@ class NeighborLoader:
             node_off[t] = np.maximum.accumulate(node_off[t])
         return BatchCaps(node_off.tolist(), [up(e) for e in edges], [up(c) for c in chunks])
 
+    def _fanout_caps(self, full: BatchCaps, round_to: int) -> BatchCaps:
+        dg, ks = self.dg, self.fanout
+        sc, L = dg.schema, dg.num_layers
+        up = lambda v: int(-(-int(v) // round_to) * round_to)
+        node_off = [list(map(int, row)) for row in full.node_off]
+        new = [self.batch_size if t == self.seed_type else 0 for t in range(sc.NT)]     # rows new at hop h: upper bounds
+        edge_cum, chunk_cum, e_sum, c_sum = [], [], 0, 0
+        inf = float('inf')
+        for h in range(dg.n_hops):
+            k = ks[h]
+            segs = [new[int(sc.dst_type[r])] for r in range(sc.NR)]                        # segments of relation r at hop h
+            e_sum = inf if k < 0 else e_sum + sum(segs) * k
+            c_sum = inf if k < 0 else c_sum + sum(segs) * (-(-k // KGW_CHUNK))
+            edge_cum.append(e_sum)
+            chunk_cum.append(c_sum)
+            nxt = []
+            for t in range(sc.NT):
+                reach = inf if k < 0 else sum(segs[r] for r in range(sc.NR) if int(sc.src_type[r]) == t) * k
+                cum = min(node_off[t][h + 2], dg.n_nodes[t], up(node_off[t][h + 1] + reach) if reach != inf else inf)
+                node_off[t][h + 2] = int(max(cum, node_off[t][h + 1]))
+                nxt.append(int(min(reach, node_off[t][h + 2])))
+            new = nxt
+        for t in range(sc.NT):
+            for kk in range(dg.n_hops + 2, L + 2):
+                node_off[t][kk] = node_off[t][dg.n_hops + 1]
+        edges, chunks = list(full.edges), list(full.chunks)
+        for l in range(1, L + 1):
+            hd = min(L - l, dg.n_hops - 1)
+            if edge_cum[hd] != inf:
+                edges[l - 1] = min(int(edges[l - 1]), up(edge_cum[hd]))
+                chunks[l - 1] = min(int(chunks[l - 1]), up(chunk_cum[hd]))
+        return BatchCaps(node_off, edges, chunks)
+
     def __iter__(self):
         self._ensure()
         nb = len(self)
         if nb == 0:
             return
+        if self.fanout is not None:
+            if not self._epoch_set:
+                self.epoch += 1
+            self._epoch_set = False
+            self._words = fanout_words(self.seed, self.epoch, nb, self.device)
+            if self._stream is not None:
+                self._stream.wait_stream(torch.cuda.current_stream())      # (the words are uploaded on the consumer's stream)
+                self._words.record_stream(self._stream)
         nbuf = len(self._bufs)
         pending = {}
         if self.prefetch:
