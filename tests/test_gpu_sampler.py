@@ -76,77 +76,38 @@ def test_block_structures_are_consistent(small_kg, edge_case_graph, which):
     check_block_structures(next(iter(_loader(data, ids, len(ids), L=2))))
 
 
+def batch_view(batch):
+    """A sampled batch read back as the plain-array dict of tests/sampler_twin.py (``sample_twin`` returns the same keys)."""
+    from tests.sampler_twin import meta_to_dict
+    dg, m, buf = batch.dg, batch.meta, batch.buf
+    sc, L, H = dg.schema, dg.num_layers, dg.n_hops
+    ns, ne, nc = int(m.seg_end[H - 1]), int(m.edge_end[H - 1]), int(m.chunk_end[H - 1])
+    cpu = lambda t: t.cpu().numpy().astype(np.int64)
+    mcap = int(buf.c.multi_cap)
+    v = dict(meta=meta_to_dict(m), schema=sc, L=L, n_hops=H, short_mask=dg.short_type_mask,
+             rel_live=np.array([[dg.kg.rel_live[l][r] for r in range(sc.NR)] for l in range(L)], dtype=bool),
+             node_base=np.array(dg.node_base), g2l=cpu(buf.g2l),
+             n_id=[cpu(buf.n_id[dg.node_base[t]:dg.node_base[t] + int(m.node_off[t][H + 1])]) for t in range(sc.NT)],
+             seg_deg=cpu(buf.seg_deg[:ns]), seg_nch=cpu(buf.seg_nch[:ns]), seg_ptr=cpu(buf.seg_ptr[:ns + 1]),
+             seg_chptr=cpu(buf.seg_chptr[:ns + 1]), col_local=cpu(buf.col_local[:ne]), chunks=cpu(buf.chunks[:nc * 8]).reshape(-1, 8),
+             multi=[cpu(buf.multi[h * mcap * 4:(h * mcap + min(int(m.multi_cnt[h]), mcap)) * 4]).reshape(-1, 4) for h in range(H)],
+             t_ptr=[], t_edge=[], t_zrow=[], t_rel=[], flags=[])
+    for l in range(L):
+        nt = int(m.t_entries[l])
+        v['t_ptr'].append(cpu(buf.t_ptr[l][:int(m.t_base[l][sc.NT]) + 1]))
+        v['t_edge'].append(cpu(buf.t_edge[l][:nt]))
+        v['t_zrow'].append(cpu(buf.t_zrow[l][:nt]))
+        v['t_rel'].append(cpu(buf.t_rel[l][:nt]))
+        v['flags'].append(cpu(buf.t_cnt[l][:(int(m.src_base[l][sc.NT]) + 7) // 8]))
+    return v
+
+
 def check_block_structures(batch):
     """The body of test_block_structures_are_consistent on any sampled batch (tests/test_gpu_shard_kernels.py calls it on the
-    rank-local batches of the SNP-sharded mode)."""
-    from kgwas_amd._lib import KGW_CHUNK
-    dg, m, buf = batch.dg, batch.meta, batch.buf
-    sc = dg.schema
-    L = dg.num_layers
-    n_chunks_all = int(m.chunk_end[L - 1])
-    n_edges_all = int(m.edge_end[L - 1])
-    ch = buf.chunks[:n_chunks_all * 8].view(-1, 8).cpu().numpy()
-    col = buf.col_local[:n_edges_all].cpu().numpy()
-    assert n_chunks_all > 0 and n_edges_all > 0
-    # chunks tile [0, n_edges) in order
-    assert ch[0, 0] == 0 and ch[-1, 1] == n_edges_all
-    assert np.array_equal(ch[1:, 0], ch[:-1, 1])
-    assert np.all(ch[:, 1] - ch[:, 0] <= KGW_CHUNK) and np.all(ch[:, 1] > ch[:, 0])
-    # hub rows exist in this graph -> multi-chunk segments recorded
-    n_multi = sum(int(m.multi_cnt[h]) for h in range(L))
-    assert n_multi == len(np.unique(ch[ch[:, 5] > 1][:, 4]))
-    assert n_multi > 0, 'test graph should contain rows above KGW_CHUNK edges'
-    for l in range(1, L + 1):
-        nc, ne = int(m.n_chunks[l - 1]), int(m.n_edges[l - 1])
-        live = np.array([dg.kg.rel_live[l - 1][r] for r in range(sc.NR)], dtype=bool)
-        chl = ch[:nc]
-        chl = chl[live[chl[:, 3]]]
-        n_live_edges = int((chl[:, 1] - chl[:, 0]).sum())
-        assert int(m.t_entries[l - 1]) == n_live_edges
-        t_rows = int(m.t_base[l - 1][sc.NT])
-        tptr = buf.t_ptr[l - 1][:t_rows + 1].cpu().numpy()
-        tedge = buf.t_edge[l - 1][:n_live_edges].cpu().numpy()
-        tz = buf.t_zrow[l - 1][:n_live_edges].cpu().numpy()
-        trel = buf.t_rel[l - 1][:n_live_edges].cpu().numpy()
-        assert tptr[0] == 0 and tptr[-1] == n_live_edges and np.all(np.diff(tptr) >= 0)
-        # permutation of the live edge ids
-        expect = np.concatenate([np.arange(a, b) for a, b in chl[:, :2]]) if len(chl) else np.zeros(0, np.int64)
-        assert np.array_equal(np.sort(tedge), np.sort(expect))
-        # every entry sits in the row of its (source, slot) and carries its destination Z row
-        e2chunk = np.searchsorted(ch[:, 1], tedge, side='right')
-        rel = ch[e2chunk, 3]
-        row = ch[e2chunk, 2]
-        src_t = sc.src_type[rel]
-        dst_t = sc.dst_type[rel]
-        tb = np.array([m.t_base[l - 1][t] for t in range(sc.NT + 1)])
-        zb = np.array([m.z_base[l - 1][t] for t in range(sc.NT + 1)])
-        trow = tb[src_t] + col[tedge] * sc.R_src[src_t] + sc.slot_src[rel]
-        pos = np.arange(n_live_edges)
-        assert np.all(tptr[trow] <= pos) and np.all(pos < tptr[trow + 1])
-        assert np.array_equal(tz, zb[dst_t] + row * sc.R_dst[dst_t] + sc.slot_dst[rel])
-        assert np.array_equal(buf.t_rel[l - 1][:n_live_edges].cpu().numpy(), rel)      # relation id per entry
-        # octet flags (the backward's 8-rows-per-wavefront path): set exactly for the groups of 8 real source rows of one
-        # short-row type that hold no destination row and no row above 8 entries
-        n_src_rows = int(m.src_base[l - 1][sc.NT])
-        flags = buf.t_cnt[l - 1][:(n_src_rows + 7) // 8].cpu().numpy()
-        sb = np.array([m.src_base[l - 1][t] for t in range(sc.NT + 1)])
-        for o in range(len(flags)):
-            u0 = 8 * o
-            ty = int(np.searchsorted(sb[1:], u0, side='right'))
-            j0 = u0 - sb[ty]
-            ok = bool((dg.short_type_mask >> ty) & 1) and j0 + 8 <= int(m.n_src[l - 1][ty]) and \
-                not (sc.R_dst[ty] > 0 and j0 < int(m.n_rows[l - 1][ty]))
-            if ok:
-                Rs = int(sc.R_src[ty])
-                t0 = tb[ty] + j0 * Rs
-                ok = all(tptr[t0 + (q + 1) * Rs] - tptr[t0 + q * Rs] <= 8 for q in range(8))
-            assert bool(flags[o]) == ok, (l, o)
-        assert ne <= n_edges_all
-        # deterministic order: inside every src-major row the entries ascend by edge id (the structure is the edge list
-        # STABLY sorted by row: k_ts_scatter / k_ts_rows rank equal keys by lane order, nothing depends on arrival order)
-        row_of = np.repeat(np.arange(t_rows), np.diff(tptr))
-        same = row_of[1:] == row_of[:-1]
-        assert np.all(tedge[1:][same] > tedge[:-1][same])
+    rank-local batches of the SNP-sharded mode): the assertions live in tests/sampler_twin.py (check_structures), where the
+    sampler's numpy twin is held to them too."""
+    from tests.sampler_twin import check_structures
+    check_structures(batch_view(batch))
 
 
 def test_full_graph_block(edge_case_graph):
@@ -214,8 +175,11 @@ def test_coarse_bucket_sort_plans_build_the_same_structures(shift):
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, KGW_TS_MIN_SHIFT=str(shift))
+    # ... and, array for array against the numpy twin, the ladder graph at L = 2 with one launch geometry per key-block count
+    # (grid_blocks 1 / 256 / 0 -> 128 / 256 / 512 blocks): tests/test_gpu_sampler_exact.py
     p = subprocess.run([sys.executable, '-m', 'pytest', '-q', '-x', '-m', 'gpu', os.path.join(root, 'tests', 'test_gpu_sampler.py'),
-                        '-k', 'block_structures or matches_pyg_semantics'], cwd=root, env=env, stdout=subprocess.PIPE,
-                       stderr=subprocess.STDOUT, text=True, timeout=900)
+                        os.path.join(root, 'tests', 'test_gpu_sampler_exact.py'),
+                        '-k', 'block_structures or matches_pyg_semantics or (launch_geometry and (g0001 or g0256 or g0000))'],
+                       cwd=root, env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=900)
     assert p.returncode == 0, p.stdout[-3000:]
     assert ' passed' in p.stdout
