@@ -766,6 +766,40 @@ int kgw_readout_wmse_train_parts(const float* H, const float* w_lin, const float
                                  kgw_stream_t stream);
 int kgw_readout_train_fold(const KgwReadoutFold* fold, kgw_stream_t stream);
 
+/* The read-out node for T label columns on one shared trunk (HeteroGNN(out_channels = T), kgwas/model.py:25,50), 1 <= T <= 32
+ * (anything else: KGW_E_RANGE, nothing launched).  H [rows][128], W [T][128], b [T], n_id [n] global ids of the seeds,
+ * y [N][T] row-major float32 labels and w [N] float64 weights indexed by global id (ONE weight per node, shared by the columns):
+ *     pred[i][t] = [relu](<H[i], W[t]> + b[t])                                                         pred [n][T] row-major
+ *     loss       = 1 / (n T) * sum_i sum_t w[n_id[i]] * (pred[i][t] - y[n_id[i]][t])^2
+ * with the dot product, the residual, its square, the weight and the sum all in float64 (pred is the float64 dot product rounded
+ * once to float32), so the loss agrees with its float64 statement to ~1e-15 relative even where a prediction nearly meets its
+ * label; T = 1 is kgw_readout_wmse_*'s definition (which takes the residual in float32).  `relu` bit 0: ReLU on pred; bit 1 (backward): H is a ReLU output whose backward is folded in (dH *= H > 0).
+ * Backward: g[i][t] = grad_loss / (n T) * w * 2 (pred - y) (0 where the ReLU is off), dH[i] = sum_t g[i][t] W[t] (t ascending;
+ * rows n..rows-1 are written as zeros), dW[t] = sum_i g[i][t] H[i], db[t] = sum_i g[i][t].
+ * Order of the sums (no float atomics, so a rerun is bit-identical): one wavefront per seed, four seeds per block; seed i's loss
+ * term is its sum over t ascending (float64); the block's partial of dW / db is (g0 h0 + g1 h1) + (g2 h2 + g3 h3) over its four
+ * seeds; a second launch folds them: block t adds the partials of column t -- seven groups of blocks q = g, g + 7, ..., each in
+ * four interleaved accumulators (q, q+7, q+14, q+21 | +28), combined ((0+1)+(2+3)) + ((4+5)+6) -- and block 0 adds the n loss
+ * terms (256 strided accumulators, binary tree) and divides by n T.  The folds' order is the single-column calls' order; a seed's dot product is a float64 xor butterfly
+ * (1, 2, 4, ..., 32) over the lanes' two products, so T = 1 agrees with them to float32 rounding, not to the bit.
+ * Workspaces: terms / _fwd's scratch [n] doubles; scratch of the backward forms [ceil(n/4) * T * 129] floats.
+ *   kgw_readout_mt_pred        predictions only (HeteroGNN.forward, evaluation): one launch
+ *   kgw_readout_mt_pred_bwd    its backward from dpred [n][T]: dH, dW, db (relu: bit 1 only)
+ *   kgw_readout_wmse_mt_fwd    predictions and loss;  _bwd: dH, dW, db for any grad_loss;  two launches each
+ *   kgw_readout_wmse_mt_train  both for a loss gradient of exactly 1, in two launches (kgw_readout_wmse_train's form)            */
+int kgw_readout_mt_pred(const float* H, const float* W, const float* b, int32_t n, int32_t T, int32_t relu, float* pred,
+                        kgw_stream_t stream);
+int kgw_readout_mt_pred_bwd(const float* H, const float* W, const float* dpred, int32_t n, int64_t rows, int32_t T, int32_t relu,
+                            float* dH, float* dW, float* db, float* scratch, kgw_stream_t stream);
+int kgw_readout_wmse_mt_fwd(const float* H, const float* W, const float* b, const int32_t* n_id, const float* y, const double* w,
+                            int32_t n, int32_t T, int32_t relu, float* pred, double* loss, double* scratch, kgw_stream_t stream);
+int kgw_readout_wmse_mt_bwd(const float* H, const float* W, const float* pred, const int32_t* n_id, const float* y, const double* w,
+                            int32_t n, int64_t rows, int32_t T, int32_t relu, const double* grad_loss, float* dH, float* dW,
+                            float* db, float* scratch, kgw_stream_t stream);
+int kgw_readout_wmse_mt_train(const float* H, const float* W, const float* b, const int32_t* n_id, const float* y, const double* w,
+                              int32_t n, int64_t rows, int32_t T, int32_t relu, float* pred, double* loss, float* dH, float* dW,
+                              float* db, double* terms, float* scratch, kgw_stream_t stream);
+
 /* Self-test of the cross-lane reductions used by the aggregate kernels (one wavefront):
  * out_half[l] = sum over l's 32-lane half, out_wave[l] = sum over the wavefront,
  * out_steps[4][64] = the four intra-row DPP butterfly stages.                                  */

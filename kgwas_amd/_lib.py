@@ -11,6 +11,7 @@ KGW_MAX_LAYERS = 4
 KGW_CHUNK = 128
 KGW_TILE = 1024
 KGW_C = 128
+KGW_MT_MAX = 32          # label columns of the multi-trait read-out (kgw_readout_wmse_mt_*)
 PART_STRIDE = 132
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -166,7 +167,8 @@ EXPORTS = ['kgw_version', 'kgw_status_string', 'kgw_struct_sizes', 'kgw_sample_b
            'kgw_softmax_pack', 'kgw_softmax_merge', 'kgw_scatter_rows', 'kgw_linear_splitk', 'kgw_linear_splitk_workspace_floats', 'kgw_linear_splitk_ind', 'kgw_ind_colsum', 'kgw_linear_splitk_multi', 'kgw_ind_colsum_multi', 'kgw_fold_fwd', 'kgw_fold_bwd', 'kgw_relation_sums',
            'kgw_gat_aggregate_fwd', 'kgw_gat_aggregate_bwd_dst', 'kgw_gat_aggregate_bwd_src',
            'kgw_gather_rows', 'kgw_gather_rows_multi', 'kgw_scatter_relu_rows', 'kgw_scatter_relu_rows_workspace_floats', 'kgw_edge_alpha', 'kgw_debug_reduce', 'kgw_debug_reduce8', 'kgw_tn_gemm', 'kgw_tn_gemm_ex', 'kgw_tn_gemm_multi', 'kgw_tn_gemm_workspace_floats', 'kgw_tn_gemm_partial', 'kgw_tn_gemm_multi_partial', 'kgw_tn_split', 'kgw_tn_direct_rows', 'kgw_param_tail', 'kgw_tn_reduce_launch', 'kgw_tn_gemm_partial_ride', 'kgw_transform_bwd_ex', 'kgw_mlp2_bwd_first_partial', 'kgw_mlp2_bwd_first_packed', 'kgw_adam_fused', 'kgw_gemm3_partial', 'kgw_gemm3_flip', 'kgw_transform_bwd', 'kgw_grad_finish',
-           'kgw_linear', 'kgw_mlp2_fwd', 'kgw_mlp2w_fwd', 'kgw_mlp2_bwd_first', 'kgw_mlp2_bwd_first_workspace_floats', 'kgw_gemm3', 'kgw_gemm3_riders', 'kgw_gemm3_rider_blocks', 'kgw_gemm3_pack', 'kgw_gemm3_packed_bytes', 'kgw_gemm3_workspace_floats', 'kgw_adam', 'kgw_adam_notick', 'kgw_relvec_fwd', 'kgw_relvec_bwd', 'kgw_relvec_bwd_acc', 'kgw_relvec_fwd_multi', 'kgw_relvec_bwd_multi', 'kgw_wmse_fwd', 'kgw_wmse_bwd', 'kgw_readout_wmse_fwd', 'kgw_readout_wmse_bwd', 'kgw_readout_wmse_train', 'kgw_readout_wmse_train_parts', 'kgw_readout_train_fold', 'kgw_accumulate_stats', 'kgw_accumulate_stats_tick']
+           'kgw_linear', 'kgw_mlp2_fwd', 'kgw_mlp2w_fwd', 'kgw_mlp2_bwd_first', 'kgw_mlp2_bwd_first_workspace_floats', 'kgw_gemm3', 'kgw_gemm3_riders', 'kgw_gemm3_rider_blocks', 'kgw_gemm3_pack', 'kgw_gemm3_packed_bytes', 'kgw_gemm3_workspace_floats', 'kgw_adam', 'kgw_adam_notick', 'kgw_relvec_fwd', 'kgw_relvec_bwd', 'kgw_relvec_bwd_acc', 'kgw_relvec_fwd_multi', 'kgw_relvec_bwd_multi', 'kgw_wmse_fwd', 'kgw_wmse_bwd', 'kgw_readout_wmse_fwd', 'kgw_readout_wmse_bwd', 'kgw_readout_wmse_train', 'kgw_readout_wmse_train_parts', 'kgw_readout_train_fold', 'kgw_readout_mt_pred', 'kgw_readout_mt_pred_bwd', 'kgw_readout_wmse_mt_fwd', 'kgw_readout_wmse_mt_bwd',
+           'kgw_readout_wmse_mt_train', 'kgw_accumulate_stats', 'kgw_accumulate_stats_tick']
 
 _lib = None
 
@@ -300,6 +302,12 @@ def lib():
     L.kgw_readout_wmse_train.argtypes = [C.c_void_p] * 6 + [C.c_int32, C.c_int64, C.c_int32] + [C.c_void_p] * 8
     L.kgw_readout_wmse_train_parts.argtypes = [C.c_void_p] * 6 + [C.c_int32, C.c_int64, C.c_int32] + [C.c_void_p] * 9
     L.kgw_readout_train_fold.argtypes = [C.c_void_p, C.c_void_p]
+    if hasattr(L, 'kgw_readout_wmse_mt_train'):     # (absent from an older library named by KGW_LIB_PATH for an A/B run)
+        L.kgw_readout_mt_pred.argtypes = [C.c_void_p] * 3 + [C.c_int32] * 3 + [C.c_void_p] * 2
+        L.kgw_readout_mt_pred_bwd.argtypes = [C.c_void_p] * 3 + [C.c_int32, C.c_int64, C.c_int32, C.c_int32] + [C.c_void_p] * 5
+        L.kgw_readout_wmse_mt_fwd.argtypes = [C.c_void_p] * 6 + [C.c_int32] * 3 + [C.c_void_p] * 4
+        L.kgw_readout_wmse_mt_bwd.argtypes = [C.c_void_p] * 6 + [C.c_int32, C.c_int64, C.c_int32, C.c_int32] + [C.c_void_p] * 6
+        L.kgw_readout_wmse_mt_train.argtypes = [C.c_void_p] * 6 + [C.c_int32, C.c_int64, C.c_int32, C.c_int32] + [C.c_void_p] * 8
     L.kgw_accumulate_stats.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
     L.kgw_accumulate_stats_tick.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     _lib = L

@@ -306,3 +306,249 @@ extern "C" int kgw_readout_wmse_train(const float* H, const float* w_lin, const 
     KGW_LAUNCH_CHECK();
     return KGW_OK;
 }
+
+// ======================================================================================================
+// kgw_readout_mt_* / kgw_readout_wmse_mt_*: the read-out node for T label columns on ONE shared trunk (HeteroGNN(out_channels = T),
+// kgwas/model.py:25,50): pred[i][t] = [relu](<H[i], W[t]> + b[t]) and
+//     loss = 1 / (n T) * sum_i sum_t w[n_id[i]] * (pred[i][t] - y[n_id[i]][t])^2      (float64 throughout: see below).
+// One wavefront per seed, four per block, as in the single-column node above: a lane holds its two columns of H[i] ONCE and walks the
+// T rows of W in LDS (<= 16 KB; a lane's float2 of a row: 32 lanes x 8 B = one conflict-free 256-B bank row per half), reusing the
+// row for the T dot products and for dH[i] = sum_t g[i][t] W[t] (t ascending).  Lane t of the wavefront carries column t's label,
+// bias, prediction and d prediction, so the per-seed global traffic is one coalesced access each.  The block's weight-gradient
+// partial [T][129] (128 columns + the bias term) is (g0 h0 + g1 h1) + (g2 h2 + g3 h3) of its four seeds; a second launch of T blocks
+// folds the partials of column t in k_readout_fold's order (seven row groups, four interleaved accumulators, one tree) and block 0
+// adds up the per-seed loss terms in k_fold_f64's order.  No float atomics: reruns are bit-identical.
+// The forward's dot product, the residual and its square are float64 (the float32 products are exact in it; xor butterfly 1, 2, ...,
+// 32, so every lane holds the same bits), and pred is that sum rounded once to float32.  Where a prediction nearly meets its label the
+// residual is the small difference of two large numbers, and a float32 dot product's rounding (~1e-7 |pred|) would show in the loss at
+// 1e-7 |pred| / |residual|; in float64 the loss agrees with its float64 statement to rounding of the sum.  The gradients take the
+// residual rounded to float32.  T = 1 therefore agrees with the single-column node to float32 rounding, not to the bit.
+// ======================================================================================================
+namespace {
+
+constexpr int KGW_MT_MAX = 32;                      // T <= 32: one lane of a 32-lane half per column, W <= 16 KB of LDS
+enum { KGW_MT_FWD = 0, KGW_MT_TRAIN = 1, KGW_MT_BWD = 2, KGW_MT_BWD_PRED = 3 };
+
+struct KgwMtArgs {
+    const float* H; const float* W; const float* b; const int32_t* n_id; const float* y; const double* w;
+    const float* pred_in;               // _BWD: the forward's predictions;  _BWD_PRED: d loss / d pred [n][T]
+    const double* gloss;                // _BWD: the loss gradient
+    float* pred; double* terms; float* dH; float* part;
+    int64_t rows;
+    int n, T, relu;
+};
+
+__device__ __forceinline__ float kgw_lane_value(float v, int lane_uniform) {
+    return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), lane_uniform));
+}
+
+__device__ __forceinline__ double kgw_wave_allsum_f64(double v) {
+    for (int o = 1; o < 64; o <<= 1) v += __shfl_xor(v, o);
+    return v;
+}
+
+template <int MODE>
+__global__ void __launch_bounds__(256) k_readout_mt(const KgwMtArgs a) {
+    __shared__ float sW[KGW_MT_MAX * KGW_C];
+    __shared__ float sH[4][KGW_C + 1];
+    __shared__ float sG[4][KGW_MT_MAX];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t i = (int64_t)blockIdx.x * 4 + wave;
+    const int T = a.T, n = a.n;
+    if ((int64_t)blockIdx.x * 4 >= n) {                   // a block without seeds: its rows of dH are zero, it holds no partial
+        if (MODE != KGW_MT_FWD && i < a.rows) ((float2*)(a.dH + i * KGW_C))[lane] = make_float2(0.f, 0.f);
+        return;
+    }
+    for (int q = threadIdx.x; q < T * (KGW_C / 2); q += 256) ((float2*)sW)[q] = ((const float2*)a.W)[q];
+    __syncthreads();
+    float2 h2 = make_float2(0.f, 0.f);
+    float g_mine = 0.f;                                    // lane t: d loss / d (pre-activation of column t) of this seed
+    if (i < n) {
+        h2 = ((const float2*)(a.H + i * KGW_C))[lane];
+        const bool labelled = MODE == KGW_MT_TRAIN || MODE == KGW_MT_BWD || (MODE == KGW_MT_FWD && a.y != nullptr);
+        const bool mine = lane < T;
+        double wg = 0.0;
+        float y_mine = 0.f, b_mine = 0.f, in_mine = 0.f, p_mine = 0.f, scale = 0.f;
+        if (labelled) {
+            const int g = a.n_id[i];
+            wg = a.w[g];
+            if (mine) y_mine = a.y[(int64_t)g * T + lane];
+        }
+        if ((MODE == KGW_MT_FWD || MODE == KGW_MT_TRAIN) && mine) b_mine = a.b[lane];
+        if ((MODE == KGW_MT_BWD || MODE == KGW_MT_BWD_PRED) && mine) in_mine = a.pred_in[i * T + lane];
+        if (MODE == KGW_MT_TRAIN) scale = (float)(1.0 / ((double)n * (double)T) * wg);
+        if (MODE == KGW_MT_BWD) scale = (float)(a.gloss[0] / ((double)n * (double)T) * wg);
+        double term = 0.0;
+        float2 dh = make_float2(0.f, 0.f);
+        for (int t = 0; t < T; ++t) {
+            const float2 w2 = ((const float2*)(sW + t * KGW_C))[lane];
+            float p = 0.f, dp = 0.f;
+            double p64 = 0.0;
+            if (MODE == KGW_MT_FWD || MODE == KGW_MT_TRAIN) {
+                p64 = kgw_wave_allsum_f64(fma((double)h2.x, (double)w2.x, (double)h2.y * (double)w2.y)) +
+                      (double)kgw_lane_value(b_mine, t);
+                if (a.relu & 1) p64 = fmax(p64, 0.0);
+                p = (float)p64;
+                if (lane == t) p_mine = p;
+            } else {
+                p = kgw_lane_value(in_mine, t);
+                p64 = (double)p;
+            }
+            if (MODE == KGW_MT_BWD_PRED) {
+                dp = p;                                    // (the caller's ReLU, if any, is its own autograd node)
+            } else if (labelled) {
+                const double d64 = p64 - (double)kgw_lane_value(y_mine, t);
+                const float d = (float)d64;
+                if (MODE != KGW_MT_BWD) term += wg * (d64 * d64);
+                if (MODE != KGW_MT_FWD) {
+                    dp = scale * (2.0f * d);
+                    if ((a.relu & 1) && !(p > 0.f)) dp = 0.f;
+                }
+            }
+            if (MODE != KGW_MT_FWD) {
+                dh.x = fmaf(dp, w2.x, dh.x); dh.y = fmaf(dp, w2.y, dh.y);
+                if (lane == t) g_mine = dp;
+            }
+        }
+        if ((MODE == KGW_MT_FWD || MODE == KGW_MT_TRAIN) && mine) a.pred[i * T + lane] = p_mine;
+        if ((MODE == KGW_MT_FWD || MODE == KGW_MT_TRAIN) && labelled && lane == 0) a.terms[i] = term;
+        if (MODE != KGW_MT_FWD) {
+            // (bit 1 of `relu`: H itself is the output of a ReLU whose backward the caller folds in here: dH *= (H > 0))
+            const bool mk = (a.relu & 2) != 0;
+            ((float2*)(a.dH + i * KGW_C))[lane] = make_float2((!mk || h2.x > 0.f) ? dh.x : 0.f, (!mk || h2.y > 0.f) ? dh.y : 0.f);
+        }
+    } else if (MODE != KGW_MT_FWD && i < a.rows) {
+        ((float2*)(a.dH + i * KGW_C))[lane] = make_float2(0.f, 0.f);
+    }
+    if (MODE == KGW_MT_FWD) return;
+    sH[wave][2 * lane] = h2.x; sH[wave][2 * lane + 1] = h2.y;          // (a wavefront past the seeds: zeros times zeros)
+    if (lane == 0) sH[wave][KGW_C] = 1.0f;                              // the bias column: g * 1
+    if (lane < KGW_MT_MAX) sG[wave][lane] = g_mine;
+    __syncthreads();
+    float* part = a.part + (int64_t)blockIdx.x * T * (KGW_C + 1);
+    for (int q = threadIdx.x; q < T * (KGW_C + 1); q += 256) {
+        const int t = q / (KGW_C + 1), c = q - t * (KGW_C + 1);
+        part[q] = (__fmul_rn(sG[0][t], sH[0][c]) + __fmul_rn(sG[1][t], sH[1][c])) +
+                  (__fmul_rn(sG[2][t], sH[2][c]) + __fmul_rn(sG[3][t], sH[3][c]));
+    }
+}
+
+// block t: d W[t] [128] and d b[t] from the per-block partials [nb][T][129] (k_readout_fold's order); block 0 also the loss from the
+// per-seed terms (k_fold_f64's order, divided by n T).  part == nullptr: the loss only;  terms == nullptr: the gradients only.
+__global__ void __launch_bounds__(1024) k_readout_mt_fold(const float* __restrict__ part, int nb, int T, const double* __restrict__ terms,
+                                                          int n, float* __restrict__ dW, float* __restrict__ db,
+                                                          double* __restrict__ loss) {
+    __shared__ float sm[7][KGW_C + 1];
+    __shared__ double sd[256];
+    const int c = threadIdx.x % (KGW_C + 1), g = threadIdx.x / (KGW_C + 1), t = blockIdx.x;
+    const int64_t ld = (int64_t)T * (KGW_C + 1);
+    const bool with_loss = terms != nullptr && t == 0;                   // (uniform over the block)
+    if (part != nullptr && g < 7) {
+        const float* p = part + (int64_t)t * (KGW_C + 1) + c;
+        float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+        int q = g;
+        for (; q + 21 < nb; q += 28) {
+            a0 += p[(int64_t)q * ld];        a1 += p[(int64_t)(q + 7) * ld];
+            a2 += p[(int64_t)(q + 14) * ld]; a3 += p[(int64_t)(q + 21) * ld];
+        }
+        for (; q < nb; q += 7) a0 += p[(int64_t)q * ld];
+        sm[g][c] = (a0 + a1) + (a2 + a3);
+    }
+    if (with_loss && threadIdx.x < 256) {
+        double acc = 0.0;
+        for (int q = threadIdx.x; q < n; q += 256) acc += terms[q];
+        sd[threadIdx.x] = acc;
+    }
+    __syncthreads();
+    if (with_loss) {
+        for (int o = 128; o > 0; o >>= 1) {
+            if (threadIdx.x < o) sd[threadIdx.x] += sd[threadIdx.x + o];
+            __syncthreads();
+        }
+        if (threadIdx.x == 0) loss[0] = sd[0] / ((double)n * (double)T);
+    }
+    if (part != nullptr && g == 0) {
+        const float s = ((sm[0][c] + sm[1][c]) + (sm[2][c] + sm[3][c])) + ((sm[4][c] + sm[5][c]) + sm[6][c]);
+        if (c < KGW_C) dW[(int64_t)t * KGW_C + c] = s; else db[t] = s;
+    }
+}
+
+inline int kgw_mt_range(int32_t n, int64_t rows, int32_t T) {
+    return (n <= 0 || rows < n || T < 1 || T > KGW_MT_MAX || (rows + 3) / 4 > 0x7fffffff) ? KGW_E_RANGE : KGW_OK;
+}
+
+}  // namespace
+
+extern "C" int kgw_readout_mt_pred(const float* H, const float* W, const float* b, int32_t n, int32_t T, int32_t relu, float* pred,
+                                   kgw_stream_t stream_) {
+    if (!H || !W || !b || !pred) return KGW_E_NULL;
+    if (kgw_mt_range(n, n, T)) return KGW_E_RANGE;
+    KgwMtArgs a{};
+    a.H = H; a.W = W; a.b = b; a.pred = pred; a.rows = n; a.n = n; a.T = T; a.relu = relu;
+    k_readout_mt<KGW_MT_FWD><<<(n + 3) / 4, 256, 0, (hipStream_t)stream_>>>(a);
+    KGW_LAUNCH_CHECK();
+    return KGW_OK;
+}
+
+extern "C" int kgw_readout_mt_pred_bwd(const float* H, const float* W, const float* dpred, int32_t n, int64_t rows, int32_t T,
+                                       int32_t relu, float* dH, float* dW, float* db, float* scratch, kgw_stream_t stream_) {
+    if (!H || !W || !dpred || !dH || !dW || !db || !scratch) return KGW_E_NULL;
+    if (kgw_mt_range(n, rows, T)) return KGW_E_RANGE;
+    hipStream_t st = (hipStream_t)stream_;
+    KgwMtArgs a{};
+    a.H = H; a.W = W; a.pred_in = dpred; a.dH = dH; a.part = scratch; a.rows = rows; a.n = n; a.T = T; a.relu = relu & 2;
+    k_readout_mt<KGW_MT_BWD_PRED><<<(unsigned)((rows + 3) / 4), 256, 0, st>>>(a);
+    KGW_LAUNCH_CHECK();
+    k_readout_mt_fold<<<T, 1024, 0, st>>>(scratch, (n + 3) / 4, T, nullptr, n, dW, db, nullptr);
+    KGW_LAUNCH_CHECK();
+    return KGW_OK;
+}
+
+extern "C" int kgw_readout_wmse_mt_fwd(const float* H, const float* W, const float* b, const int32_t* n_id, const float* y,
+                                       const double* w, int32_t n, int32_t T, int32_t relu, float* pred, double* loss,
+                                       double* scratch, kgw_stream_t stream_) {
+    if (!H || !W || !b || !n_id || !y || !w || !pred || !loss || !scratch) return KGW_E_NULL;
+    if (kgw_mt_range(n, n, T)) return KGW_E_RANGE;
+    hipStream_t st = (hipStream_t)stream_;
+    KgwMtArgs a{};
+    a.H = H; a.W = W; a.b = b; a.n_id = n_id; a.y = y; a.w = w; a.pred = pred; a.terms = scratch; a.rows = n; a.n = n; a.T = T;
+    a.relu = relu;
+    k_readout_mt<KGW_MT_FWD><<<(n + 3) / 4, 256, 0, st>>>(a);
+    KGW_LAUNCH_CHECK();
+    k_readout_mt_fold<<<1, 1024, 0, st>>>(nullptr, 0, T, scratch, n, nullptr, nullptr, loss);
+    KGW_LAUNCH_CHECK();
+    return KGW_OK;
+}
+
+extern "C" int kgw_readout_wmse_mt_bwd(const float* H, const float* W, const float* pred, const int32_t* n_id, const float* y,
+                                       const double* w, int32_t n, int64_t rows, int32_t T, int32_t relu, const double* grad_loss,
+                                       float* dH, float* dW, float* db, float* scratch, kgw_stream_t stream_) {
+    if (!H || !W || !pred || !n_id || !y || !w || !grad_loss || !dH || !dW || !db || !scratch) return KGW_E_NULL;
+    if (kgw_mt_range(n, rows, T)) return KGW_E_RANGE;
+    hipStream_t st = (hipStream_t)stream_;
+    KgwMtArgs a{};
+    a.H = H; a.W = W; a.pred_in = pred; a.n_id = n_id; a.y = y; a.w = w; a.gloss = grad_loss; a.dH = dH; a.part = scratch;
+    a.rows = rows; a.n = n; a.T = T; a.relu = relu;
+    k_readout_mt<KGW_MT_BWD><<<(unsigned)((rows + 3) / 4), 256, 0, st>>>(a);
+    KGW_LAUNCH_CHECK();
+    k_readout_mt_fold<<<T, 1024, 0, st>>>(scratch, (n + 3) / 4, T, nullptr, n, dW, db, nullptr);
+    KGW_LAUNCH_CHECK();
+    return KGW_OK;
+}
+
+extern "C" int kgw_readout_wmse_mt_train(const float* H, const float* W, const float* b, const int32_t* n_id, const float* y,
+                                         const double* w, int32_t n, int64_t rows, int32_t T, int32_t relu, float* pred,
+                                         double* loss, float* dH, float* dW, float* db, double* terms, float* scratch,
+                                         kgw_stream_t stream_) {
+    if (!H || !W || !b || !n_id || !y || !w || !pred || !loss || !dH || !dW || !db || !terms || !scratch) return KGW_E_NULL;
+    if (kgw_mt_range(n, rows, T)) return KGW_E_RANGE;
+    hipStream_t st = (hipStream_t)stream_;
+    KgwMtArgs a{};
+    a.H = H; a.W = W; a.b = b; a.n_id = n_id; a.y = y; a.w = w; a.pred = pred; a.terms = terms; a.dH = dH; a.part = scratch;
+    a.rows = rows; a.n = n; a.T = T; a.relu = relu;
+    k_readout_mt<KGW_MT_TRAIN><<<(unsigned)((rows + 3) / 4), 256, 0, st>>>(a);
+    KGW_LAUNCH_CHECK();
+    k_readout_mt_fold<<<T, 1024, 0, st>>>(scratch, (n + 3) / 4, T, terms, n, dW, db, loss);
+    KGW_LAUNCH_CHECK();
+    return KGW_OK;
+}

@@ -764,7 +764,8 @@ class GraphEvalStep:
         self.bufs = [BatchBuffers(self.dg, grid) for _ in range(2 if self.n_batches > 1 else 1)]
         self.meta = self.dg.static_meta()
         self.seeds = torch.zeros(bs, dtype=torch.int64, device=dev)
-        self.out = torch.zeros(self.n_batches * bs, device=dev)
+        self.T = int(model.lin.out_features)              # label columns: predictions [n] for 1, [n, T] beyond
+        self.out = torch.zeros(self.n_batches * bs, device=dev) if self.T == 1 else torch.zeros(self.n_batches * bs, self.T, device=dev)
         self.pred = [None, None]
         self.graphs = [None, None]
         self.sample_graphs = [None, None]
@@ -775,7 +776,8 @@ class GraphEvalStep:
     def _forward(self, cur: int):
         batch = SampledBatch(self.dg, self.bufs[cur], self.meta, self.input_type, self.batch_size, static=True)
         with torch.no_grad():
-            return self.model(batch.x_dict, batch.edge_index_dict, self.batch_size).reshape(-1)
+            out = self.model(batch.x_dict, batch.edge_index_dict, self.batch_size)
+            return out.reshape(-1) if self.T == 1 else out
 
     def _sample_now(self, which: int, i: int):
         b = self.batch_size
@@ -807,7 +809,7 @@ class GraphEvalStep:
             self.sample_graphs[cur] = gs
 
     def run(self) -> torch.Tensor:
-        """Predictions of every input node, in input order (device tensor [n])."""
+        """Predictions of every input node, in input order (device tensor [n]; [n, T] for out_channels = T > 1)."""
         b, main = self.batch_size, torch.cuda.current_stream()
         self._sample_now(0, 0)
         err = torch.zeros(1, dtype=torch.int32, device=self.out.device)

@@ -49,11 +49,19 @@ class KGWAS:
         self.exp_name = exp_name
 
     def initialize_model(self, gnn_num_layers=2, gnn_hidden_dim=128, gnn_backbone='GAT', gnn_aggr='sum',
-                         gat_num_head=1, no_relu=False):
+                         gat_num_head=1, no_relu=False, out_channels=1):
+        """``out_channels`` (extra, default 1 = the reference, kgwas.py:52): T > 1 reads ONE shared trunk out into T label columns
+        (``data['SNP'].y`` [N, T], KGWAS_Data.from_synthetic(n_traits=T)) -- a shared-trunk multi-task model, not T independent
+        models.  It enters ``config`` only when it is not 1, so the config.pkl of a single-trait run is what it always was."""
         self.config = {'gnn_num_layers': gnn_num_layers, 'gnn_hidden_dim': gnn_hidden_dim,
                        'gnn_backbone': gnn_backbone, 'gnn_aggr': gnn_aggr, 'gat_num_head': gat_num_head}
+        out_channels = int(out_channels)
+        if not 1 <= out_channels <= 32:
+            raise NotImplementedError(f'out_channels = {out_channels}: the read-out kernels take 1 to 32 label columns')
+        if out_channels != 1:
+            self.config['out_channels'] = out_channels
         self.gnn_num_layers = gnn_num_layers
-        self.model = HeteroGNN(self.data.data, gnn_hidden_dim, 1, gnn_num_layers, gnn_backbone, gnn_aggr,
+        self.model = HeteroGNN(self.data.data, gnn_hidden_dim, out_channels, gnn_num_layers, gnn_backbone, gnn_aggr,
                                self.data.snp_init_dim_size, self.data.gene_init_dim_size,
                                self.data.go_init_dim_size, gat_num_head, no_relu=no_relu).to(self.device)
 
@@ -118,6 +126,9 @@ class KGWAS:
         batches of the reference's order and owns the SNPs of one id range; validation / test / inference predictions are
         computed shard-wise and summed, so every rank sees the same metrics and keeps the same best model."""
         from .shard import ShardedTrainer
+        if self.model.lin.out_features != 1:
+            raise NotImplementedError("out_channels > 1 (multi-trait labels) is not available with parallelism='shard': the "
+                                      "sharded step's read-out and loss are single-column; use parallelism='seed'")
         rank, world = kdist.rank_world()
         if world > 1:
             kdist.broadcast_params(self.model)
@@ -226,13 +237,14 @@ class KGWAS:
             if graph_step is not None:
                 graph_step.check()
             val_res = evaluate_minibatch_clean(self.val_loader, self.model, self.device)
-            val_metrics = compute_metrics(val_res, False, -1, -1, F.mse_loss)
+            val_metrics = self._metrics(val_res)
             print_sys('Epoch {}: Validation MSE: {:.4f} Validation Pearson: {:.4f}. '.format(
                 ep + 1, val_metrics['mse'], val_metrics['pearsonr']))
             self.val_metrics = val_metrics
             if self.wandb:
                 for i, j in val_metrics.items():
-                    self.wandb.log({'val_' + i: j})
+                    if i != 'per_trait':
+                        self.wandb.log({'val_' + i: j})
             if val_metrics['pearsonr'] > min_val:                    # kgwas.py:170-173
                 min_val = val_metrics['pearsonr']
                 self.best_model = deepcopy(self.model)
@@ -241,13 +253,39 @@ class KGWAS:
             print_sys('Saving models to ' + os.path.join(save_model_path, save_name))
             save_model(self.best_model, self.config, os.path.join(save_model_path, save_name))
         test_res = evaluate_minibatch_clean(self.test_loader, self.best_model, self.device)
-        self.test_metrics = compute_metrics(test_res, False, -1, -1, F.mse_loss)
+        self.test_metrics = self._metrics(test_res)
         if self.wandb:
             for i, j in self.test_metrics.items():
-                self.wandb.log({'test_' + i: j})
+                if i != 'per_trait':
+                    self.wandb.log({'test_' + i: j})
         infer_res = evaluate_minibatch_clean(self.infer_loader, self.best_model, self.device)
+        if self.model.lin.out_features != 1:
+            return self._postprocess_traits(infer_res['pred'], save_name)
         self.data.lr_uni['pred'] = infer_res['pred']                 # kgwas.py:191
         self._postprocess(save_name, save_best_model and rank == 0)
+
+    def _metrics(self, res):
+        """compute_metrics of one evaluation; with T > 1 label columns: the metrics of every column under 'per_trait' and their
+        means under the usual keys -- the best model is the one with the highest MEAN validation Pearson over the traits."""
+        if self.model.lin.out_features == 1:
+            return compute_metrics(res, False, -1, -1, F.mse_loss)
+        per = [compute_metrics({'pred': res['pred'][:, t], 'truth': res['truth'][:, t]}, False, -1, -1, F.mse_loss)
+               for t in range(res['pred'].shape[1])]
+        return {'mse': float(np.mean([m['mse'] for m in per])), 'pearsonr': float(np.mean([m['pearsonr'] for m in per])),
+                'per_trait': per}
+
+    def _postprocess_traits(self, pred, save_name):
+        """``_postprocess`` once per label column: trait t's summary statistics (KGWAS_Data.trait_table) with column t of the
+        predictions, written to <save_name>_trait<t>_pred.csv; ``kgwas_res`` becomes the list of the T tables."""
+        base = self.data.lr_uni
+        tables = []
+        for t in range(pred.shape[1]):
+            self.data.lr_uni = self.data.trait_table(t)
+            self.data.lr_uni['pred'] = pred[:, t]
+            self._postprocess(f'{save_name}_trait{t}', False)
+            tables.append(self.kgwas_res)
+        self.data.lr_uni = base
+        self.kgwas_res = tables
 
     def get_network_weight(self):
         """The graph-side half of kgwas/kgwas.py:268-273: per-edge raw attention weights of the best model."""

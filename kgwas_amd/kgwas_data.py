@@ -142,13 +142,16 @@ class KGWAS_Data:
     @classmethod
     def from_synthetic(cls, scale=1.0, seed=1, mode='fast', data_path='/tmp/kgwas_synth', n_labelled=None,
                        gwas_kind='causal', sample_size=None, feat_dims=None, split=True, snp_scale=1.0,
-                       sample_edges=False, sample_ratio=1.0, node_counts=None):
+                       sample_edges=False, sample_ratio=1.0, node_counts=None, n_traits=1):
         """SynthKG + synthetic summary statistics through the same pipeline as the real files.
         ``gwas_kind`` mirrors the reference's four label sources (BASELINE.json configs): 'causal' / 'null' = the
         simulations of load_simulation_gwas (N = 5000, kgwas_data.py:275-294), 'subsample' = load_gwas_subsample
         (N = ``sample_size``, default 10000, :367-389), 'full_cohort' = load_full_gwas (N = 387113, :341-365).
         ``sample_edges`` / ``sample_ratio``: load_kg's edge thinning (:261-268) -- int(E * ratio) edges of every ORIGINAL
-        relation, seeded permutation, before ToUndirected + AddSelfLoops."""
+        relation, seeded permutation, before ToUndirected + AddSelfLoops.
+        ``n_traits`` = T > 1: labels [N, T] for a multi-trait model (KGWAS.initialize_model(out_channels=T)) -- column 0 is the
+        single-trait label vector, column t the chi-square / P draw of make_synth_gwas under the seed ``seed + 7919 * t``, over the
+        SAME labelled SNPs, LD scores and split."""
         import pandas as pd
         from .synth import FEAT_DIMS, make_synth_edges, make_synth_gwas
         self = cls(data_path)
@@ -181,6 +184,12 @@ class KGWAS_Data:
         self.lr_uni = pd.DataFrame({'#CHROM': 1, 'ID': [f'rs{i}' for i in g['ids']], 'P': g['P'], 'N': g['N'],
                                     'chi': g['y']})
         self._synth_ld = (g['ld_score'], g['w_ld_score'])
+        n_traits = int(n_traits)
+        if n_traits < 1:
+            raise ValueError('n_traits must be at least 1')
+        if n_traits > 1:            # (a draw's y / P belong to positions of the labelled list, whichever ids the draw itself chose)
+            extra = [make_synth_gwas(n_snp, n_labelled, seed + 7919 * t, gwas_kind, sample_size) for t in range(1, n_traits)]
+            self._trait_cols = [{'chi': e['y'], 'P': e['P']} for e in extra]
         self.idx2id['SNP'] = _IdentityMap(n_snp, 'rs')
         self.id2idx['SNP'] = _IdentityMap(n_snp, 'rs', inverse=True)
         self.sample_size = sample_size
@@ -334,6 +343,14 @@ class KGWAS_Data:
         y_snp[train_ids] = torch.tensor(y_train).float()
         y_snp[val_ids] = torch.tensor(y_val).float()
         y_snp[test_ids] = torch.tensor(y_test).float()
+        extra = getattr(self, '_trait_cols', None)
+        if extra:                                   # multi-trait: [N, T], column 0 = the vector above
+            cols = [y_snp]
+            for e in extra:
+                c = torch.zeros_like(y_snp) - 1
+                c[torch.from_numpy(np.asarray(self.all_ids))] = torch.tensor(np.asarray(e['chi'])).float()
+                cols.append(c)
+            y_snp = torch.stack(cols, 1).contiguous()
         self.data['SNP'].y = y_snp
         for t in self.data.node_types:
             self.data[t].n_id = torch.arange(self.data[t].x.shape[0])
@@ -342,6 +359,15 @@ class KGWAS_Data:
         self.data.test_mask = test_ids
         self.data.all_mask = self.all_ids
         self.data._extra.pop('_device_graphs', None)   # labels changed: rebuild resident copies lazily
+
+    def trait_table(self, t: int):
+        """A copy of ``lr_uni`` carrying trait t's summary statistics (chi, y, P); t = 0 is ``lr_uni`` itself."""
+        df = self.lr_uni.copy()
+        extra = getattr(self, '_trait_cols', None) or []
+        if t:
+            df['chi'] = df['y'] = np.asarray(extra[t - 1]['chi'])
+            df['P'] = np.asarray(extra[t - 1]['P'])
+        return df
 
     def get_pheno_list(self):
         return {'large_cohort': [],

@@ -637,11 +637,11 @@ class HeteroGNN(nn.Module):
 
     def _readout(self, h):
         """self.lin(h) (kgwas/model.py:50,83-86).  For the reference's out_channels == 1 (kgwas.py:52) the Linear(128 -> 1) is a
-        row-wise dot product: elementwise multiply + row sum, not a library GEMV."""
+        row-wise dot product: elementwise multiply + row sum, not a library GEMV; out_channels = T > 1 (a shared trunk read out into
+        T label columns) runs the read-out kernel of the multi-trait loss node without the loss."""
         if self.lin.out_features == 1:
             return (h * self.lin.weight.view(1, -1)).sum(1, keepdim=True) + self.lin.bias
-        ops.LIBRARY_GEMM.note('read-out', h.shape[0], h.shape[1], self.lin.out_features)
-        return self.lin(h)
+        return ops.readout_linear(h, self.lin.weight, self.lin.bias)      # out_channels = T <= 32: kgw_readout_mt_pred
 
     @torch.no_grad()
     def hot_path_attention(self, batch: SampledBatch):
@@ -656,15 +656,16 @@ class HeteroGNN(nn.Module):
     def forward_loss(self, x_dict, edge_index_dict, batch_size, n_id, y_all, w_all, mlp_out=None, unit_grad=False):
         """The training step's forward (kgwas/kgwas.py:137-145): HeteroGNN.forward followed by
         mean(w_all[n_id] * (pred - y_all[n_id])**2), with the read-out Linear + ReLU (model.py:86) and the loss fused
-        into one node.  Returns (loss [float64 scalar], pred [batch_size]).  ``mlp_out`` (list): receives the feature MLPs'
+        into one node.  Returns (loss [float64 scalar], pred [batch_size]) -- with ``out_channels = T > 1`` (a shared trunk read out
+        into T label columns, ``y_all`` [N,T]) the mean runs over seeds and columns and pred is [batch_size, T].  ``mlp_out`` (list): receives the feature MLPs'
         output tensors -- the cut between the two halves of a backward pass whose first half's gradients are all-reduced
         while the second half runs (multi-GPU GraphTrainStep).  ``unit_grad``: the caller will backpropagate exactly
         ``loss.backward()`` (gradient 1): the read-out node then does its forward and backward in two launches."""
         batch: Optional[SampledBatch] = getattr(x_dict, 'kgw_batch', None) or getattr(edge_index_dict, 'kgw_batch', None)
         if batch is None:
             batch = self._block_from_coo(x_dict, edge_index_dict)
-        if self.lin.out_features != 1:
-            raise NotImplementedError('the fused read-out + loss is for out_channels == 1 (kgwas/kgwas.py:52)')
+        if not 1 <= self.lin.out_features <= 32:
+            raise NotImplementedError('the fused read-out + loss takes out_channels from 1 (kgwas/kgwas.py:52) to 32')
         hbuf, blocks = self._layer_input(batch, 1)
         gat = self.backbone == 'GAT' and self.aggr in ('sum', 'mean')
         prep = None

@@ -2412,11 +2412,122 @@ class _ReadoutWeightedMSE(torch.autograd.Function):
         return dH, dw, db, None, None, None, None, None, None, None
 
 
+class _ReadoutWeightedMSEMulti(torch.autograd.Function):
+    """_ReadoutWeightedMSE for T > 1 label columns (HeteroGNN(out_channels=T)): loss = mean over seeds AND columns of
+    w[n_id] * ([relu](H[:n] @ W^T + b) - y[n_id])**2, kgw_readout_wmse_mt_*.  Both launches are issued where the node is -- no
+    deferred fold, no rider: d W and d b reach autograd as finished tensors, which GradSink and kgw_adam_fused take like any other."""
+
+    @staticmethod
+    def forward(ctx, H, W, b, n_id, y_all, w_all, n, relu, h_is_relu=False, unit_grad=False):
+        H, W, b = H.contiguous(), W.contiguous(), b.contiguous()
+        T = W.shape[0]
+        assert H.dtype == torch.float32 and H.shape[1] == KGW_C and H.shape[0] >= n and W.shape[1] == KGW_C and b.numel() == T
+        assert W.dtype == torch.float32 and b.dtype == torch.float32
+        assert n_id.dtype == torch.int32 and y_all.dtype == torch.float32 and w_all.dtype == torch.float64
+        assert y_all.dim() == 2 and y_all.shape[1] == T and y_all.is_contiguous() and n_id.numel() >= n
+        dev = H.device
+        L = _lib.lib()
+        pred = torch.empty(n, T, device=dev)
+        loss = torch.empty((), dtype=torch.float64, device=dev)
+        terms = torch.empty(n, dtype=torch.float64, device=dev)
+        ctx.n, ctx.relu, ctx.h_is_relu = n, relu, h_is_relu
+        ctx.mark_non_differentiable(pred)
+        ctx.set_materialize_grads(False)
+        ctx.ready = None
+        if unit_grad and ctx.needs_input_grad[0]:
+            dH, dW, db = torch.empty_like(H), torch.empty_like(W), torch.empty_like(b)
+            part = torch.empty(((n + 3) // 4) * T * (KGW_C + 1), device=dev)
+            _lib.check(L.kgw_readout_wmse_mt_train(_p(H), _p(W), _p(b), _p(n_id), _p(y_all), _p(w_all), n, H.shape[0], T,
+                                                   (1 if relu else 0) | (2 if h_is_relu else 0), _p(pred), _p(loss), _p(dH), _p(dW),
+                                                   _p(db), _p(terms), _p(part), _lib.stream_ptr()), 'kgw_readout_wmse_mt_train')
+            _route('kgw_readout_wmse_mt_train')
+            ctx.ready = (dH, dW, db)
+            return loss, pred
+        _lib.check(L.kgw_readout_wmse_mt_fwd(_p(H), _p(W), _p(b), _p(n_id), _p(y_all), _p(w_all), n, T, 1 if relu else 0, _p(pred),
+                                             _p(loss), _p(terms), _lib.stream_ptr()), 'kgw_readout_wmse_mt_fwd')
+        _route('kgw_readout_wmse_mt_fwd')
+        ctx.save_for_backward(H, W, pred, n_id, y_all, w_all)
+        return loss, pred
+
+    @staticmethod
+    def backward(ctx, gloss, _gpred):
+        if gloss is None:
+            return (None,) * 10
+        if ctx.ready is not None:
+            dH, dW, db = ctx.ready
+            ctx.ready = None
+            unit = _UNIT_GRADS.get(gloss.device)
+            if not (unit is not None and gloss.data_ptr() == unit.data_ptr()):
+                k = gloss.to(torch.float32)            # (not the resident 1.0: the precomputed gradients are for a loss gradient of 1)
+                dH, dW, db = dH * k, dW * k, db * k
+            return dH, dW, db, None, None, None, None, None, None, None
+        H, W, pred, n_id, y_all, w_all = ctx.saved_tensors
+        T = W.shape[0]
+        gloss = gloss.contiguous().to(torch.float64)
+        dH, dW, db = torch.empty_like(H), torch.empty_like(W), torch.empty(T, device=H.device)
+        part = torch.empty(((ctx.n + 3) // 4) * T * (KGW_C + 1), device=H.device)
+        _lib.check(_lib.lib().kgw_readout_wmse_mt_bwd(_p(H), _p(W), _p(pred), _p(n_id), _p(y_all), _p(w_all), ctx.n, H.shape[0], T,
+                                                      (1 if ctx.relu else 0) | (2 if ctx.h_is_relu else 0), _p(gloss), _p(dH), _p(dW),
+                                                      _p(db), _p(part), _lib.stream_ptr()), 'kgw_readout_wmse_mt_bwd')
+        return dH, dW, db, None, None, None, None, None, None, None
+
+
+class _ReadoutLinearMulti(torch.autograd.Function):
+    """H @ W^T + b for the read-out Linear(128 -> T), 1 < T <= 32, on this package's kernels (kgw_readout_mt_pred / _pred_bwd)."""
+
+    @staticmethod
+    def forward(ctx, H, W, b):
+        H, W, b = H.contiguous(), W.contiguous(), b.contiguous()
+        n, T = H.shape[0], W.shape[0]
+        assert H.dtype == torch.float32 and W.dtype == torch.float32 and b.dtype == torch.float32
+        assert H.shape[1] == KGW_C and W.shape[1] == KGW_C and b.numel() == T
+        pred = torch.empty(n, T, device=H.device)
+        if n:
+            _lib.check(_lib.lib().kgw_readout_mt_pred(_p(H), _p(W), _p(b), n, T, 0, _p(pred), _lib.stream_ptr()), 'kgw_readout_mt_pred')
+            _route('kgw_readout_mt_pred')
+        ctx.save_for_backward(H, W)
+        return pred
+
+    @staticmethod
+    def backward(ctx, dpred):
+        H, W = ctx.saved_tensors
+        n, T = H.shape[0], W.shape[0]
+        dH, dW, db = torch.empty_like(H), torch.empty_like(W), torch.empty(T, device=H.device)
+        if n == 0:
+            return dH, dW.zero_(), db.zero_()
+        dpred = dpred.contiguous()
+        part = torch.empty(((n + 3) // 4) * T * (KGW_C + 1), device=H.device)
+        _lib.check(_lib.lib().kgw_readout_mt_pred_bwd(_p(H), _p(W), _p(dpred), n, n, T, 0, _p(dH), _p(dW), _p(db), _p(part),
+                                                      _lib.stream_ptr()), 'kgw_readout_mt_pred_bwd')
+        return dH, dW, db
+
+
+def readout_linear(H, W, b):
+    """``H @ W.T + b`` [n, T] for HeteroGNN.lin with 1 < T <= 32 output columns (forward(), evaluation): no library GEMM."""
+    if not 1 <= W.shape[0] <= _lib.KGW_MT_MAX:
+        raise NotImplementedError(f'the read-out kernels take 1 to {_lib.KGW_MT_MAX} output columns, not {W.shape[0]}')
+    return _ReadoutLinearMulti.apply(H, W, b)
+
+
 def readout_weighted_mse(H, w_lin, b_lin, n_id, y_all, w_all, n: int, relu: bool = True, h_is_relu: bool = False,
                          unit_grad: bool = False):
     """Returns (loss float64 scalar, pred float32 [n]); ``w_lin`` [1,128] / ``b_lin`` [1] = HeteroGNN.lin.
     ``h_is_relu``: see layer_transform's ``premasked``.  ``unit_grad``: the caller expects to backpropagate a loss gradient of
     exactly 1: forward and backward of this node then share two launches instead of four.  Passing the resident
     ``unit_gradient(device)`` to ``backward(gradient=...)`` takes the precomputed gradients as they are; any other loss gradient
-    (``(k * loss).backward()``) multiplies them -- correct either way."""
-    return _ReadoutWeightedMSE.apply(H, w_lin, b_lin, n_id, y_all, w_all, int(n), bool(relu), bool(h_is_relu), bool(unit_grad))
+    (``(k * loss).backward()``) multiplies them -- correct either way.
+    Multi-trait: ``w_lin`` [T,128], ``b_lin`` [T] and a 2-D ``y_all`` [N,T] (T <= 32, one weight per node in ``w_all``) give the
+    mean over seeds and columns and pred [n,T] (kgw_readout_wmse_mt_*: two launches where the node is, nothing deferred)."""
+    T = w_lin.shape[0] if w_lin.dim() == 2 else 1
+    if T == 1:
+        if y_all.dim() == 2:
+            if y_all.shape[1] != 1:
+                raise ValueError(f'{y_all.shape[1]} label columns for a read-out of one')
+            y_all = y_all.reshape(-1)
+        return _ReadoutWeightedMSE.apply(H, w_lin, b_lin, n_id, y_all, w_all, int(n), bool(relu), bool(h_is_relu), bool(unit_grad))
+    if T > _lib.KGW_MT_MAX:
+        raise NotImplementedError(f'the fused read-out + loss takes up to {_lib.KGW_MT_MAX} label columns, not {T}')
+    if y_all.dim() != 2 or y_all.shape[1] != T:
+        raise ValueError(f'a read-out of {T} columns needs labels [N, {T}], not {tuple(y_all.shape)}')
+    return _ReadoutWeightedMSEMulti.apply(H, w_lin, b_lin, n_id, y_all.contiguous(), w_all, int(n), bool(relu), bool(h_is_relu),
+                                          bool(unit_grad))

@@ -103,7 +103,8 @@ def write_tsv(df, path):
 
 
 def evaluate_minibatch_clean(loader, model, device):
-    """kgwas/utils.py:20-39: eval-mode forward over a loader; returns {'pred', 'truth'} numpy arrays.
+    """kgwas/utils.py:20-39: eval-mode forward over a loader; returns {'pred', 'truth'} numpy arrays ([n]; [n, T] for a model
+    with out_channels = T > 1).
     Differences by design: wrapped in no_grad (the reference builds and frees autograd graphs), predictions stay on
     the GPU until the end (one D2H copy instead of one per batch), and -- for this package's own NeighborLoader on a
     ROCm device -- the per-batch forward is a captured HIP graph (kgwas_amd/graph_step.py::GraphEvalStep; set
@@ -129,13 +130,14 @@ def evaluate_minibatch_clean(loader, model, device):
             pred = ge.run()
             truth = loader.dg.y[loader.input_type][ge.eval_ids]
             return {'pred': pred.float().cpu().numpy(), 'truth': truth.float().cpu().numpy()}
+    T = int(getattr(getattr(model, 'lin', None), 'out_features', 1))       # label columns: [n, T] arrays when T > 1
     preds, truths = [], []
     with torch.no_grad():
         for batch in loader:
             batch = batch.to(device)
             bs = batch['SNP'].batch_size
             out = model(batch.x_dict, batch.edge_index_dict, bs)
-            preds.append(out.reshape(-1))
+            preds.append(out.reshape(-1) if T == 1 else out)
             truths.append(batch['SNP'].y[:bs])
     if not preds:
         return {'pred': np.zeros(0, np.float32), 'truth': np.zeros(0, np.float32)}
