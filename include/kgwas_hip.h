@@ -786,7 +786,12 @@ int kgw_readout_train_fold(const KgwReadoutFold* fold, kgw_stream_t stream);
  *   kgw_readout_mt_pred        predictions only (HeteroGNN.forward, evaluation): one launch
  *   kgw_readout_mt_pred_bwd    its backward from dpred [n][T]: dH, dW, db (relu: bit 1 only)
  *   kgw_readout_wmse_mt_fwd    predictions and loss;  _bwd: dH, dW, db for any grad_loss;  two launches each
- *   kgw_readout_wmse_mt_train  both for a loss gradient of exactly 1, in two launches (kgw_readout_wmse_train's form)            */
+ *   kgw_readout_wmse_mt_train  both for a loss gradient of exactly 1, in two launches (kgw_readout_wmse_train's form)
+ * kgw_readout_wmse_mtw_fwd / _bwd / _train: the same three calls -- arguments, grids, folds, workspaces, status codes -- with a weight
+ * MATRIX, const double* w [N_SNP][T], row = global SNP id: loss = 1 / (n T) sum_i sum_t w[n_id[i]][t] (pred[i][t] - y[n_id[i]][t])^2,
+ * the divisor n T whatever is observed.  w[g][t] == 0.0 means "column t is not observed at SNP g": that pair's loss term and d pred
+ * are exactly 0 whatever bits y[g][t] holds (NaN and +-Inf included); pred[i][t] is still written.  Where every column of a row holds
+ * the row's shared weight, the outputs equal those of the kgw_readout_wmse_mt_* call bit for bit.                                */
 int kgw_readout_mt_pred(const float* H, const float* W, const float* b, int32_t n, int32_t T, int32_t relu, float* pred,
                         kgw_stream_t stream);
 int kgw_readout_mt_pred_bwd(const float* H, const float* W, const float* dpred, int32_t n, int64_t rows, int32_t T, int32_t relu,
@@ -799,6 +804,15 @@ int kgw_readout_wmse_mt_bwd(const float* H, const float* W, const float* pred, c
 int kgw_readout_wmse_mt_train(const float* H, const float* W, const float* b, const int32_t* n_id, const float* y, const double* w,
                               int32_t n, int64_t rows, int32_t T, int32_t relu, float* pred, double* loss, float* dH, float* dW,
                               float* db, double* terms, float* scratch, kgw_stream_t stream);
+int kgw_readout_wmse_mtw_fwd(const float* H, const float* W, const float* b, const int32_t* n_id, const float* y,
+                             const double* w /* [N_SNP][T], row = global SNP id */, int32_t n, int32_t T, int32_t relu, float* pred,
+                             double* loss, double* scratch, kgw_stream_t stream);
+int kgw_readout_wmse_mtw_bwd(const float* H, const float* W, const float* pred, const int32_t* n_id, const float* y,
+                             const double* w /* [N_SNP][T] */, int32_t n, int64_t rows, int32_t T, int32_t relu,
+                             const double* grad_loss, float* dH, float* dW, float* db, float* scratch, kgw_stream_t stream);
+int kgw_readout_wmse_mtw_train(const float* H, const float* W, const float* b, const int32_t* n_id, const float* y,
+                               const double* w /* [N_SNP][T] */, int32_t n, int64_t rows, int32_t T, int32_t relu, float* pred,
+                               double* loss, float* dH, float* dW, float* db, double* terms, float* scratch, kgw_stream_t stream);
 
 /* Self-test of the cross-lane reductions used by the aggregate kernels (one wavefront):
  * out_half[l] = sum over l's 32-lane half, out_wave[l] = sum over the wavefront,

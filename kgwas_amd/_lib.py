@@ -168,7 +168,8 @@ EXPORTS = ['kgw_version', 'kgw_status_string', 'kgw_struct_sizes', 'kgw_sample_b
            'kgw_gat_aggregate_fwd', 'kgw_gat_aggregate_bwd_dst', 'kgw_gat_aggregate_bwd_src',
            'kgw_gather_rows', 'kgw_gather_rows_multi', 'kgw_scatter_relu_rows', 'kgw_scatter_relu_rows_workspace_floats', 'kgw_edge_alpha', 'kgw_debug_reduce', 'kgw_debug_reduce8', 'kgw_tn_gemm', 'kgw_tn_gemm_ex', 'kgw_tn_gemm_multi', 'kgw_tn_gemm_workspace_floats', 'kgw_tn_gemm_partial', 'kgw_tn_gemm_multi_partial', 'kgw_tn_split', 'kgw_tn_direct_rows', 'kgw_param_tail', 'kgw_tn_reduce_launch', 'kgw_tn_gemm_partial_ride', 'kgw_transform_bwd_ex', 'kgw_mlp2_bwd_first_partial', 'kgw_mlp2_bwd_first_packed', 'kgw_adam_fused', 'kgw_gemm3_partial', 'kgw_gemm3_flip', 'kgw_transform_bwd', 'kgw_grad_finish',
            'kgw_linear', 'kgw_mlp2_fwd', 'kgw_mlp2w_fwd', 'kgw_mlp2_bwd_first', 'kgw_mlp2_bwd_first_workspace_floats', 'kgw_gemm3', 'kgw_gemm3_riders', 'kgw_gemm3_rider_blocks', 'kgw_gemm3_pack', 'kgw_gemm3_packed_bytes', 'kgw_gemm3_workspace_floats', 'kgw_adam', 'kgw_adam_notick', 'kgw_relvec_fwd', 'kgw_relvec_bwd', 'kgw_relvec_bwd_acc', 'kgw_relvec_fwd_multi', 'kgw_relvec_bwd_multi', 'kgw_wmse_fwd', 'kgw_wmse_bwd', 'kgw_readout_wmse_fwd', 'kgw_readout_wmse_bwd', 'kgw_readout_wmse_train', 'kgw_readout_wmse_train_parts', 'kgw_readout_train_fold', 'kgw_readout_mt_pred', 'kgw_readout_mt_pred_bwd', 'kgw_readout_wmse_mt_fwd', 'kgw_readout_wmse_mt_bwd',
-           'kgw_readout_wmse_mt_train', 'kgw_accumulate_stats', 'kgw_accumulate_stats_tick']
+           'kgw_readout_wmse_mt_train', 'kgw_readout_wmse_mtw_fwd', 'kgw_readout_wmse_mtw_bwd', 'kgw_readout_wmse_mtw_train',
+           'kgw_accumulate_stats', 'kgw_accumulate_stats_tick']
 
 _lib = None
 
@@ -308,6 +309,10 @@ def lib():
         L.kgw_readout_wmse_mt_fwd.argtypes = [C.c_void_p] * 6 + [C.c_int32] * 3 + [C.c_void_p] * 4
         L.kgw_readout_wmse_mt_bwd.argtypes = [C.c_void_p] * 6 + [C.c_int32, C.c_int64, C.c_int32, C.c_int32] + [C.c_void_p] * 6
         L.kgw_readout_wmse_mt_train.argtypes = [C.c_void_p] * 6 + [C.c_int32, C.c_int64, C.c_int32, C.c_int32] + [C.c_void_p] * 8
+    if hasattr(L, 'kgw_readout_wmse_mtw_train'):    # (the same argument lists; w is [N_SNP][T])
+        L.kgw_readout_wmse_mtw_fwd.argtypes = L.kgw_readout_wmse_mt_fwd.argtypes
+        L.kgw_readout_wmse_mtw_bwd.argtypes = L.kgw_readout_wmse_mt_bwd.argtypes
+        L.kgw_readout_wmse_mtw_train.argtypes = L.kgw_readout_wmse_mt_train.argtypes
     L.kgw_accumulate_stats.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
     L.kgw_accumulate_stats_tick.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     _lib = L

@@ -323,6 +323,14 @@ extern "C" int kgw_readout_wmse_train(const float* H, const float* w_lin, const 
 // residual is the small difference of two large numbers, and a float32 dot product's rounding (~1e-7 |pred|) would show in the loss at
 // 1e-7 |pred| / |residual|; in float64 the loss agrees with its float64 statement to rounding of the sum.  The gradients take the
 // residual rounded to float32.  T = 1 therefore agrees with the single-column node to float32 rounding, not to the bit.
+// kgw_readout_wmse_mtw_*: the same node with a weight MATRIX w [N_SNP][T] (a trait's LD-score regression weight depends on its own
+// sample size, and a trait covers its own subset of the SNPs):
+//     loss = 1 / (n T) * sum_i sum_t w[n_id[i]][t] * (pred[i][t] - y[n_id[i]][t])^2      (the divisor is n T whatever is observed).
+// Lane t loads w[g][t] once per seed (coalesced, like the label); iteration t of the column loop reads it with two 32-bit readlanes
+// and then uses the shared-weight kernel's expressions in their order, so equal columns give equal bits.  w[g][t] == 0.0 means "trait
+// t is not observed at SNP g": the residual of that pair is taken as 0 before the label is touched, so its loss term and its d pred
+// are exactly 0 whatever bits y[g][t] holds (NaN, +-Inf); pred[i][t] is still written.  A compile-time variant (W_COLS) of
+// k_readout_mt: the shared-weight instantiations compile from the expressions they had.
 // ======================================================================================================
 namespace {
 
@@ -342,12 +350,20 @@ __device__ __forceinline__ float kgw_lane_value(float v, int lane_uniform) {
     return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), lane_uniform));
 }
 
+__device__ __forceinline__ double kgw_lane_value_f64(double v, int lane_uniform) {
+    const uint64_t u = __builtin_bit_cast(uint64_t, v);
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)u, lane_uniform);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(u >> 32), lane_uniform);
+    return __builtin_bit_cast(double, ((uint64_t)hi << 32) | lo);
+}
+
 __device__ __forceinline__ double kgw_wave_allsum_f64(double v) {
     for (int o = 1; o < 64; o <<= 1) v += __shfl_xor(v, o);
     return v;
 }
 
-template <int MODE>
+// W_COLS: a.w is [N_SNP][T] (one weight per SNP and column, 0.0 = unobserved) instead of [N_SNP]
+template <int MODE, bool W_COLS = false>
 __global__ void __launch_bounds__(256) k_readout_mt(const KgwMtArgs a) {
     __shared__ float sW[KGW_MT_MAX * KGW_C];
     __shared__ float sH[4][KGW_C + 1];
@@ -367,17 +383,23 @@ __global__ void __launch_bounds__(256) k_readout_mt(const KgwMtArgs a) {
         h2 = ((const float2*)(a.H + i * KGW_C))[lane];
         const bool labelled = MODE == KGW_MT_TRAIN || MODE == KGW_MT_BWD || (MODE == KGW_MT_FWD && a.y != nullptr);
         const bool mine = lane < T;
-        double wg = 0.0;
+        double wg = 0.0, w_mine = 0.0, base = 0.0;         // (W_COLS: lane t holds w[g][t]; base = the part of `scale` before w)
         float y_mine = 0.f, b_mine = 0.f, in_mine = 0.f, p_mine = 0.f, scale = 0.f;
         if (labelled) {
             const int g = a.n_id[i];
-            wg = a.w[g];
+            if (W_COLS) { if (mine) w_mine = a.w[(int64_t)g * T + lane]; }
+            else wg = a.w[g];
             if (mine) y_mine = a.y[(int64_t)g * T + lane];
         }
         if ((MODE == KGW_MT_FWD || MODE == KGW_MT_TRAIN) && mine) b_mine = a.b[lane];
         if ((MODE == KGW_MT_BWD || MODE == KGW_MT_BWD_PRED) && mine) in_mine = a.pred_in[i * T + lane];
-        if (MODE == KGW_MT_TRAIN) scale = (float)(1.0 / ((double)n * (double)T) * wg);
-        if (MODE == KGW_MT_BWD) scale = (float)(a.gloss[0] / ((double)n * (double)T) * wg);
+        if (W_COLS) {
+            if (MODE == KGW_MT_TRAIN) base = 1.0 / ((double)n * (double)T);
+            if (MODE == KGW_MT_BWD) base = a.gloss[0] / ((double)n * (double)T);
+        } else {
+            if (MODE == KGW_MT_TRAIN) scale = (float)(1.0 / ((double)n * (double)T) * wg);
+            if (MODE == KGW_MT_BWD) scale = (float)(a.gloss[0] / ((double)n * (double)T) * wg);
+        }
         double term = 0.0;
         float2 dh = make_float2(0.f, 0.f);
         for (int t = 0; t < T; ++t) {
@@ -397,7 +419,14 @@ __global__ void __launch_bounds__(256) k_readout_mt(const KgwMtArgs a) {
             if (MODE == KGW_MT_BWD_PRED) {
                 dp = p;                                    // (the caller's ReLU, if any, is its own autograd node)
             } else if (labelled) {
-                const double d64 = p64 - (double)kgw_lane_value(y_mine, t);
+                double d64;
+                if (W_COLS) {                              // (t is wavefront-uniform; an unobserved pair never reads its label)
+                    wg = kgw_lane_value_f64(w_mine, t);
+                    scale = (float)(base * wg);
+                    d64 = wg != 0.0 ? p64 - (double)kgw_lane_value(y_mine, t) : 0.0;
+                } else {
+                    d64 = p64 - (double)kgw_lane_value(y_mine, t);
+                }
                 const float d = (float)d64;
                 if (MODE != KGW_MT_BWD) term += wg * (d64 * d64);
                 if (MODE != KGW_MT_FWD) {
@@ -504,51 +533,96 @@ extern "C" int kgw_readout_mt_pred_bwd(const float* H, const float* W, const flo
     return KGW_OK;
 }
 
-extern "C" int kgw_readout_wmse_mt_fwd(const float* H, const float* W, const float* b, const int32_t* n_id, const float* y,
-                                       const double* w, int32_t n, int32_t T, int32_t relu, float* pred, double* loss,
-                                       double* scratch, kgw_stream_t stream_) {
+namespace {
+
+// the three loss forms, W_COLS = false: w [N_SNP] (kgw_readout_wmse_mt_*);  true: w [N_SNP][T] (kgw_readout_wmse_mtw_*).  Same grids,
+// same folds, same workspaces.
+template <bool W_COLS>
+int kgw_mt_wmse_fwd(const float* H, const float* W, const float* b, const int32_t* n_id, const float* y, const double* w, int32_t n,
+                    int32_t T, int32_t relu, float* pred, double* loss, double* scratch, kgw_stream_t stream_) {
     if (!H || !W || !b || !n_id || !y || !w || !pred || !loss || !scratch) return KGW_E_NULL;
     if (kgw_mt_range(n, n, T)) return KGW_E_RANGE;
     hipStream_t st = (hipStream_t)stream_;
     KgwMtArgs a{};
     a.H = H; a.W = W; a.b = b; a.n_id = n_id; a.y = y; a.w = w; a.pred = pred; a.terms = scratch; a.rows = n; a.n = n; a.T = T;
     a.relu = relu;
-    k_readout_mt<KGW_MT_FWD><<<(n + 3) / 4, 256, 0, st>>>(a);
+    k_readout_mt<KGW_MT_FWD, W_COLS><<<(n + 3) / 4, 256, 0, st>>>(a);
     KGW_LAUNCH_CHECK();
     k_readout_mt_fold<<<1, 1024, 0, st>>>(nullptr, 0, T, scratch, n, nullptr, nullptr, loss);
     KGW_LAUNCH_CHECK();
     return KGW_OK;
 }
 
-extern "C" int kgw_readout_wmse_mt_bwd(const float* H, const float* W, const float* pred, const int32_t* n_id, const float* y,
-                                       const double* w, int32_t n, int64_t rows, int32_t T, int32_t relu, const double* grad_loss,
-                                       float* dH, float* dW, float* db, float* scratch, kgw_stream_t stream_) {
+template <bool W_COLS>
+int kgw_mt_wmse_bwd(const float* H, const float* W, const float* pred, const int32_t* n_id, const float* y, const double* w, int32_t n,
+                    int64_t rows, int32_t T, int32_t relu, const double* grad_loss, float* dH, float* dW, float* db, float* scratch,
+                    kgw_stream_t stream_) {
     if (!H || !W || !pred || !n_id || !y || !w || !grad_loss || !dH || !dW || !db || !scratch) return KGW_E_NULL;
     if (kgw_mt_range(n, rows, T)) return KGW_E_RANGE;
     hipStream_t st = (hipStream_t)stream_;
     KgwMtArgs a{};
     a.H = H; a.W = W; a.pred_in = pred; a.n_id = n_id; a.y = y; a.w = w; a.gloss = grad_loss; a.dH = dH; a.part = scratch;
     a.rows = rows; a.n = n; a.T = T; a.relu = relu;
-    k_readout_mt<KGW_MT_BWD><<<(unsigned)((rows + 3) / 4), 256, 0, st>>>(a);
+    k_readout_mt<KGW_MT_BWD, W_COLS><<<(unsigned)((rows + 3) / 4), 256, 0, st>>>(a);
     KGW_LAUNCH_CHECK();
     k_readout_mt_fold<<<T, 1024, 0, st>>>(scratch, (n + 3) / 4, T, nullptr, n, dW, db, nullptr);
     KGW_LAUNCH_CHECK();
     return KGW_OK;
 }
 
-extern "C" int kgw_readout_wmse_mt_train(const float* H, const float* W, const float* b, const int32_t* n_id, const float* y,
-                                         const double* w, int32_t n, int64_t rows, int32_t T, int32_t relu, float* pred,
-                                         double* loss, float* dH, float* dW, float* db, double* terms, float* scratch,
-                                         kgw_stream_t stream_) {
+template <bool W_COLS>
+int kgw_mt_wmse_train(const float* H, const float* W, const float* b, const int32_t* n_id, const float* y, const double* w, int32_t n,
+                      int64_t rows, int32_t T, int32_t relu, float* pred, double* loss, float* dH, float* dW, float* db, double* terms,
+                      float* scratch, kgw_stream_t stream_) {
     if (!H || !W || !b || !n_id || !y || !w || !pred || !loss || !dH || !dW || !db || !terms || !scratch) return KGW_E_NULL;
     if (kgw_mt_range(n, rows, T)) return KGW_E_RANGE;
     hipStream_t st = (hipStream_t)stream_;
     KgwMtArgs a{};
     a.H = H; a.W = W; a.b = b; a.n_id = n_id; a.y = y; a.w = w; a.pred = pred; a.terms = terms; a.dH = dH; a.part = scratch;
     a.rows = rows; a.n = n; a.T = T; a.relu = relu;
-    k_readout_mt<KGW_MT_TRAIN><<<(unsigned)((rows + 3) / 4), 256, 0, st>>>(a);
+    k_readout_mt<KGW_MT_TRAIN, W_COLS><<<(unsigned)((rows + 3) / 4), 256, 0, st>>>(a);
     KGW_LAUNCH_CHECK();
     k_readout_mt_fold<<<T, 1024, 0, st>>>(scratch, (n + 3) / 4, T, terms, n, dW, db, loss);
     KGW_LAUNCH_CHECK();
     return KGW_OK;
+}
+
+}  // namespace
+
+extern "C" int kgw_readout_wmse_mt_fwd(const float* H, const float* W, const float* b, const int32_t* n_id, const float* y,
+                                       const double* w, int32_t n, int32_t T, int32_t relu, float* pred, double* loss,
+                                       double* scratch, kgw_stream_t stream_) {
+    return kgw_mt_wmse_fwd<false>(H, W, b, n_id, y, w, n, T, relu, pred, loss, scratch, stream_);
+}
+
+extern "C" int kgw_readout_wmse_mt_bwd(const float* H, const float* W, const float* pred, const int32_t* n_id, const float* y,
+                                       const double* w, int32_t n, int64_t rows, int32_t T, int32_t relu, const double* grad_loss,
+                                       float* dH, float* dW, float* db, float* scratch, kgw_stream_t stream_) {
+    return kgw_mt_wmse_bwd<false>(H, W, pred, n_id, y, w, n, rows, T, relu, grad_loss, dH, dW, db, scratch, stream_);
+}
+
+extern "C" int kgw_readout_wmse_mt_train(const float* H, const float* W, const float* b, const int32_t* n_id, const float* y,
+                                         const double* w, int32_t n, int64_t rows, int32_t T, int32_t relu, float* pred,
+                                         double* loss, float* dH, float* dW, float* db, double* terms, float* scratch,
+                                         kgw_stream_t stream_) {
+    return kgw_mt_wmse_train<false>(H, W, b, n_id, y, w, n, rows, T, relu, pred, loss, dH, dW, db, terms, scratch, stream_);
+}
+
+extern "C" int kgw_readout_wmse_mtw_fwd(const float* H, const float* W, const float* b, const int32_t* n_id, const float* y,
+                                        const double* w, int32_t n, int32_t T, int32_t relu, float* pred, double* loss,
+                                        double* scratch, kgw_stream_t stream_) {
+    return kgw_mt_wmse_fwd<true>(H, W, b, n_id, y, w, n, T, relu, pred, loss, scratch, stream_);
+}
+
+extern "C" int kgw_readout_wmse_mtw_bwd(const float* H, const float* W, const float* pred, const int32_t* n_id, const float* y,
+                                        const double* w, int32_t n, int64_t rows, int32_t T, int32_t relu, const double* grad_loss,
+                                        float* dH, float* dW, float* db, float* scratch, kgw_stream_t stream_) {
+    return kgw_mt_wmse_bwd<true>(H, W, pred, n_id, y, w, n, rows, T, relu, grad_loss, dH, dW, db, scratch, stream_);
+}
+
+extern "C" int kgw_readout_wmse_mtw_train(const float* H, const float* W, const float* b, const int32_t* n_id, const float* y,
+                                          const double* w, int32_t n, int64_t rows, int32_t T, int32_t relu, float* pred,
+                                          double* loss, float* dH, float* dW, float* db, double* terms, float* scratch,
+                                          kgw_stream_t stream_) {
+    return kgw_mt_wmse_train<true>(H, W, b, n_id, y, w, n, rows, T, relu, pred, loss, dH, dW, db, terms, scratch, stream_);
 }

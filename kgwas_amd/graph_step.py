@@ -172,7 +172,7 @@ class GraphTrainStep:
         # finite fan-out: the 64-bit sample seed the (captured) sampler reads, fed like ``seeds``; the words of an epoch's batches
         self.sample_word = torch.zeros(1, dtype=torch.int64, device=dev) if self.fanout is not None else None
         self._epoch_words = {}
-        self.ld_w = run._ld_weight_vector()
+        self.ld_w = run._ld_weight_vector()             # ([N] or, per-trait weights, [N, T]: resident, read in place by the graph)
         self.capture_optimizer = capture_optimizer
         self.world = 1
         try:

@@ -81,8 +81,16 @@ class KGWAS:
     # ------------------------------------------------------------------------------------------
     def _ld_weight_vector(self) -> torch.Tensor:
         """float64 [N_SNP] LD-score regression weight per SNP index (kgwas.py:142-143 without the
-        per-step Python look-ups); SNPs without a weight get 0 and are never seeds."""
+        per-step Python look-ups); SNPs without a weight get 0 and are never seeds.  A data object with per-trait weights
+        (``ldsc_weight_traits``, KGWAS_Data.from_synthetic(trait_sample_sizes=) / load_external_gwas_traits) gives [N_SNP, T]: one
+        weight per (SNP, trait), 0 where the trait is not observed -- the read-out node's kgw_readout_wmse_mtw_* form."""
         n = int(self.data.data['SNP'].x.shape[0])
+        wt = getattr(self.data, 'ldsc_weight_traits', None)
+        if wt is not None:
+            wt = np.ascontiguousarray(wt, dtype=np.float64)
+            w = torch.zeros(n, wt.shape[1], dtype=torch.float64)
+            w[torch.from_numpy(np.asarray(self.data.all_ids, dtype=np.int64))] = torch.from_numpy(wt)
+            return w.to(self.device)
         w = torch.zeros(n, dtype=torch.float64)
         ids = np.asarray(self.data.all_ids, dtype=np.int64)
         w[torch.from_numpy(ids)] = torch.from_numpy(np.asarray(self.data.ldsc_weight, dtype=np.float64))
@@ -129,6 +137,8 @@ class KGWAS:
         if self.model.lin.out_features != 1:
             raise NotImplementedError("out_channels > 1 (multi-trait labels) is not available with parallelism='shard': the "
                                       "sharded step's read-out and loss are single-column; use parallelism='seed'")
+        if getattr(self.data, 'ldsc_weight_traits', None) is not None:
+            raise NotImplementedError("per-trait LD weights are not available with parallelism='shard'; use parallelism='seed'")
         rank, world = kdist.rank_world()
         if world > 1:
             kdist.broadcast_params(self.model)
@@ -237,7 +247,7 @@ class KGWAS:
             if graph_step is not None:
                 graph_step.check()
             val_res = evaluate_minibatch_clean(self.val_loader, self.model, self.device)
-            val_metrics = self._metrics(val_res)
+            val_metrics = self._metrics(val_res, self._observed_rows(self.val_loader, len(val_res['pred'])))
             print_sys('Epoch {}: Validation MSE: {:.4f} Validation Pearson: {:.4f}. '.format(
                 ep + 1, val_metrics['mse'], val_metrics['pearsonr']))
             self.val_metrics = val_metrics
@@ -253,35 +263,69 @@ class KGWAS:
             print_sys('Saving models to ' + os.path.join(save_model_path, save_name))
             save_model(self.best_model, self.config, os.path.join(save_model_path, save_name))
         test_res = evaluate_minibatch_clean(self.test_loader, self.best_model, self.device)
-        self.test_metrics = self._metrics(test_res)
+        self.test_metrics = self._metrics(test_res, self._observed_rows(self.test_loader, len(test_res['pred'])))
         if self.wandb:
             for i, j in self.test_metrics.items():
                 if i != 'per_trait':
                     self.wandb.log({'test_' + i: j})
         infer_res = evaluate_minibatch_clean(self.infer_loader, self.best_model, self.device)
-        if self.model.lin.out_features != 1:
+        if self.model.lin.out_features != 1 or getattr(self.data, 'trait_observed', None) is not None:
             return self._postprocess_traits(infer_res['pred'], save_name)
         self.data.lr_uni['pred'] = infer_res['pred']                 # kgwas.py:191
         self._postprocess(save_name, save_best_model and rank == 0)
 
-    def _metrics(self, res):
+    def _observed_rows(self, loader, n):
+        """bool [n, T]: which traits observe the first ``n`` input nodes of ``loader`` (the rows of its evaluation), or None for a
+        data object without per-trait SNP lists."""
+        observed = getattr(self.data, 'trait_observed', None)
+        if observed is None:
+            return None
+        by_snp = np.zeros((int(self.data.data['SNP'].x.shape[0]), observed.shape[1]), dtype=bool)
+        by_snp[np.asarray(self.data.all_ids, dtype=np.int64)] = observed
+        return by_snp[torch.as_tensor(loader.ids).cpu().numpy()[:n]]
+
+    def _metrics(self, res, observed=None):
         """compute_metrics of one evaluation; with T > 1 label columns: the metrics of every column under 'per_trait' and their
-        means under the usual keys -- the best model is the one with the highest MEAN validation Pearson over the traits."""
-        if self.model.lin.out_features == 1:
-            return compute_metrics(res, False, -1, -1, F.mse_loss)
-        per = [compute_metrics({'pred': res['pred'][:, t], 'truth': res['truth'][:, t]}, False, -1, -1, F.mse_loss)
-               for t in range(res['pred'].shape[1])]
-        return {'mse': float(np.mean([m['mse'] for m in per])), 'pearsonr': float(np.mean([m['pearsonr'] for m in per])),
+        means under the usual keys -- the best model is the one with the highest MEAN validation Pearson over the traits.
+        ``observed`` (bool [n, T], per-trait SNP lists): trait t's metrics run over the rows it observes; a trait with fewer than
+        two of them gets nan and stays out of the means; no trait left is an error."""
+        if observed is None:
+            if self.model.lin.out_features == 1:
+                return compute_metrics(res, False, -1, -1, F.mse_loss)
+            per = [compute_metrics({'pred': res['pred'][:, t], 'truth': res['truth'][:, t]}, False, -1, -1, F.mse_loss)
+                   for t in range(res['pred'].shape[1])]
+            return {'mse': float(np.mean([m['mse'] for m in per])), 'pearsonr': float(np.mean([m['pearsonr'] for m in per])),
+                    'per_trait': per}
+        pred, truth = np.asarray(res['pred']), np.asarray(res['truth'])
+        pred, truth = pred.reshape(len(pred), -1), truth.reshape(len(truth), -1)
+        per = []
+        for t in range(pred.shape[1]):
+            o = np.asarray(observed[:, t], dtype=bool)
+            if o.sum() < 2:
+                per.append({'mse': float('nan'), 'pearsonr': float('nan')})
+            else:
+                per.append(compute_metrics({'pred': pred[o, t], 'truth': truth[o, t]}, False, -1, -1, F.mse_loss))
+        live = [m for m in per if not np.isnan(m['mse'])]
+        if not live:
+            raise ValueError('no trait observes two or more labels in this split: no metric can be computed')
+        return {'mse': float(np.mean([m['mse'] for m in live])), 'pearsonr': float(np.mean([m['pearsonr'] for m in live])),
                 'per_trait': per}
 
     def _postprocess_traits(self, pred, save_name):
         """``_postprocess`` once per label column: trait t's summary statistics (KGWAS_Data.trait_table) with column t of the
-        predictions, written to <save_name>_trait<t>_pred.csv; ``kgwas_res`` becomes the list of the T tables."""
+        predictions, written to <save_name>_trait<t>_pred.csv; ``kgwas_res`` becomes the list of the T tables.  With per-trait SNP
+        lists a table holds the rows its trait observes; ``trait_pred`` keeps the whole matrix [len(all_ids), T], the predictions
+        for the unobserved pairs included."""
         base = self.data.lr_uni
+        pred = np.asarray(pred).reshape(len(pred), -1)
+        self.trait_pred = pred
         tables = []
+        per_trait_rows = getattr(self.data, 'trait_observed', None) is not None
         for t in range(pred.shape[1]):
+            if per_trait_rows:                      # (a trait's table is cut from the base table, not from the previous trait's)
+                self.data.lr_uni = base
             self.data.lr_uni = self.data.trait_table(t)
-            self.data.lr_uni['pred'] = pred[:, t]
+            self.data.lr_uni['pred'] = pred[self.data.trait_rows(t), t]
             self._postprocess(f'{save_name}_trait{t}', False)
             tables.append(self.kgwas_res)
         self.data.lr_uni = base

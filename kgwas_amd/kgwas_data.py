@@ -142,7 +142,8 @@ class KGWAS_Data:
     @classmethod
     def from_synthetic(cls, scale=1.0, seed=1, mode='fast', data_path='/tmp/kgwas_synth', n_labelled=None,
                        gwas_kind='causal', sample_size=None, feat_dims=None, split=True, snp_scale=1.0,
-                       sample_edges=False, sample_ratio=1.0, node_counts=None, n_traits=1):
+                       sample_edges=False, sample_ratio=1.0, node_counts=None, n_traits=1, trait_sample_sizes=None,
+                       trait_coverage=None):
         """SynthKG + synthetic summary statistics through the same pipeline as the real files.
         ``gwas_kind`` mirrors the reference's four label sources (BASELINE.json configs): 'causal' / 'null' = the
         simulations of load_simulation_gwas (N = 5000, kgwas_data.py:275-294), 'subsample' = load_gwas_subsample
@@ -151,7 +152,13 @@ class KGWAS_Data:
         relation, seeded permutation, before ToUndirected + AddSelfLoops.
         ``n_traits`` = T > 1: labels [N, T] for a multi-trait model (KGWAS.initialize_model(out_channels=T)) -- column 0 is the
         single-trait label vector, column t the chi-square / P draw of make_synth_gwas under the seed ``seed + 7919 * t``, over the
-        SAME labelled SNPs, LD scores and split."""
+        SAME labelled SNPs, LD scores and split.
+        ``trait_sample_sizes`` (T sample sizes) / ``trait_coverage`` (T fractions in (0, 1]), both None by default: per-trait LD
+        weights and per-trait SNP lists, as T real summary-statistics files have them.  Trait t observes a random
+        ceil(c_t * n_labelled) of the labelled SNPs (drawn under ``seed + 7919 * t``); its weights are
+        ldsc_regression_weights(ld, w_ld, N_t, M, 0.5) divided by their mean over the SNPs it observes and 0 elsewhere:
+        ``ldsc_weight_traits`` float64 [len(all_ids), T] and ``trait_observed`` bool [len(all_ids), T], rows as ``all_ids``;
+        ``data['SNP'].y[:, t]`` is 0 where trait t is not observed.  One list alone leaves the other at ``sample_size`` / 1."""
         import pandas as pd
         from .synth import FEAT_DIMS, make_synth_edges, make_synth_gwas
         self = cls(data_path)
@@ -196,9 +203,35 @@ class KGWAS_Data:
         self.pheno = {'causal': 'simulation', 'null': 'simulation'}.get(gwas_kind, 'synthetic_' + gwas_kind)
         self.seed = seed
         self.process_gwas_file()
+        if trait_sample_sizes is not None or trait_coverage is not None:
+            sizes = [sample_size] * n_traits if trait_sample_sizes is None else [float(v) for v in trait_sample_sizes]
+            cover = [1.0] * n_traits if trait_coverage is None else [float(v) for v in trait_coverage]
+            if len(sizes) != n_traits or len(cover) != n_traits:
+                raise ValueError(f'trait_sample_sizes / trait_coverage need one entry per trait ({n_traits})')
+            if not all(0.0 < c <= 1.0 for c in cover) or not all(v > 0 for v in sizes):
+                raise ValueError('trait_coverage entries lie in (0, 1], trait_sample_sizes are positive')
+            n_lab = len(self.all_ids)
+            observed = np.zeros((n_lab, n_traits), dtype=bool)
+            for t, c in enumerate(cover):
+                k = int(np.ceil(c * n_lab))
+                observed[np.random.default_rng(seed + 7919 * t).choice(n_lab, size=k, replace=False), t] = True
+            self._set_trait_weights(g['ld_score'], g['w_ld_score'], sizes, observed)
         if split:
             self.prepare_split()
         return self
+
+    def _set_trait_weights(self, ld, w_ld, sizes, observed):
+        """``ldsc_weight_traits`` [len(all_ids), T]: column t = the LD-score regression weights at sample size ``sizes[t]``
+        (the formula and constants of process_gwas_file), divided by their mean over the rows trait t observes, 0 elsewhere."""
+        w = np.zeros(observed.shape, dtype=np.float64)
+        for t, n_t in enumerate(sizes):
+            o = observed[:, t]
+            if o.any():
+                wt = ldsc_regression_weights(np.asarray(ld)[o], np.asarray(w_ld)[o], n_t, 15000000, 0.5)
+                w[o, t] = wt / np.mean(wt)
+        self.ldsc_weight_traits = w
+        self.trait_observed = observed
+        self.trait_sample_sizes = [float(v) for v in sizes]
 
     # --- GWAS loaders (kgwas_data.py:275-389) -------------------------------------------------------
     def load_simulation_gwas(self, simulation_type, seed):
@@ -241,6 +274,66 @@ class KGWAS_Data:
         self.pheno = 'EXTERNAL'
         self.seed = seed
 
+    def load_external_gwas_traits(self, paths, seed=42):
+        """T summary-statistics files (the format and column checks of ``load_external_gwas``) for ONE multi-trait model
+        (KGWAS.initialize_model(out_channels=T)).  The base table ``lr_uni`` / ``all_ids`` is the union of their KG SNPs in the
+        order of first appearance; trait t takes N from its own file, its labels by the 'chi' branch order of
+        ``process_gwas_file`` and its weights from the LD-score files under ``data_path`` at that N, normalised over its own rows
+        and 0 elsewhere -- the attributes of from_synthetic(trait_sample_sizes=, trait_coverage=).  ``ldsc_weight`` (1-D) is
+        trait 0's column.  Calls for ``prepare_split`` next, not ``process_gwas_file``."""
+        import pandas as pd
+        paths = list(paths)
+        if not 1 <= len(paths) <= 32:
+            raise ValueError(f'{len(paths)} files: a multi-trait model reads out 1 to 32 traits')
+        kg = set(self.idx2id['SNP'].values())
+        frames = []
+        for path in paths:
+            df = pd.read_csv(path, sep=None, engine='python')
+            for col, msg in (('CHR', 'CHR chromosome'), ('SNP', 'SNP column'), ('P', 'P column'),
+                             ('N', 'N column number of sample size')):
+                if col not in df.columns.values:
+                    raise ValueError(f'{msg} not in the file {path}!')
+            df = df.rename(columns={'CHR': '#CHROM', 'SNP': 'ID'})
+            df = df[df.ID.isin(kg)].drop_duplicates('ID', keep='last').reset_index(drop=True)
+            frames.append(df)
+        base = pd.concat([f[['#CHROM', 'ID']] for f in frames], ignore_index=True).drop_duplicates('ID', keep='first')
+        base = base.reset_index(drop=True)
+        print('Number of SNPs in the KG:', len(self.idx2id['SNP']))
+        print('Number of SNPs in the KG variant set, per trait:', [len(f) for f in frames], 'union:', len(base))
+        base['ld_score'], base['w_ld_score'] = self._ld_scores_of(base.ID)
+        row_of = pd.Series(np.arange(len(base)), index=base.ID.values)
+        T = len(frames)
+        observed = np.zeros((len(base), T), dtype=bool)
+        labels = np.zeros((len(base), T), dtype=np.float64)
+        pvals = np.full((len(base), T), np.nan)
+        self.pheno, self.seed = 'EXTERNAL', seed
+        sizes, rows_of = [], []
+        for t, df in enumerate(frames):
+            rows = row_of[df.ID.values].values
+            rows_of.append(rows)
+            observed[rows, t] = True
+            sizes.append(float(np.mean(df.N)))
+            self.sample_size = sizes[-1]                # (what _chi_labels' binary-trait branch looks at; 'EXTERNAL' never takes it)
+            df['ld_score'], df['w_ld_score'] = base.ld_score.values[rows], base.w_ld_score.values[rows]
+            self._chi_labels(df)
+            labels[rows, t] = df.y.values
+            pvals[rows, t] = df.P.values
+        id2idx = self.id2idx['SNP']
+        self.all_ids = np.array([id2idx[i] for i in base.ID.values], dtype=np.int64)
+        self._set_trait_weights(base.ld_score.values, base.w_ld_score.values, sizes, observed)
+        for t, df in enumerate(frames):
+            df['ld_weight'] = self.ldsc_weight_traits[rows_of[t], t]
+        self.sample_size = sizes[0]
+        self.ldsc_weight = self.ldsc_weight_traits[:, 0].copy()
+        self.rs_id_to_ldsc_weight = dict(zip(base.ID.values, self.ldsc_weight))
+        base['N'], base['P'] = sizes[0], pvals[:, 0]
+        base['y'] = labels[:, 0]
+        self.y = labels[:, 0]
+        self._trait_cols = [{'chi': labels[:, t], 'P': pvals[:, t]} for t in range(1, T)]
+        self._trait_frames, self._trait_rows = frames, rows_of
+        self._synth_ld = None
+        self.lr_uni = base
+
     def load_full_gwas(self, pheno, seed=42):
         import pandas as pd
         self.pheno = pheno
@@ -265,21 +358,11 @@ class KGWAS_Data:
 
     # --- labels + LD weights (kgwas_data.py:391-500) ----------------------------------------------
     def process_gwas_file(self, label='chi'):
-        import pandas as pd
         lr_uni = self.lr_uni
         if getattr(self, '_synth_ld', None) is not None:
             lr_uni['ld_score'], lr_uni['w_ld_score'] = self._synth_ld
         else:
-            dp = self.data_path
-            ld_scores = pd.read_csv(os.path.join(dp, 'ld_score/filter_genotyped_ldscores.csv'))
-            w_ld_scores = pd.read_csv(os.path.join(dp, 'ld_score/ldscores_from_data.csv'))
-            ld_map = pd.Series(ld_scores.iloc[:, 1].values, index=ld_scores.iloc[:, 0].values)
-            wld_map = pd.Series(w_ld_scores.iloc[:, 1].values, index=w_ld_scores.iloc[:, 0].values)
-            ld_map = ld_map[~ld_map.index.duplicated(keep='last')]
-            wld_map = wld_map[~wld_map.index.duplicated(keep='last')]
-            # SNPs without an LD score get the minimum (kgwas_data.py:410-417); w_ld excludes the SNP itself -> +1
-            lr_uni['ld_score'] = lr_uni.ID.map(ld_map).fillna(ld_map.min()).values
-            lr_uni['w_ld_score'] = 1 + lr_uni.ID.map(wld_map).fillna(wld_map.min()).values
+            lr_uni['ld_score'], lr_uni['w_ld_score'] = self._ld_scores_of(lr_uni.ID)
         m = 15000000
         n = self.sample_size if 'N' not in lr_uni.columns.values else np.mean(lr_uni.N)
         h_g_2 = 0.5
@@ -289,20 +372,7 @@ class KGWAS_Data:
         self.ldsc_weight = w
         self.rs_id_to_ldsc_weight = dict(zip(lr_uni.ID.values, w))
         if label == 'chi':
-            # branch order of kgwas_data.py:431-446: pre-computed chi; Z_STAT for the binary traits run through PLINK's
-            # logistic model (sample_size <= 3000); BETA/SE; else the P column -- NaN labels become 0 in every branch
-            if 'chi' in lr_uni.columns.values:
-                lr_uni['y'] = lr_uni['chi'].values
-            elif getattr(self, 'pheno', None) in _BINARY_PHENOS and getattr(self, 'sample_size', 1 << 30) <= 3000:
-                lr_uni['y'] = lr_uni['Z_STAT'].values ** 2
-                lr_uni['y'] = lr_uni.y.fillna(0)
-            elif ('BETA' in lr_uni.columns.values) and ('SE' in lr_uni.columns.values):
-                lr_uni['y'] = ((lr_uni['BETA'] / lr_uni['SE']).values ** 2)
-                lr_uni['y'] = lr_uni.y.fillna(0)
-            else:
-                from scipy.stats import chi2
-                lr_uni['y'] = chi2.ppf(1 - lr_uni['P'].values, 1)
-                lr_uni['y'] = lr_uni.y.fillna(0)
+            self._chi_labels(lr_uni)
         elif label in ('residual-w-ld', 'residual-ld', 'residual-ld-ols', 'residual-ld-ols-abs'):
             # kgwas_data.py:448-500: chi-square from BETA / SE, NaN -> 0, then the residual of a straight-line fit on an LD
             # score -- weighted by the LDSC weights (sm.WLS) for the first two, unweighted (sm.OLS) for the '-ols' ones.
@@ -326,6 +396,36 @@ class KGWAS_Data:
         self.all_ids = np.array([id2idx[i] for i in lr_uni.ID.values], dtype=np.int64)
         self.y = lr_uni.y.values
         self.lr_uni = lr_uni
+
+    def _ld_scores_of(self, ids):
+        """(ld_score, w_ld_score) of a Series of SNP ids from the two LD-score files under ``data_path``."""
+        import pandas as pd
+        dp = self.data_path
+        ld_scores = pd.read_csv(os.path.join(dp, 'ld_score/filter_genotyped_ldscores.csv'))
+        w_ld_scores = pd.read_csv(os.path.join(dp, 'ld_score/ldscores_from_data.csv'))
+        ld_map = pd.Series(ld_scores.iloc[:, 1].values, index=ld_scores.iloc[:, 0].values)
+        wld_map = pd.Series(w_ld_scores.iloc[:, 1].values, index=w_ld_scores.iloc[:, 0].values)
+        ld_map = ld_map[~ld_map.index.duplicated(keep='last')]
+        wld_map = wld_map[~wld_map.index.duplicated(keep='last')]
+        # SNPs without an LD score get the minimum (kgwas_data.py:410-417); w_ld excludes the SNP itself -> +1
+        return ids.map(ld_map).fillna(ld_map.min()).values, 1 + ids.map(wld_map).fillna(wld_map.min()).values
+
+    def _chi_labels(self, lr_uni):
+        """lr_uni['y'] for label = 'chi', in the branch order of kgwas_data.py:431-446: pre-computed chi; Z_STAT for the binary
+        traits run through PLINK's logistic model (sample_size <= 3000); BETA/SE; else the P column -- NaN labels become 0 in
+        every branch but the first."""
+        if 'chi' in lr_uni.columns.values:
+            lr_uni['y'] = lr_uni['chi'].values
+        elif getattr(self, 'pheno', None) in _BINARY_PHENOS and getattr(self, 'sample_size', 1 << 30) <= 3000:
+            lr_uni['y'] = lr_uni['Z_STAT'].values ** 2
+            lr_uni['y'] = lr_uni.y.fillna(0)
+        elif ('BETA' in lr_uni.columns.values) and ('SE' in lr_uni.columns.values):
+            lr_uni['y'] = ((lr_uni['BETA'] / lr_uni['SE']).values ** 2)
+            lr_uni['y'] = lr_uni.y.fillna(0)
+        else:
+            from scipy.stats import chi2
+            lr_uni['y'] = chi2.ppf(1 - lr_uni['P'].values, 1)
+            lr_uni['y'] = lr_uni.y.fillna(0)
 
     def prepare_split(self, test_set_fraction_data=0.05):
         """kgwas_data.py:522-545: sklearn train_test_split twice (5 % test, then 5 % of the rest val)."""
@@ -351,6 +451,14 @@ class KGWAS_Data:
                 c[torch.from_numpy(np.asarray(self.all_ids))] = torch.tensor(np.asarray(e['chi'])).float()
                 cols.append(c)
             y_snp = torch.stack(cols, 1).contiguous()
+        observed = getattr(self, 'trait_observed', None)
+        if observed is not None:                    # a pair a trait does not observe carries the label 0 (and the weight 0)
+            rows, cols = np.nonzero(~observed)
+            ids = torch.from_numpy(np.asarray(self.all_ids)[rows])
+            if y_snp.dim() == 2:
+                y_snp[ids, torch.from_numpy(cols)] = 0.0
+            else:
+                y_snp[ids] = 0.0
         self.data['SNP'].y = y_snp
         for t in self.data.node_types:
             self.data[t].n_id = torch.arange(self.data[t].x.shape[0])
@@ -361,13 +469,28 @@ class KGWAS_Data:
         self.data._extra.pop('_device_graphs', None)   # labels changed: rebuild resident copies lazily
 
     def trait_table(self, t: int):
-        """A copy of ``lr_uni`` carrying trait t's summary statistics (chi, y, P); t = 0 is ``lr_uni`` itself."""
+        """A copy of ``lr_uni`` carrying trait t's summary statistics (chi, y, P); t = 0 is ``lr_uni`` itself.  With per-trait SNP
+        lists (``trait_observed``): the rows trait t observes only, N = its own sample size."""
+        frames = getattr(self, '_trait_frames', None)
+        if frames is not None:                      # load_external_gwas_traits: each file's own table
+            return frames[t].copy()
         df = self.lr_uni.copy()
         extra = getattr(self, '_trait_cols', None) or []
         if t:
             df['chi'] = df['y'] = np.asarray(extra[t - 1]['chi'])
             df['P'] = np.asarray(extra[t - 1]['P'])
+        observed = getattr(self, 'trait_observed', None)
+        if observed is not None:
+            df['N'] = self.trait_sample_sizes[t]
+            df = df[observed[:, t]].reset_index(drop=True)
         return df
+
+    def trait_rows(self, t: int):
+        """The rows of ``all_ids`` (and of a prediction matrix over it) that ``trait_table(t)`` lists, in its order."""
+        if getattr(self, '_trait_frames', None) is not None:
+            return np.asarray(self._trait_rows[t])
+        observed = getattr(self, 'trait_observed', None)
+        return np.arange(len(self.all_ids)) if observed is None else np.nonzero(observed[:, t])[0]
 
     def get_pheno_list(self):
         return {'large_cohort': [],

@@ -657,7 +657,8 @@ class HeteroGNN(nn.Module):
         """The training step's forward (kgwas/kgwas.py:137-145): HeteroGNN.forward followed by
         mean(w_all[n_id] * (pred - y_all[n_id])**2), with the read-out Linear + ReLU (model.py:86) and the loss fused
         into one node.  Returns (loss [float64 scalar], pred [batch_size]) -- with ``out_channels = T > 1`` (a shared trunk read out
-        into T label columns, ``y_all`` [N,T]) the mean runs over seeds and columns and pred is [batch_size, T].  ``mlp_out`` (list): receives the feature MLPs'
+        into T label columns, ``y_all`` [N,T]) the mean runs over seeds and columns and pred is [batch_size, T]; ``w_all`` is then [N]
+        (one weight per SNP) or [N,T] (per-trait weights, 0 = unobserved pair: ops.readout_weighted_mse).  ``mlp_out`` (list): receives the feature MLPs'
         output tensors -- the cut between the two halves of a backward pass whose first half's gradients are all-reduced
         while the second half runs (multi-GPU GraphTrainStep).  ``unit_grad``: the caller will backpropagate exactly
         ``loss.backward()`` (gradient 1): the read-out node then does its forward and backward in two launches."""

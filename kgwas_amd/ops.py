@@ -2415,7 +2415,9 @@ class _ReadoutWeightedMSE(torch.autograd.Function):
 class _ReadoutWeightedMSEMulti(torch.autograd.Function):
     """_ReadoutWeightedMSE for T > 1 label columns (HeteroGNN(out_channels=T)): loss = mean over seeds AND columns of
     w[n_id] * ([relu](H[:n] @ W^T + b) - y[n_id])**2, kgw_readout_wmse_mt_*.  Both launches are issued where the node is -- no
-    deferred fold, no rider: d W and d b reach autograd as finished tensors, which GradSink and kgw_adam_fused take like any other."""
+    deferred fold, no rider: d W and d b reach autograd as finished tensors, which GradSink and kgw_adam_fused take like any other.
+    A 2-D ``w_all`` [N, T] (per-trait weights, 0 = that trait is not observed at that SNP) takes the kgw_readout_wmse_mtw_* calls:
+    the same launches, the weight read per column."""
 
     @staticmethod
     def forward(ctx, H, W, b, n_id, y_all, w_all, n, relu, h_is_relu=False, unit_grad=False):
@@ -2425,8 +2427,11 @@ class _ReadoutWeightedMSEMulti(torch.autograd.Function):
         assert W.dtype == torch.float32 and b.dtype == torch.float32
         assert n_id.dtype == torch.int32 and y_all.dtype == torch.float32 and w_all.dtype == torch.float64
         assert y_all.dim() == 2 and y_all.shape[1] == T and y_all.is_contiguous() and n_id.numel() >= n
+        assert w_all.dim() == 1 or (tuple(w_all.shape) == (y_all.shape[0], T) and w_all.is_contiguous())
         dev = H.device
         L = _lib.lib()
+        fam = 'kgw_readout_wmse_mtw_' if w_all.dim() == 2 else 'kgw_readout_wmse_mt_'
+        ctx.fam = fam
         pred = torch.empty(n, T, device=dev)
         loss = torch.empty((), dtype=torch.float64, device=dev)
         terms = torch.empty(n, dtype=torch.float64, device=dev)
@@ -2437,15 +2442,15 @@ class _ReadoutWeightedMSEMulti(torch.autograd.Function):
         if unit_grad and ctx.needs_input_grad[0]:
             dH, dW, db = torch.empty_like(H), torch.empty_like(W), torch.empty_like(b)
             part = torch.empty(((n + 3) // 4) * T * (KGW_C + 1), device=dev)
-            _lib.check(L.kgw_readout_wmse_mt_train(_p(H), _p(W), _p(b), _p(n_id), _p(y_all), _p(w_all), n, H.shape[0], T,
-                                                   (1 if relu else 0) | (2 if h_is_relu else 0), _p(pred), _p(loss), _p(dH), _p(dW),
-                                                   _p(db), _p(terms), _p(part), _lib.stream_ptr()), 'kgw_readout_wmse_mt_train')
-            _route('kgw_readout_wmse_mt_train')
+            _lib.check(getattr(L, fam + 'train')(_p(H), _p(W), _p(b), _p(n_id), _p(y_all), _p(w_all), n, H.shape[0], T,
+                                                 (1 if relu else 0) | (2 if h_is_relu else 0), _p(pred), _p(loss), _p(dH), _p(dW),
+                                                 _p(db), _p(terms), _p(part), _lib.stream_ptr()), fam + 'train')
+            _route(fam + 'train')
             ctx.ready = (dH, dW, db)
             return loss, pred
-        _lib.check(L.kgw_readout_wmse_mt_fwd(_p(H), _p(W), _p(b), _p(n_id), _p(y_all), _p(w_all), n, T, 1 if relu else 0, _p(pred),
-                                             _p(loss), _p(terms), _lib.stream_ptr()), 'kgw_readout_wmse_mt_fwd')
-        _route('kgw_readout_wmse_mt_fwd')
+        _lib.check(getattr(L, fam + 'fwd')(_p(H), _p(W), _p(b), _p(n_id), _p(y_all), _p(w_all), n, T, 1 if relu else 0, _p(pred),
+                                           _p(loss), _p(terms), _lib.stream_ptr()), fam + 'fwd')
+        _route(fam + 'fwd')
         ctx.save_for_backward(H, W, pred, n_id, y_all, w_all)
         return loss, pred
 
@@ -2466,9 +2471,9 @@ class _ReadoutWeightedMSEMulti(torch.autograd.Function):
         gloss = gloss.contiguous().to(torch.float64)
         dH, dW, db = torch.empty_like(H), torch.empty_like(W), torch.empty(T, device=H.device)
         part = torch.empty(((ctx.n + 3) // 4) * T * (KGW_C + 1), device=H.device)
-        _lib.check(_lib.lib().kgw_readout_wmse_mt_bwd(_p(H), _p(W), _p(pred), _p(n_id), _p(y_all), _p(w_all), ctx.n, H.shape[0], T,
-                                                      (1 if ctx.relu else 0) | (2 if ctx.h_is_relu else 0), _p(gloss), _p(dH), _p(dW),
-                                                      _p(db), _p(part), _lib.stream_ptr()), 'kgw_readout_wmse_mt_bwd')
+        _lib.check(getattr(_lib.lib(), ctx.fam + 'bwd')(_p(H), _p(W), _p(pred), _p(n_id), _p(y_all), _p(w_all), ctx.n, H.shape[0], T,
+                                                        (1 if ctx.relu else 0) | (2 if ctx.h_is_relu else 0), _p(gloss), _p(dH),
+                                                        _p(dW), _p(db), _p(part), _lib.stream_ptr()), ctx.fam + 'bwd')
         return dH, dW, db, None, None, None, None, None, None, None
 
 
@@ -2517,8 +2522,24 @@ def readout_weighted_mse(H, w_lin, b_lin, n_id, y_all, w_all, n: int, relu: bool
     ``unit_gradient(device)`` to ``backward(gradient=...)`` takes the precomputed gradients as they are; any other loss gradient
     (``(k * loss).backward()``) multiplies them -- correct either way.
     Multi-trait: ``w_lin`` [T,128], ``b_lin`` [T] and a 2-D ``y_all`` [N,T] (T <= 32, one weight per node in ``w_all``) give the
-    mean over seeds and columns and pred [n,T] (kgw_readout_wmse_mt_*: two launches where the node is, nothing deferred)."""
+    mean over seeds and columns and pred [n,T] (kgw_readout_wmse_mt_*: two launches where the node is, nothing deferred).
+    Per-trait weights: a 2-D ``w_all`` [N,T] (float64, contiguous) weighs every (SNP, column) pair on its own, and a weight of
+    exactly 0 marks a pair as unobserved -- its label, NaN included, reaches neither the loss nor a gradient; the divisor stays
+    n * T (kgw_readout_wmse_mtw_*).  With T == 1 a weight [N,1] is the single-column call's [N]."""
     T = w_lin.shape[0] if w_lin.dim() == 2 else 1
+    if w_all.dim() == 2:                # (checked here, before any library call)
+        if w_all.dtype != torch.float64:
+            raise ValueError(f'a weight matrix must be float64, not {w_all.dtype}')
+        if w_all.shape[1] != T:
+            raise ValueError(f'a read-out of {T} columns needs weights [N] or [N, {T}], not {tuple(w_all.shape)}')
+        if y_all.dim() == 2 and w_all.shape[0] != y_all.shape[0]:
+            raise ValueError(f'weights {tuple(w_all.shape)} and labels {tuple(y_all.shape)} differ in their rows')
+        if not w_all.is_contiguous():
+            raise ValueError('a weight matrix must be contiguous (it is read in place, at a fixed address)')
+        if T == 1:
+            w_all = w_all.reshape(-1)
+    elif w_all.dim() != 1:
+        raise ValueError(f'weights must be [N] or [N, T], not {tuple(w_all.shape)}')
     if T == 1:
         if y_all.dim() == 2:
             if y_all.shape[1] != 1:

@@ -1,7 +1,22 @@
 #!/bin/bash
 # A/B of two builds on one box: the default bench alternating between kgwas_amd/csrc/libkgwas_hip_prev.so (KGW_LIB_PATH) and the
 # current library.  usage (gpurun, repo root): bash tools/ab_lib.sh [rounds] [extra bench args]
+# AB_TRAITS=T: the captured step of tools/bench_multitrait.py with T shared-weight label columns instead of the default bench; odd
+# rounds run prev then cur, even rounds cur then prev, so that the prev lines show what the position in a pair alone does.
 n=${1:-3}; shift
+if [ -n "$AB_TRAITS" ]; then
+  for i in $(seq $n); do
+    if [ $((i % 2)) = 1 ]; then order="prev cur"; else order="cur prev"; fi
+    for which in $order; do
+      if [ $which = prev ]; then export KGW_LIB_PATH=$PWD/kgwas_amd/csrc/libkgwas_hip_prev.so; else unset KGW_LIB_PATH; fi
+      python tools/bench_multitrait.py --traits $AB_TRAITS --out '' "$@" 2>/dev/null | python -c "
+import json,sys
+d=json.loads(sys.stdin.read().strip().splitlines()[-1])
+print('$which  T=%d  ms/step %.4f' % (d['traits'], d['ms_per_step']))" || exit 1
+    done
+  done
+  exit 0
+fi
 for i in $(seq $n); do
   for which in prev cur; do
     if [ $which = prev ]; then export KGW_LIB_PATH=$PWD/kgwas_amd/csrc/libkgwas_hip_prev.so; else unset KGW_LIB_PATH; fi
