@@ -8,6 +8,7 @@
 //                           its backward
 //   kgw_dense_optim.h       Adam (kgwas/kgwas.py:116,151) incl. the fused optimiser launch of a captured step
 //   kgw_dense_loss.h        read-out + LD-weighted MSE (model.py:86, kgwas.py:139-145)
+//   kgw_readout_order.h     the fixed summation orders of the read-out fold, shared by kgw_dense_loss.h and kgw_dense_transform.h
 //   kgw_dense_relvec.h      attention vectors u_r / v_r (conv.py:138-151) and the parameter-only end of the backward pass
 //
 // Mapping of the tall TN product (gfx950): v_mfma_f32_32x32x2_f32.  The MFMA operand layout IS the memory layout:
@@ -17,6 +18,7 @@
 // through LDS, blocks through a partial buffer and a second kernel in a fixed order: no atomics, deterministic.
 #include "kgw_common.h"
 #include "kgw_fold_common.h"
+#include "kgw_readout_order.h"
 #include <stdlib.h>
 #include <cstdlib>
 

@@ -12,20 +12,13 @@ namespace {
 __global__ void __launch_bounds__(256) k_wmse_fwd(const float* __restrict__ pred, const int32_t* __restrict__ n_id,
                                                   const float* __restrict__ y, const double* __restrict__ w, int n,
                                                   double* __restrict__ loss) {
-    __shared__ double sm[256];
-    double acc = 0.0;
-    for (int i = threadIdx.x; i < n; i += 256) {
+    __shared__ double sd[256];
+    const double total = kgw_sum256_f64(sd, n, [&](int i) {
         const int g = n_id[i];
         const float d = pred[i] - y[g];
-        acc += w[g] * (double)(d * d);
-    }
-    sm[threadIdx.x] = acc;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if (threadIdx.x < o) sm[threadIdx.x] += sm[threadIdx.x + o];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) loss[0] = sm[0] / (double)n;
+        return w[g] * (double)(d * d);
+    });
+    if (threadIdx.x == 0) loss[0] = total / (double)n;
 }
 
 __global__ void __launch_bounds__(256) k_wmse_bwd(const float* __restrict__ pred, const int32_t* __restrict__ n_id,
@@ -61,52 +54,25 @@ extern "C" int kgw_wmse_bwd(const float* pred, const int32_t* n_id, const float*
 
 // ======================================================================================================
 // kgw_readout_wmse: read-out Linear(128 -> 1) (+ ReLU) of the seed rows (kgwas/model.py:86) fused with the
-// LD-score weighted MSE (kgwas/kgwas.py:139-145).  One block: wavefront w takes seeds w, w+4, ...; partial sums are
-// combined in a fixed order.  _bwd also produces the gradients of the read-out weight / bias and dH (zero for the
-// rows beyond the seeds).
+// LD-score weighted MSE (kgwas/kgwas.py:139-145).  One wavefront per seed, four per block (k_readout_1); per-seed loss terms and
+// per-block weight-gradient partials go to scratch buffers and a second, single-block launch (k_readout_fold, shared with the
+// multi-trait node below) folds them in a fixed order -- parallel across the chip, yet a fixed summation order.  (A "last block
+// folds" hand-off inside one launch was tried: its device-scope fence cost more than the second launch.)  _bwd and _train also
+// produce the gradients of the read-out weight / bias and dH (zero for the rows beyond the seeds).
 // ======================================================================================================
 namespace {
 
-// One wavefront per seed, four per block; per-seed / per-block partial results go to a scratch buffer and a second,
-// single-block launch folds them in index order -- parallel across the chip, yet a fixed summation order.  (A
-// "last block folds" hand-off inside one launch was tried: its device-scope fence cost more than the second launch.)
-__global__ void __launch_bounds__(256) k_readout_wmse_fwd(const float* __restrict__ H, const float* __restrict__ wl,
-                                                          const float* __restrict__ bl, const int32_t* __restrict__ n_id,
-                                                          const float* __restrict__ y, const double* __restrict__ w, int n,
-                                                          int relu, float* __restrict__ pred, double* __restrict__ terms) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int i = blockIdx.x * 4 + wave;
-    if (i >= n) return;
-    const float2 w2 = ((const float2*)wl)[lane];
-    const float2 h2 = ((const float2*)(H + (int64_t)i * KGW_C))[lane];
-    float p = kgw_wave_allsum(fmaf(h2.x, w2.x, h2.y * w2.y)) + bl[0];
-    if (relu) p = fmaxf(p, 0.f);
-    if (lane == 0) {
-        const int g = n_id[i];
-        const float d = p - y[g];
-        pred[i] = p;
-        terms[i] = w[g] * (double)(d * d);
-    }
-}
+enum { KGW_MT_FWD = 0, KGW_MT_TRAIN = 1, KGW_MT_BWD = 2, KGW_MT_BWD_PRED = 3 };    // (the last: k_readout_mt only)
 
-__global__ void __launch_bounds__(256) k_fold_f64(const double* __restrict__ terms, int n, double* __restrict__ out) {
-    __shared__ double sm[256];
-    double acc = 0.0;
-    for (int q = threadIdx.x; q < n; q += 256) acc += terms[q];
-    sm[threadIdx.x] = acc;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if (threadIdx.x < o) sm[threadIdx.x] += sm[threadIdx.x + o];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) out[0] = sm[0] / (double)n;
-}
-
-__global__ void __launch_bounds__(256) k_readout_wmse_bwd(const float* __restrict__ H, const float* __restrict__ wl,
-                                                          const float* __restrict__ pred, const int32_t* __restrict__ n_id,
-                                                          const float* __restrict__ y, const double* __restrict__ w, int n,
-                                                          int64_t rows, int relu, const double* __restrict__ gloss,
-                                                          float* __restrict__ dH, float* __restrict__ part) {
+// _FWD: prediction and loss term of seed i.  _TRAIN (a unit loss gradient: loss.backward()): forward and backward in ONE launch --
+// prediction, loss term, d prediction, the dH row and the block's weight-gradient partial.  _BWD: the same from the forward's
+// predictions and the loss gradient gloss[0].
+template <int MODE>
+__global__ void __launch_bounds__(256) k_readout_1(const float* __restrict__ H, const float* __restrict__ wl, const float* __restrict__ bl,
+                                                   const float* __restrict__ pred_in, const int32_t* __restrict__ n_id,
+                                                   const float* __restrict__ y, const double* __restrict__ w, int n, int64_t rows,
+                                                   int relu, const double* __restrict__ gloss, float* __restrict__ pred,
+                                                   double* __restrict__ terms, float* __restrict__ dH, float* __restrict__ part) {
     __shared__ float sw[4][KGW_C + 1];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int64_t i = (int64_t)blockIdx.x * 4 + wave;
@@ -114,20 +80,32 @@ __global__ void __launch_bounds__(256) k_readout_wmse_bwd(const float* __restric
     float dp = 0.f;
     if (i < n) {
         const float2 w2 = ((const float2*)wl)[lane];
-        const int g = n_id[i];
-        const float p = pred[i];
-        dp = (float)(gloss[0] / (double)n * w[g]) * (2.0f * (p - y[g]));
-        if ((relu & 1) && !(p > 0.f)) dp = 0.f;
         const float2 h2 = ((const float2*)(H + i * KGW_C))[lane];
+        float p;
+        if (MODE == KGW_MT_BWD) {
+            p = pred_in[i];
+        } else {
+            p = kgw_wave_allsum(fmaf(h2.x, w2.x, h2.y * w2.y)) + bl[0];
+            if (relu & 1) p = fmaxf(p, 0.f);
+        }
+        const int g = n_id[i];
+        const float d = p - y[g];
+        if (MODE != KGW_MT_BWD && lane == 0) {
+            pred[i] = p;
+            terms[i] = w[g] * (double)(d * d);
+        }
+        if (MODE == KGW_MT_FWD) return;
+        dp = (float)((MODE == KGW_MT_BWD ? gloss[0] : 1.0) / (double)n * w[g]) * (2.0f * d);
+        if ((relu & 1) && !(p > 0.f)) dp = 0.f;
         // (bit 1 of `relu`: H itself is the output of a ReLU whose backward the caller folds in here: dH *= (H > 0))
         const bool mk = (relu & 2) != 0;
         ((float2*)(dH + i * KGW_C))[lane] = make_float2((!mk || h2.x > 0.f) ? dp * w2.x : 0.f,
                                                          (!mk || h2.y > 0.f) ? dp * w2.y : 0.f);
         dw = make_float2(dp * h2.x, dp * h2.y);
-    } else if (i < rows) {
+    } else if (MODE != KGW_MT_FWD && i < rows) {
         ((float2*)(dH + i * KGW_C))[lane] = make_float2(0.f, 0.f);
     }
-    if ((int64_t)blockIdx.x * 4 >= n) return;            // blocks without seeds hold no partial
+    if (MODE == KGW_MT_FWD || (int64_t)blockIdx.x * 4 >= n) return;            // blocks without seeds hold no partial
     sw[wave][2 * lane] = dw.x; sw[wave][2 * lane + 1] = dw.y;
     if (lane == 0) sw[wave][KGW_C] = dp;
     __syncthreads();
@@ -137,140 +115,61 @@ __global__ void __launch_bounds__(256) k_readout_wmse_bwd(const float* __restric
     }
 }
 
-// d w_lin [128] and d b_lin from the per-block partials [nb][129]: 129 columns x 7 row groups of one block, fixed order
-__global__ void __launch_bounds__(1024) k_readout_fold(const float* __restrict__ part, int nb, float* __restrict__ dwl,
-                                                       float* __restrict__ dbl) {
-    __shared__ float sm[7][KGW_C + 1];
-    const int c = threadIdx.x % (KGW_C + 1), g = threadIdx.x / (KGW_C + 1);
-    if (g < 7) {
-        float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
-        int q = g;
-        for (; q + 21 < nb; q += 28) {
-            a0 += part[(int64_t)q * (KGW_C + 1) + c];        a1 += part[(int64_t)(q + 7) * (KGW_C + 1) + c];
-            a2 += part[(int64_t)(q + 14) * (KGW_C + 1) + c]; a3 += part[(int64_t)(q + 21) * (KGW_C + 1) + c];
-        }
-        for (; q < nb; q += 7) a0 += part[(int64_t)q * (KGW_C + 1) + c];
-        sm[g][c] = (a0 + a1) + (a2 + a3);
-    }
-    __syncthreads();
-    if (g == 0) {
-        const float t = ((sm[0][c] + sm[1][c]) + (sm[2][c] + sm[3][c])) + ((sm[4][c] + sm[5][c]) + sm[6][c]);
-        if (c < KGW_C) dwl[c] = t; else dbl[0] = t;
-    }
-}
-
-// Training step with a unit loss gradient (loss.backward()): forward and backward of the read-out in ONE launch per
-// stage -- the per-seed stage computes prediction, loss term, d prediction, the dH row and the block's weight-gradient
-// partial; the fold stage adds up the loss terms (float64, index order) and the partials.  Two launches instead of four.
-__global__ void __launch_bounds__(256) k_readout_wmse_train(const float* __restrict__ H, const float* __restrict__ wl,
-                                                            const float* __restrict__ bl, const int32_t* __restrict__ n_id,
-                                                            const float* __restrict__ y, const double* __restrict__ w, int n,
-                                                            int64_t rows, int relu, float* __restrict__ pred,
-                                                            double* __restrict__ terms, float* __restrict__ dH,
-                                                            float* __restrict__ part) {
-    __shared__ float sw[4][KGW_C + 1];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int64_t i = (int64_t)blockIdx.x * 4 + wave;
-    float2 dw = make_float2(0.f, 0.f);
-    float dp = 0.f;
-    if (i < n) {
-        const float2 w2 = ((const float2*)wl)[lane];
-        const float2 h2 = ((const float2*)(H + i * KGW_C))[lane];
-        float p = kgw_wave_allsum(fmaf(h2.x, w2.x, h2.y * w2.y)) + bl[0];
-        if (relu & 1) p = fmaxf(p, 0.f);
-        const int g = n_id[i];
-        const float d = p - y[g];
-        if (lane == 0) {
-            pred[i] = p;
-            terms[i] = w[g] * (double)(d * d);
-        }
-        dp = (float)(1.0 / (double)n * w[g]) * (2.0f * d);
-        if ((relu & 1) && !(p > 0.f)) dp = 0.f;
-        const bool mk = (relu & 2) != 0;
-        ((float2*)(dH + i * KGW_C))[lane] = make_float2((!mk || h2.x > 0.f) ? dp * w2.x : 0.f,
-                                                         (!mk || h2.y > 0.f) ? dp * w2.y : 0.f);
-        dw = make_float2(dp * h2.x, dp * h2.y);
-    } else if (i < rows) {
-        ((float2*)(dH + i * KGW_C))[lane] = make_float2(0.f, 0.f);
-    }
-    if ((int64_t)blockIdx.x * 4 >= n) return;            // blocks without seeds hold no partial
-    sw[wave][2 * lane] = dw.x; sw[wave][2 * lane + 1] = dw.y;
-    if (lane == 0) sw[wave][KGW_C] = dp;
-    __syncthreads();
-    if (threadIdx.x <= KGW_C) {
-        const int c = threadIdx.x;
-        part[(int64_t)blockIdx.x * (KGW_C + 1) + c] = (sw[0][c] + sw[1][c]) + (sw[2][c] + sw[3][c]);
-    }
-}
-
-__global__ void __launch_bounds__(1024) k_readout_train_fold(const float* __restrict__ part, int nb, const double* __restrict__ terms,
-                                                             int n, float* __restrict__ dwl, float* __restrict__ dbl,
-                                                             double* __restrict__ loss) {
+// The second launch of every read-out entry point, single-column (T = 1) and multi-trait.  Block t: d W[t] [128] and d b[t] from the
+// per-block partials [nb][T][129] (thread = (c, g): 129 columns x 7 row groups, kgw_walk_finish, then kgw_tree7); block 0 also the loss
+// from the per-seed terms (kgw_sum256_f64, divided by n T).  part == nullptr: the loss only;  terms == nullptr: the gradients only.
+__global__ void __launch_bounds__(1024) k_readout_fold(const float* __restrict__ part, int nb, int T, const double* __restrict__ terms,
+                                                       int n, float* __restrict__ dW, float* __restrict__ db,
+                                                       double* __restrict__ loss) {
     __shared__ float sm[7][KGW_C + 1];
     __shared__ double sd[256];
-    const int c = threadIdx.x % (KGW_C + 1), g = threadIdx.x / (KGW_C + 1);
-    if (g < 7) {
-        float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
-        int q = g;
-        for (; q + 21 < nb; q += 28) {
-            a0 += part[(int64_t)q * (KGW_C + 1) + c];        a1 += part[(int64_t)(q + 7) * (KGW_C + 1) + c];
-            a2 += part[(int64_t)(q + 14) * (KGW_C + 1) + c]; a3 += part[(int64_t)(q + 21) * (KGW_C + 1) + c];
-        }
-        for (; q < nb; q += 7) a0 += part[(int64_t)q * (KGW_C + 1) + c];
-        sm[g][c] = (a0 + a1) + (a2 + a3);
+    const int c = threadIdx.x % (KGW_C + 1), g = threadIdx.x / (KGW_C + 1), t = blockIdx.x;
+    if (part != nullptr && g < 7) {
+        KgwWalk4 a;
+        sm[g][c] = kgw_walk_finish(a, part + (int64_t)t * (KGW_C + 1) + c, g, nb, (int64_t)T * (KGW_C + 1));
     }
-    if (threadIdx.x < 256) {                                  // the loss: same order as k_fold_f64
-        double acc = 0.0;
-        for (int q = threadIdx.x; q < n; q += 256) acc += terms[q];
-        sd[threadIdx.x] = acc;
-    }
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if (threadIdx.x < o) sd[threadIdx.x] += sd[threadIdx.x + o];
+    if (terms != nullptr && t == 0) {                                    // (uniform over the block)
+        const double total = kgw_sum256_f64(sd, n, [&](int q) { return terms[q]; });
+        if (threadIdx.x == 0) loss[0] = total / ((double)n * (double)T);
+    } else {
         __syncthreads();
     }
-    if (threadIdx.x == 0) loss[0] = sd[0] / (double)n;
-    if (g == 0) {
-        const float t = ((sm[0][c] + sm[1][c]) + (sm[2][c] + sm[3][c])) + ((sm[4][c] + sm[5][c]) + sm[6][c]);
-        if (c < KGW_C) dwl[c] = t; else dbl[0] = t;
+    if (part != nullptr && g == 0) {
+        const float s = kgw_tree7(sm, c);
+        if (c < KGW_C) dW[(int64_t)t * KGW_C + c] = s; else db[t] = s;
     }
+}
+
+inline int kgw_readout_fold_launch(const float* part, int nb, int T, const double* terms, int n, float* dW, float* db, double* loss,
+                                   hipStream_t st) {
+    k_readout_fold<<<part != nullptr ? T : 1, 1024, 0, st>>>(part, nb, T, terms, n, dW, db, loss);
+    KGW_LAUNCH_CHECK();
+    return KGW_OK;
+}
+
+// the first launch of the single-column entries: _FWD covers the seeds, the others every row of dH
+template <int MODE>
+int kgw_readout_1_launch(const float* H, const float* w_lin, const float* b_lin, const float* pred_in, const int32_t* n_id, const float* y,
+                         const double* w, int32_t n, int64_t rows, int32_t relu, const double* gloss, float* pred, double* terms, float* dH,
+                         float* part, hipStream_t st) {
+    if (n <= 0 || rows < n) return KGW_E_RANGE;
+    k_readout_1<MODE><<<(unsigned)(((MODE == KGW_MT_FWD ? n : rows) + 3) / 4), 256, 0, st>>>(H, w_lin, b_lin, pred_in, n_id, y, w, n, rows, relu,
+                                                                                            gloss, pred, terms, dH, part);
+    KGW_LAUNCH_CHECK();
+    return KGW_OK;
 }
 
 }  // namespace
-
-extern "C" int kgw_readout_wmse_train_parts(const float* H, const float* w_lin, const float* b_lin, const int32_t* n_id,
-                                            const float* y, const double* w, int32_t n, int64_t rows, int32_t relu, float* pred,
-                                            double* loss, float* dH, float* dw_lin, float* db_lin, double* terms, float* scratch,
-                                            KgwReadoutFold* fold_out, kgw_stream_t stream_) {
-    if (!H || !w_lin || !b_lin || !n_id || !y || !w || !pred || !loss || !dH || !dw_lin || !db_lin || !terms || !scratch || !fold_out)
-        return KGW_E_NULL;
-    if (n <= 0 || rows < n) return KGW_E_RANGE;
-    k_readout_wmse_train<<<(unsigned)((rows + 3) / 4), 256, 0, (hipStream_t)stream_>>>(H, w_lin, b_lin, n_id, y, w, n, rows, relu, pred,
-                                                                                        terms, dH, scratch);
-    KGW_LAUNCH_CHECK();
-    *fold_out = KgwReadoutFold{scratch, terms, dw_lin, db_lin, loss, (n + 3) / 4, n};
-    return KGW_OK;
-}
-
-extern "C" int kgw_readout_train_fold(const KgwReadoutFold* f, kgw_stream_t stream_) {
-    if (!f || !f->scratch || !f->terms || !f->dw_lin || !f->db_lin || !f->loss) return KGW_E_NULL;
-    if (f->n <= 0 || f->nb <= 0) return KGW_E_RANGE;
-    k_readout_train_fold<<<1, 1024, 0, (hipStream_t)stream_>>>(f->scratch, f->nb, f->terms, f->n, f->dw_lin, f->db_lin, f->loss);
-    KGW_LAUNCH_CHECK();
-    return KGW_OK;
-}
 
 extern "C" int kgw_readout_wmse_fwd(const float* H, const float* w_lin, const float* b_lin, const int32_t* n_id,
                                     const float* y, const double* w, int32_t n, int32_t relu, float* pred,
                                     double* loss, double* scratch, kgw_stream_t stream_) {
     if (!H || !w_lin || !b_lin || !n_id || !y || !w || !pred || !loss || !scratch) return KGW_E_NULL;
-    if (n <= 0) return KGW_E_RANGE;
     hipStream_t st = (hipStream_t)stream_;
-    k_readout_wmse_fwd<<<(n + 3) / 4, 256, 0, st>>>(H, w_lin, b_lin, n_id, y, w, n, relu, pred, scratch);
-    KGW_LAUNCH_CHECK();
-    k_fold_f64<<<1, 256, 0, st>>>(scratch, n, loss);
-    KGW_LAUNCH_CHECK();
-    return KGW_OK;
+    // (this entry's `relu` is a truth value, the others' a bit set)
+    const int rc = kgw_readout_1_launch<KGW_MT_FWD>(H, w_lin, b_lin, nullptr, n_id, y, w, n, n, relu != 0, nullptr, pred, scratch, nullptr,
+                                                    nullptr, st);
+    return rc != KGW_OK ? rc : kgw_readout_fold_launch(nullptr, 0, 1, scratch, n, nullptr, nullptr, loss, st);
 }
 
 extern "C" int kgw_readout_wmse_bwd(const float* H, const float* w_lin, const float* pred, const int32_t* n_id,
@@ -279,32 +178,40 @@ extern "C" int kgw_readout_wmse_bwd(const float* H, const float* w_lin, const fl
                                     kgw_stream_t stream_) {
     if (!H || !w_lin || !pred || !n_id || !y || !w || !grad_loss || !dH || !dw_lin || !db_lin || !scratch)
         return KGW_E_NULL;
-    if (n <= 0 || rows < n) return KGW_E_RANGE;
     hipStream_t st = (hipStream_t)stream_;
-    k_readout_wmse_bwd<<<(unsigned)((rows + 3) / 4), 256, 0, st>>>(H, w_lin, pred, n_id, y, w, n, rows, relu, grad_loss, dH,
-                                                                    scratch);
-    KGW_LAUNCH_CHECK();
-    k_readout_fold<<<1, 1024, 0, st>>>(scratch, (n + 3) / 4, dw_lin, db_lin);
-    KGW_LAUNCH_CHECK();
-    return KGW_OK;
+    const int rc = kgw_readout_1_launch<KGW_MT_BWD>(H, w_lin, nullptr, pred, n_id, y, w, n, rows, relu, grad_loss, nullptr, nullptr, dH,
+                                                    scratch, st);
+    return rc != KGW_OK ? rc : kgw_readout_fold_launch(scratch, (n + 3) / 4, 1, nullptr, n, dw_lin, db_lin, nullptr, st);
+}
+
+// (round 4, measured and dropped: the whole training node as ONE block of 16 wavefronts walking the 512 rows -- no partial buffer, no
+//  fold launch -- ran the step 40 - 45 us SLOWER: 32 dependent row trips per wavefront instead of one)
+extern "C" int kgw_readout_wmse_train_parts(const float* H, const float* w_lin, const float* b_lin, const int32_t* n_id,
+                                            const float* y, const double* w, int32_t n, int64_t rows, int32_t relu, float* pred,
+                                            double* loss, float* dH, float* dw_lin, float* db_lin, double* terms, float* scratch,
+                                            KgwReadoutFold* fold_out, kgw_stream_t stream_) {
+    if (!H || !w_lin || !b_lin || !n_id || !y || !w || !pred || !loss || !dH || !dw_lin || !db_lin || !terms || !scratch || !fold_out)
+        return KGW_E_NULL;
+    const int rc = kgw_readout_1_launch<KGW_MT_TRAIN>(H, w_lin, b_lin, nullptr, n_id, y, w, n, rows, relu, nullptr, pred, terms, dH, scratch,
+                                                      (hipStream_t)stream_);
+    if (rc == KGW_OK) *fold_out = KgwReadoutFold{scratch, terms, dw_lin, db_lin, loss, (n + 3) / 4, n};
+    return rc;
+}
+
+extern "C" int kgw_readout_train_fold(const KgwReadoutFold* f, kgw_stream_t stream_) {
+    if (!f || !f->scratch || !f->terms || !f->dw_lin || !f->db_lin || !f->loss) return KGW_E_NULL;
+    if (f->n <= 0 || f->nb <= 0) return KGW_E_RANGE;
+    return kgw_readout_fold_launch(f->scratch, f->nb, 1, f->terms, f->n, f->dw_lin, f->db_lin, f->loss, (hipStream_t)stream_);
 }
 
 extern "C" int kgw_readout_wmse_train(const float* H, const float* w_lin, const float* b_lin, const int32_t* n_id,
                                       const float* y, const double* w, int32_t n, int64_t rows, int32_t relu, float* pred,
                                       double* loss, float* dH, float* dw_lin, float* db_lin, double* terms, float* scratch,
                                       kgw_stream_t stream_) {
-    if (!H || !w_lin || !b_lin || !n_id || !y || !w || !pred || !loss || !dH || !dw_lin || !db_lin || !terms || !scratch)
-        return KGW_E_NULL;
-    if (n <= 0 || rows < n) return KGW_E_RANGE;
-    hipStream_t st = (hipStream_t)stream_;
-    // (round 4, measured and dropped: the whole node as ONE block of 16 wavefronts walking the 512 rows -- no partial buffer, no
-    //  fold launch -- ran the step 40 - 45 us SLOWER: 32 dependent row trips per wavefront instead of one)
-    k_readout_wmse_train<<<(unsigned)((rows + 3) / 4), 256, 0, st>>>(H, w_lin, b_lin, n_id, y, w, n, rows, relu, pred, terms, dH,
-                                                                      scratch);
-    KGW_LAUNCH_CHECK();
-    k_readout_train_fold<<<1, 1024, 0, st>>>(scratch, (n + 3) / 4, terms, n, dw_lin, db_lin, loss);
-    KGW_LAUNCH_CHECK();
-    return KGW_OK;
+    KgwReadoutFold f;
+    const int rc = kgw_readout_wmse_train_parts(H, w_lin, b_lin, n_id, y, w, n, rows, relu, pred, loss, dH, dw_lin, db_lin, terms, scratch,
+                                                &f, stream_);
+    return rc != KGW_OK ? rc : kgw_readout_train_fold(&f, stream_);
 }
 
 // ======================================================================================================
@@ -316,8 +223,8 @@ extern "C" int kgw_readout_wmse_train(const float* H, const float* w_lin, const 
 // row for the T dot products and for dH[i] = sum_t g[i][t] W[t] (t ascending).  Lane t of the wavefront carries column t's label,
 // bias, prediction and d prediction, so the per-seed global traffic is one coalesced access each.  The block's weight-gradient
 // partial [T][129] (128 columns + the bias term) is (g0 h0 + g1 h1) + (g2 h2 + g3 h3) of its four seeds; a second launch of T blocks
-// folds the partials of column t in k_readout_fold's order (seven row groups, four interleaved accumulators, one tree) and block 0
-// adds up the per-seed loss terms in k_fold_f64's order.  No float atomics: reruns are bit-identical.
+// (k_readout_fold above) folds the partials of column t (seven row groups, four interleaved accumulators, one tree) and block 0 adds up
+// the per-seed loss terms (256 float64 accumulators, one tree).  No float atomics: reruns are bit-identical.
 // The forward's dot product, the residual and its square are float64 (the float32 products are exact in it; xor butterfly 1, 2, ...,
 // 32, so every lane holds the same bits), and pred is that sum rounded once to float32.  Where a prediction nearly meets its label the
 // residual is the small difference of two large numbers, and a float32 dot product's rounding (~1e-7 |pred|) would show in the loss at
@@ -335,8 +242,6 @@ extern "C" int kgw_readout_wmse_train(const float* H, const float* w_lin, const 
 namespace {
 
 constexpr int KGW_MT_MAX = 32;                      // T <= 32: one lane of a 32-lane half per column, W <= 16 KB of LDS
-enum { KGW_MT_FWD = 0, KGW_MT_TRAIN = 1, KGW_MT_BWD = 2, KGW_MT_BWD_PRED = 3 };
-
 struct KgwMtArgs {
     const float* H; const float* W; const float* b; const int32_t* n_id; const float* y; const double* w;
     const float* pred_in;               // _BWD: the forward's predictions;  _BWD_PRED: d loss / d pred [n][T]
@@ -462,46 +367,6 @@ __global__ void __launch_bounds__(256) k_readout_mt(const KgwMtArgs a) {
     }
 }
 
-// block t: d W[t] [128] and d b[t] from the per-block partials [nb][T][129] (k_readout_fold's order); block 0 also the loss from the
-// per-seed terms (k_fold_f64's order, divided by n T).  part == nullptr: the loss only;  terms == nullptr: the gradients only.
-__global__ void __launch_bounds__(1024) k_readout_mt_fold(const float* __restrict__ part, int nb, int T, const double* __restrict__ terms,
-                                                          int n, float* __restrict__ dW, float* __restrict__ db,
-                                                          double* __restrict__ loss) {
-    __shared__ float sm[7][KGW_C + 1];
-    __shared__ double sd[256];
-    const int c = threadIdx.x % (KGW_C + 1), g = threadIdx.x / (KGW_C + 1), t = blockIdx.x;
-    const int64_t ld = (int64_t)T * (KGW_C + 1);
-    const bool with_loss = terms != nullptr && t == 0;                   // (uniform over the block)
-    if (part != nullptr && g < 7) {
-        const float* p = part + (int64_t)t * (KGW_C + 1) + c;
-        float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
-        int q = g;
-        for (; q + 21 < nb; q += 28) {
-            a0 += p[(int64_t)q * ld];        a1 += p[(int64_t)(q + 7) * ld];
-            a2 += p[(int64_t)(q + 14) * ld]; a3 += p[(int64_t)(q + 21) * ld];
-        }
-        for (; q < nb; q += 7) a0 += p[(int64_t)q * ld];
-        sm[g][c] = (a0 + a1) + (a2 + a3);
-    }
-    if (with_loss && threadIdx.x < 256) {
-        double acc = 0.0;
-        for (int q = threadIdx.x; q < n; q += 256) acc += terms[q];
-        sd[threadIdx.x] = acc;
-    }
-    __syncthreads();
-    if (with_loss) {
-        for (int o = 128; o > 0; o >>= 1) {
-            if (threadIdx.x < o) sd[threadIdx.x] += sd[threadIdx.x + o];
-            __syncthreads();
-        }
-        if (threadIdx.x == 0) loss[0] = sd[0] / ((double)n * (double)T);
-    }
-    if (part != nullptr && g == 0) {
-        const float s = ((sm[0][c] + sm[1][c]) + (sm[2][c] + sm[3][c])) + ((sm[4][c] + sm[5][c]) + sm[6][c]);
-        if (c < KGW_C) dW[(int64_t)t * KGW_C + c] = s; else db[t] = s;
-    }
-}
-
 inline int kgw_mt_range(int32_t n, int64_t rows, int32_t T) {
     return (n <= 0 || rows < n || T < 1 || T > KGW_MT_MAX || (rows + 3) / 4 > 0x7fffffff) ? KGW_E_RANGE : KGW_OK;
 }
@@ -528,9 +393,7 @@ extern "C" int kgw_readout_mt_pred_bwd(const float* H, const float* W, const flo
     a.H = H; a.W = W; a.pred_in = dpred; a.dH = dH; a.part = scratch; a.rows = rows; a.n = n; a.T = T; a.relu = relu & 2;
     k_readout_mt<KGW_MT_BWD_PRED><<<(unsigned)((rows + 3) / 4), 256, 0, st>>>(a);
     KGW_LAUNCH_CHECK();
-    k_readout_mt_fold<<<T, 1024, 0, st>>>(scratch, (n + 3) / 4, T, nullptr, n, dW, db, nullptr);
-    KGW_LAUNCH_CHECK();
-    return KGW_OK;
+    return kgw_readout_fold_launch(scratch, (n + 3) / 4, T, nullptr, n, dW, db, nullptr, st);
 }
 
 namespace {
@@ -548,9 +411,7 @@ int kgw_mt_wmse_fwd(const float* H, const float* W, const float* b, const int32_
     a.relu = relu;
     k_readout_mt<KGW_MT_FWD, W_COLS><<<(n + 3) / 4, 256, 0, st>>>(a);
     KGW_LAUNCH_CHECK();
-    k_readout_mt_fold<<<1, 1024, 0, st>>>(nullptr, 0, T, scratch, n, nullptr, nullptr, loss);
-    KGW_LAUNCH_CHECK();
-    return KGW_OK;
+    return kgw_readout_fold_launch(nullptr, 0, T, scratch, n, nullptr, nullptr, loss, st);
 }
 
 template <bool W_COLS>
@@ -565,9 +426,7 @@ int kgw_mt_wmse_bwd(const float* H, const float* W, const float* pred, const int
     a.rows = rows; a.n = n; a.T = T; a.relu = relu;
     k_readout_mt<KGW_MT_BWD, W_COLS><<<(unsigned)((rows + 3) / 4), 256, 0, st>>>(a);
     KGW_LAUNCH_CHECK();
-    k_readout_mt_fold<<<T, 1024, 0, st>>>(scratch, (n + 3) / 4, T, nullptr, n, dW, db, nullptr);
-    KGW_LAUNCH_CHECK();
-    return KGW_OK;
+    return kgw_readout_fold_launch(scratch, (n + 3) / 4, T, nullptr, n, dW, db, nullptr, st);
 }
 
 template <bool W_COLS>
@@ -582,9 +441,7 @@ int kgw_mt_wmse_train(const float* H, const float* W, const float* b, const int3
     a.rows = rows; a.n = n; a.T = T; a.relu = relu;
     k_readout_mt<KGW_MT_TRAIN, W_COLS><<<(unsigned)((rows + 3) / 4), 256, 0, st>>>(a);
     KGW_LAUNCH_CHECK();
-    k_readout_mt_fold<<<T, 1024, 0, st>>>(scratch, (n + 3) / 4, T, terms, n, dW, db, loss);
-    KGW_LAUNCH_CHECK();
-    return KGW_OK;
+    return kgw_readout_fold_launch(scratch, (n + 3) / 4, T, terms, n, dW, db, loss, st);
 }
 
 }  // namespace

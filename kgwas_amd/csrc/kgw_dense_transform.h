@@ -368,63 +368,43 @@ __device__ __forceinline__ void ind_colsum_block256(const ColsumJobs& J, const i
 //   the d gamma sums of a folded layer          (k_ind_colsum)
 // -- as blocks of one grid.  They are independent of each other, each is a few hundred latency-bound blocks at two per CU, and as
 // three launches one after the other each waits for the last block of the one before it.  Same code per block, same values.
-// k_readout_train_fold (one block of 1 024 threads: thread = (c, g), 129 x 7) on a 256-thread block that walks the same (c, g) pairs:
-// the step's read-out fold as ONE MORE block of the launch that follows it (kgw_transform_bwd_ex's fold_in).  lds: >= 1.5 k floats
+// k_readout_fold (one block of 1 024 threads: thread = (c, g), 129 x 7; T = 1) on a 256-thread block that walks the same (c, g) pairs
+// with the same accumulators and trees (kgw_readout_order.h): the step's read-out fold as ONE MORE block of the launch that follows it
+// (kgw_transform_bwd_ex's fold_in).  lds: >= 1.5 k floats
 __device__ __forceinline__ void readout_train_fold_block256(const KgwReadoutFold& F, float* lds) {
     float (*sm)[KGW_C + 1] = (float (*)[KGW_C + 1])lds;            // [7][129]
     double* sd = (double*)(lds + 1024);                            // [256] (8-byte aligned: the LDS base is 16-byte aligned)
-    const float* __restrict__ part = F.scratch;
     const int nb = F.nb, n = F.n;
     {   // the thread's (up to) four (c, g) pairs side by side: 16 loads in flight instead of 4 (one pair after the other made this
         // block's latency 3 x the 1 024-thread kernel's -- longer than the launch it rides in)
         int cc[4], gg[4];
         bool ok[4];
-        float a0[4], a1[4], a2[4], a3[4];
+        KgwWalk4 a[4];
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             const int idx = threadIdx.x + 256 * k;
             ok[k] = idx < 7 * (KGW_C + 1);
             cc[k] = ok[k] ? idx % (KGW_C + 1) : 0; gg[k] = ok[k] ? idx / (KGW_C + 1) : 0;
-            a0[k] = a1[k] = a2[k] = a3[k] = 0.f;
         }
-        // (every pair walks q = g, g + 7, ...: the trip counts differ by at most one between the groups -- the common part unrolled
-        //  over the four pairs, the rest pair by pair, every accumulator in the 1 024-thread kernel's order)
+        // (every pair walks q = g, g + 7, ...: the trip counts differ by at most one between the groups -- the rounds all pairs have
+        //  interleaved over the four pairs, the rest pair by pair)
         int qn = 0;                                            // full rounds of 28 every pair has
         while (6 + 28 * qn + 21 < nb) ++qn;
         for (int r = 0; r < qn; ++r) {
 #pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const int q = gg[k] + 28 * r;
-                const float* p = part + (int64_t)q * (KGW_C + 1) + cc[k];
-                a0[k] += p[0]; a1[k] += p[7 * (KGW_C + 1)]; a2[k] += p[14 * (KGW_C + 1)]; a3[k] += p[21 * (KGW_C + 1)];
-            }
+            for (int k = 0; k < 4; ++k) kgw_walk_round(a[k], F.scratch + cc[k], gg[k] + 28 * r, KGW_C + 1);
         }
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-            int q = gg[k] + 28 * qn;
-            for (; q + 21 < nb; q += 28) {
-                a0[k] += part[(int64_t)q * (KGW_C + 1) + cc[k]];        a1[k] += part[(int64_t)(q + 7) * (KGW_C + 1) + cc[k]];
-                a2[k] += part[(int64_t)(q + 14) * (KGW_C + 1) + cc[k]]; a3[k] += part[(int64_t)(q + 21) * (KGW_C + 1) + cc[k]];
-            }
-            for (; q < nb; q += 7) a0[k] += part[(int64_t)q * (KGW_C + 1) + cc[k]];
-            if (ok[k]) sm[gg[k]][cc[k]] = (a0[k] + a1[k]) + (a2[k] + a3[k]);
+            const float s = kgw_walk_finish(a[k], F.scratch + cc[k], gg[k] + 28 * qn, nb, KGW_C + 1);
+            if (ok[k]) sm[gg[k]][cc[k]] = s;
         }
     }
-    {
-        double acc = 0.0;
-        for (int q = threadIdx.x; q < n; q += 256) acc += F.terms[q];
-        sd[threadIdx.x] = acc;
-    }
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if (threadIdx.x < o) sd[threadIdx.x] += sd[threadIdx.x + o];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) F.loss[0] = sd[0] / (double)n;
+    const double total = kgw_sum256_f64(sd, n, [&](int q) { return F.terms[q]; });
+    if (threadIdx.x == 0) F.loss[0] = total / (double)n;
     if (threadIdx.x <= KGW_C) {
-        const int c = threadIdx.x;
-        const float t = ((sm[0][c] + sm[1][c]) + (sm[2][c] + sm[3][c])) + ((sm[4][c] + sm[5][c]) + sm[6][c]);
-        if (c < KGW_C) F.dw_lin[c] = t; else F.db_lin[0] = t;
+        const float t = kgw_tree7(sm, threadIdx.x);
+        if (threadIdx.x < KGW_C) F.dw_lin[threadIdx.x] = t; else F.db_lin[0] = t;
     }
 }
 

@@ -2329,6 +2329,30 @@ def unit_gradient(device) -> torch.Tensor:
     return t
 
 
+def _relu_word(relu, h_is_relu) -> int:
+    """The `relu` argument of the read-out node's _bwd / _train calls: bit 0 = ReLU on the prediction, bit 1 = H is a ReLU's output."""
+    return (1 if relu else 0) | (2 if h_is_relu else 0)
+
+
+def _readout_part(rows: int, T: int, device) -> torch.Tensor:
+    """The per-block partials of d W / d b: one [T][129] per block of four rows."""
+    return torch.empty(((rows + 3) // 4) * T * (KGW_C + 1), device=device)
+
+
+def _is_unit_gradient(gloss) -> bool:
+    unit = _UNIT_GRADS.get(gloss.device)
+    return unit is not None and gloss.data_ptr() == unit.data_ptr()
+
+
+def _for_gradient(gloss, grads):
+    """Gradients precomputed for a loss gradient of 1: as they are for the resident ``unit_gradient``, else scaled by ``gloss`` (a
+    scaled loss, gradient accumulation, plain loss.backward() with its ones_like)."""
+    if _is_unit_gradient(gloss):
+        return grads
+    k = gloss.to(torch.float32)
+    return tuple(g * k for g in grads)
+
+
 class _ReadoutWeightedMSE(torch.autograd.Function):
     """loss = mean(w[n_id] * ([relu](H[:n] @ w_lin^T + b_lin) - y[n_id])**2): the read-out Linear(128 -> 1) of the seed
     rows (kgwas/model.py:86) and the weighted MSE (kgwas/kgwas.py:139-145) as one node, two launches per step."""
@@ -2349,7 +2373,7 @@ class _ReadoutWeightedMSE(torch.autograd.Function):
         if unit_grad and ctx.needs_input_grad[0]:
             # the caller backpropagates a loss gradient of exactly 1: everything the backward returns is computed here
             dH, dw, db = torch.empty_like(H), torch.empty_like(w_lin), torch.empty(1, device=dev)
-            part = torch.empty(((H.shape[0] + 3) // 4) * (KGW_C + 1), device=dev)
+            part = _readout_part(H.shape[0], 1, dev)
             ctx.fold = None
             if _DEFER_READOUT_FOLD and READOUT_FOLD_DEFERRED:
                 # first launch only: the fold of the partial sums waits for the backward pass, where it rides in the next launch
@@ -2357,13 +2381,13 @@ class _ReadoutWeightedMSE(torch.autograd.Function):
                 # then -- only a caller that always runs the backward takes this form (``readout_fold_deferred``)
                 f = _lib.KgwReadoutFold()
                 _lib.check(_lib.lib().kgw_readout_wmse_train_parts(_p(H), _p(w_lin), _p(b_lin), _p(n_id), _p(y_all), _p(w_all), n,
-                                                                   H.shape[0], (1 if relu else 0) | (2 if h_is_relu else 0), _p(pred),
+                                                                   H.shape[0], _relu_word(relu, h_is_relu), _p(pred),
                                                                    _p(loss), _p(dH), _p(dw), _p(db), _p(terms), _p(part), C.byref(f),
                                                                    _lib.stream_ptr()), 'kgw_readout_wmse_train_parts')
                 ctx.fold = (f, (part, terms, loss))
             else:
                 _lib.check(_lib.lib().kgw_readout_wmse_train(_p(H), _p(w_lin), _p(b_lin), _p(n_id), _p(y_all), _p(w_all), n, H.shape[0],
-                                                             (1 if relu else 0) | (2 if h_is_relu else 0), _p(pred), _p(loss), _p(dH),
+                                                             _relu_word(relu, h_is_relu), _p(pred), _p(loss), _p(dH),
                                                              _p(dw), _p(db), _p(terms), _p(part), _lib.stream_ptr()),
                            'kgw_readout_wmse_train')
             ctx.ready = (dH, dw, db)
@@ -2381,8 +2405,7 @@ class _ReadoutWeightedMSE(torch.autograd.Function):
         if ctx.ready is not None:
             dH, dw, db = ctx.ready
             ctx.ready = None
-            unit = _UNIT_GRADS.get(gloss.device)
-            is_unit = unit is not None and gloss.data_ptr() == unit.data_ptr()
+            is_unit = _is_unit_gradient(gloss)
             fold, ctx.fold = getattr(ctx, 'fold', None), None
             if fold is not None:
                 sink = GRAD_SINK
@@ -2393,20 +2416,15 @@ class _ReadoutWeightedMSE(torch.autograd.Function):
                     sink.records[db.data_ptr()] = (None, db.numel(), db.untyped_storage())
                 else:
                     _lib.check(_lib.lib().kgw_readout_train_fold(C.byref(fold[0]), _lib.stream_ptr()), 'kgw_readout_train_fold')
-            if not is_unit:
-                # the caller did NOT backpropagate the resident 1.0 (a scaled loss, gradient accumulation, plain loss.backward()
-                # with its ones_like): the precomputed gradients are for a loss gradient of 1 -- scale them
-                k = gloss.to(torch.float32)
-                dH, dw, db = dH * k, dw * k, db * k
-            return dH, dw, db, None, None, None, None, None, None, None
+            return (*_for_gradient(gloss, (dH, dw, db)), None, None, None, None, None, None, None)
         H, w_lin, pred, n_id, y_all, w_all = ctx.saved_tensors
         gloss = gloss.contiguous().to(torch.float64)
         dH = torch.empty_like(H)
         dw = torch.empty_like(w_lin)
         db = torch.empty(1, device=H.device)
-        part = torch.empty(((H.shape[0] + 3) // 4) * (KGW_C + 1), device=H.device)
+        part = _readout_part(H.shape[0], 1, H.device)
         _lib.check(_lib.lib().kgw_readout_wmse_bwd(_p(H), _p(w_lin), _p(pred), _p(n_id), _p(y_all), _p(w_all), ctx.n,
-                                                   H.shape[0], (1 if ctx.relu else 0) | (2 if ctx.h_is_relu else 0), _p(gloss),
+                                                   H.shape[0], _relu_word(ctx.relu, ctx.h_is_relu), _p(gloss),
                                                    _p(dH), _p(dw), _p(db), _p(part), _lib.stream_ptr()),
                    'kgw_readout_wmse_bwd')
         return dH, dw, db, None, None, None, None, None, None, None
@@ -2441,9 +2459,9 @@ class _ReadoutWeightedMSEMulti(torch.autograd.Function):
         ctx.ready = None
         if unit_grad and ctx.needs_input_grad[0]:
             dH, dW, db = torch.empty_like(H), torch.empty_like(W), torch.empty_like(b)
-            part = torch.empty(((n + 3) // 4) * T * (KGW_C + 1), device=dev)
+            part = _readout_part(n, T, dev)
             _lib.check(getattr(L, fam + 'train')(_p(H), _p(W), _p(b), _p(n_id), _p(y_all), _p(w_all), n, H.shape[0], T,
-                                                 (1 if relu else 0) | (2 if h_is_relu else 0), _p(pred), _p(loss), _p(dH), _p(dW),
+                                                 _relu_word(relu, h_is_relu), _p(pred), _p(loss), _p(dH), _p(dW),
                                                  _p(db), _p(terms), _p(part), _lib.stream_ptr()), fam + 'train')
             _route(fam + 'train')
             ctx.ready = (dH, dW, db)
@@ -2461,18 +2479,14 @@ class _ReadoutWeightedMSEMulti(torch.autograd.Function):
         if ctx.ready is not None:
             dH, dW, db = ctx.ready
             ctx.ready = None
-            unit = _UNIT_GRADS.get(gloss.device)
-            if not (unit is not None and gloss.data_ptr() == unit.data_ptr()):
-                k = gloss.to(torch.float32)            # (not the resident 1.0: the precomputed gradients are for a loss gradient of 1)
-                dH, dW, db = dH * k, dW * k, db * k
-            return dH, dW, db, None, None, None, None, None, None, None
+            return (*_for_gradient(gloss, (dH, dW, db)), None, None, None, None, None, None, None)
         H, W, pred, n_id, y_all, w_all = ctx.saved_tensors
         T = W.shape[0]
         gloss = gloss.contiguous().to(torch.float64)
         dH, dW, db = torch.empty_like(H), torch.empty_like(W), torch.empty(T, device=H.device)
-        part = torch.empty(((ctx.n + 3) // 4) * T * (KGW_C + 1), device=H.device)
+        part = _readout_part(ctx.n, T, H.device)
         _lib.check(getattr(_lib.lib(), ctx.fam + 'bwd')(_p(H), _p(W), _p(pred), _p(n_id), _p(y_all), _p(w_all), ctx.n, H.shape[0], T,
-                                                        (1 if ctx.relu else 0) | (2 if ctx.h_is_relu else 0), _p(gloss), _p(dH),
+                                                        _relu_word(ctx.relu, ctx.h_is_relu), _p(gloss), _p(dH),
                                                         _p(dW), _p(db), _p(part), _lib.stream_ptr()), ctx.fam + 'bwd')
         return dH, dW, db, None, None, None, None, None, None, None
 
@@ -2501,7 +2515,7 @@ class _ReadoutLinearMulti(torch.autograd.Function):
         if n == 0:
             return dH, dW.zero_(), db.zero_()
         dpred = dpred.contiguous()
-        part = torch.empty(((n + 3) // 4) * T * (KGW_C + 1), device=H.device)
+        part = _readout_part(n, T, H.device)
         _lib.check(_lib.lib().kgw_readout_mt_pred_bwd(_p(H), _p(W), _p(dpred), n, n, T, 0, _p(dH), _p(dW), _p(db), _p(part),
                                                       _lib.stream_ptr()), 'kgw_readout_mt_pred_bwd')
         return dH, dW, db
