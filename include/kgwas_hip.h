@@ -208,6 +208,12 @@ typedef struct KgwLayerArgs {
      * into dU / dV [n_rels][128] (zero rows for relations the layer does not compute).  seg_chptr = KgwBatchBuf.seg_chptr;
      * duv_ws: 2 * n_rels * 8 * 128 floats of workspace.  All five or none.                                              */
     float* part_du; const int32_t* seg_chptr; float* duv_ws; float* dU; float* dV;
+    /* optional attention dropout (rule: kgwdrop_keep below), read by kgw_gat_aggregate_fwd and kgw_gat_aggregate_bwd_dst, which
+     * must be given the same three values for one layer of one step.  Together with KGW_F_RAW_WEIGHTS or a non-zero partial_rels
+     * the calls return KGW_E_UNSUPPORTED; a drop_scale that is not finite or < 1 returns KGW_E_RANGE -- before any launch.       */
+    const uint64_t* drop_word_dev; /* device, one 64-bit word read when the kernels run (NULL = no dropout: the plain kernels)   */
+    uint32_t drop_thresh;          /* floor(p * 2^32), 0 <= p < 1                                                               */
+    float drop_scale;              /* (float)(1 / (1 - p))                                                                      */
 } KgwLayerArgs;
 
 /* ---- entry points ------------------------------------------------------------------------ */
@@ -276,6 +282,29 @@ KGWFAN_INLINE uint32_t kgwfan_key(uint64_t sample_seed, int32_t rel, int32_t dst
 int kgw_sample_batch_fanout(const KgwGraph* graph, const KgwBatchBuf* buf, const int64_t* seeds, int32_t n_seeds,
                             int32_t seed_type, const int32_t* fanout /* [n_hops], host */, const uint64_t* sample_seed_dev,
                             kgw_stream_t stream);
+
+/* Attention dropout: alpha = F.dropout(alpha, p, training) after the softmax (kgwas/conv.py:224; the reference's HeteroGNN
+ * never passes p, so like the finite fan-out this is an EXTENSION, off by default).  For LOCAL edge e of the batch (the index
+ * of col_local / e_edge / adp) in layer l:
+ *      base(word, l) = kgwfan_step(kgwfan_step(kgwfan_step(0, lo32(word)), hi32(word)), l)                  (kgwdrop_base)
+ *      keep(e)       = kgwfan_mix32(base ^ e) >= thresh,   thresh = floor(p * 2^32)                          (kgwdrop_keep)
+ *      m'(e)         = keep(e) ? scale : 0,                scale = (float)(1 / (1 - p))
+ *      Z[i, r]       = sum_j m'(e_ij) alpha_ij H_src[j]    (alpha: the UNDROPPED softmax)
+ * -- a pure function of (word, layer, local edge index), and the sampler's edge layout is itself specified exactly, so the
+ * mask depends on no launch geometry, wavefront order or atomic.  stat (row max, denominator), e_edge and kgw_edge_alpha
+ * describe the undropped softmax; a row whose edges are all dropped gets Z = 0.  Backward: because the stored Z is the dropped
+ * one, <dZ_i, Z_i> = sum_k alpha_k dalpha'_k with dalpha'_e = m'(e) <dZ_i, H_j>, so d logit_e = alpha_e (dalpha'_e - <dZ_i, Z_i>)
+ * and the record of the src-major pass is adp[e] = (alpha_e m'(e), d pre-activation_e).  thresh = 0, scale = 1 computes the
+ * bits of the plain call.  word is READ FROM DEVICE MEMORY (KgwLayerArgs.drop_word_dev) when the kernels run: a captured step
+ * replays with another word for every batch.  The trainer sets it to dropout_word(seed, epoch, batch) (kgwas_amd/sampler.py). */
+KGWFAN_INLINE uint32_t kgwdrop_base(uint64_t word, int32_t layer) {
+    uint32_t h = kgwfan_step(0u, (uint32_t)(word & 0xffffffffu));
+    h = kgwfan_step(h, (uint32_t)(word >> 32));
+    return kgwfan_step(h, (uint32_t)layer);
+}
+KGWFAN_INLINE int kgwdrop_keep(uint32_t base, uint32_t local_edge, uint32_t thresh) {
+    return kgwfan_mix32(base ^ local_edge) >= thresh;
+}
 
 /* Replaces: GATConv.edge_update + message + aggregate (kgwas/conv.py:200-228,182) and their
  * autograd for all relations of one layer.                                                    */

@@ -100,6 +100,7 @@ class KgwLayerArgs(C.Structure):
         ('logit_bias', C.c_void_p), ('partial_rels', C.c_uint64),
         ('t_rel', C.c_void_p), ('oct_flags', C.c_void_p), ('rel_sums', C.c_void_p),
         ('part_du', C.c_void_p), ('seg_chptr', C.c_void_p), ('duv_ws', C.c_void_p), ('dU', C.c_void_p), ('dV', C.c_void_p),
+        ('drop_word_dev', C.c_void_p), ('drop_thresh', C.c_uint32), ('drop_scale', C.c_float),
     ]
 
 
@@ -196,6 +197,12 @@ def lib():
     L.kgw_struct_sizes(sizes, 7)
     mine = [C.sizeof(KgwGraph), C.sizeof(KgwBatchMeta), C.sizeof(KgwChunk), C.sizeof(KgwBatchBuf),
             C.sizeof(KgwLayerArgs), C.sizeof(KgwTnJob), C.sizeof(KgwGradSrc)]
+    # (an older library named by KGW_LIB_PATH for an A/B run ends KgwLayerArgs before the attention-dropout fields: it never reads
+    #  them, so the longer mirror is safe to pass; ops.gat_aggregate refuses dropout= with such a library)
+    L.kgw_has_dropout = True
+    if 'KGW_LIB_PATH' in os.environ and sizes[4] == KgwLayerArgs.drop_word_dev.offset:
+        L.kgw_has_dropout = False
+        mine[4] = sizes[4]
     if list(sizes) != mine:
         raise KgwasHipError(f'ABI struct size mismatch: library {list(sizes)} vs binding {mine}')
     L.kgw_sample_batch.argtypes = [C.POINTER(KgwGraph), C.POINTER(KgwBatchBuf), C.c_void_p, C.c_int32,

@@ -88,7 +88,31 @@ struct AggPtrs {
     int layer;
     int raw;                      // forward: raw-logit weights (attention export)
     int relu_in;                  // bwd_src: dH *= (H > 0)
+    const uint64_t* drop_word;    // attention dropout (KgwLayerArgs.drop_word_dev; NULL = off): the 64-bit word of the step,
+    uint32_t drop_thresh;         // floor(p * 2^32) and
+    float drop_scale;             // 1 / (1 - p)
 };
+
+// Attention dropout (include/kgwas_hip.h, kgwdrop_keep): the factor m'(e) of local edge e's message -- drop_scale if the edge is
+// kept, 0 if not.  A pure function of (word, layer, local edge index); the softmax itself (row max, denominator, logits) never
+// sees it.  `base` = kgwdrop_base(word, layer) is formed once per kernel from a wave-uniform load of the word.
+struct DropCtx {
+    uint32_t base, thresh;
+    float scale;
+};
+template <bool DROP>
+__device__ __forceinline__ DropCtx drop_ctx(const AggPtrs& P) {
+    DropCtx D = {0u, 0u, 1.0f};
+    if (DROP) {
+        D.base = kgwdrop_base(*P.drop_word, P.layer);
+        D.thresh = P.drop_thresh;
+        D.scale = P.drop_scale;
+    }
+    return D;
+}
+__device__ __forceinline__ float drop_factor(const DropCtx& D, int e) {
+    return kgwdrop_keep(D.base, (uint32_t)e, D.thresh) ? D.scale : 0.f;
+}
 
 __device__ __forceinline__ float dot4(const float4& a, const float4& b) {
     return fmaf(a.x, b.x, fmaf(a.y, b.y, fmaf(a.z, b.z, a.w * b.w)));
@@ -111,10 +135,13 @@ __device__ __forceinline__ KgwChunk load_chunk(const KgwChunk* chunks, int c) {
 // RAW: the messages are weighted by the leaky_relu logits themselves, no softmax -- what the reference's
 // attention export computes (conv.py:221-223 skips the softmax under return_raw_attention_weights and
 // message() :227-228 multiplies by that alpha; kgwas/utils.py:446-461).
-template <int G, bool RAW>
+// DROP: attention dropout -- the message of edge e is weighted by w * m'(e) (drop_factor; eb = the block's first local edge);
+// the running sum `s` and the logits stay those of the undropped softmax.  With m' == 1.0f the products are the plain values.
+template <int G, bool RAW, bool DROP>
 __device__ __forceinline__ void fwd_group(const float4* __restrict__ Hb4, int colv, int q0, int hn, int nb,
                                           int half, int hl, const float4& u4, float ad, float slope,
-                                          float inv_temp, float& m, float& s, float4& acc, float& ev) {
+                                          float inv_temp, float& m, float& s, float4& acc, float& ev,
+                                          const DropCtx& D, int eb) {
     float4 x[G];
     bool valid[G];
 #pragma unroll
@@ -148,7 +175,8 @@ __device__ __forceinline__ void fwd_group(const float4* __restrict__ Hb4, int co
     for (int p = 0; p < G; ++p) {
         const float w = __expf(t[p] - mn);
         s += w;
-        fma4(acc, w, x[p]);
+        if (DROP) fma4(acc, w * drop_factor(D, eb + half * hn + q0 + p), x[p]);      // (every lane, for every edge)
+        else fma4(acc, w, x[p]);
     }
 }
 
@@ -163,10 +191,10 @@ __device__ __forceinline__ void grp8_load(const float4* __restrict__ Hb4, int co
     }
 }
 
-template <bool RAW>
+template <bool RAW, bool DROP>
 __device__ __forceinline__ void fwd_grp8_compute(const float4 (&x)[8], int q0, int hn, int nb, int half, int hl,
                                                  const float4& u4, float ad, float slope, float inv_temp, float& m, float& s,
-                                                 float4& acc, float& ev) {
+                                                 float4& acc, float& ev, const DropCtx& D, int eb) {
     float part[8];
 #pragma unroll
     for (int p = 0; p < 8; ++p) part[p] = dot4(x[p], u4);
@@ -185,6 +213,7 @@ __device__ __forceinline__ void fwd_grp8_compute(const float4 (&x)[8], int q0, i
         s *= sc; scale4(acc, sc); m = mn;
         w = __expf(t - mn);                                     // 0 for invalid edges (t = -inf, mn finite: m starts at NEG_BIG)
         s += kgw_sum8(w);
+        if (DROP) w *= drop_factor(D, eb + half * hn + qm);    // the lane that owns the edge drops it, after the sum took it
     }
     fma4(acc, kgw_bcast8<0>(w), x[0]); fma4(acc, kgw_bcast8<1>(w), x[1]);
     fma4(acc, kgw_bcast8<2>(w), x[2]); fma4(acc, kgw_bcast8<3>(w), x[3]);
@@ -194,23 +223,26 @@ __device__ __forceinline__ void fwd_grp8_compute(const float4 (&x)[8], int q0, i
 
 // Eight edges per half with the transposed reduction (kgw_half_reduce8): the lane with (hl & 7) == p owns edge q0 + p --
 // its logit, its softmax weight -- and hands the weight to the other lanes of its 8-lane group with one swizzle.
-template <bool RAW>
+template <bool RAW, bool DROP>
 __device__ __forceinline__ void fwd_group8(const float4* __restrict__ Hb4, int colv, int q0, int hn, int nb,
                                            int half, int hl, const float4& u4, float ad, float slope,
-                                           float inv_temp, float& m, float& s, float4& acc, float& ev) {
+                                           float inv_temp, float& m, float& s, float4& acc, float& ev,
+                                           const DropCtx& D, int eb) {
     float4 x[8];
     grp8_load(Hb4, colv, q0, hn, nb, half, hl, x);
-    fwd_grp8_compute<RAW>(x, q0, hn, nb, half, hl, u4, ad, slope, inv_temp, m, s, acc, ev);
+    fwd_grp8_compute<RAW, DROP>(x, q0, hn, nb, half, hl, u4, ad, slope, inv_temp, m, s, acc, ev, D, eb);
 }
 
 // PIPE: software pipelining inside a chunk.  A chunk of n edges used to cost one memory round trip for the column ids of
 // every 64 edges plus one per group of 16 rows (a 256-edge chunk of a hub row: 20 dependent round trips, and the longest
 // chunks set the kernel's tail -- halving KGW_CHUNK alone took 64 -> 58 us); with PIPE the next block's column ids and
 // the next group's rows are requested before the current group is reduced.
-template <bool RAW, bool PIPE>
+template <bool RAW, bool PIPE, bool DROP>
 __global__ void __launch_bounds__(KGW_BLK) k_agg_fwd(LayerTab T, AggPtrs P, float slope, float inv_temp) {
+    static_assert(!(RAW && DROP), "attention dropout applies to softmax weights only");
     const int lane = kgw_lane(), half = lane >> 5, hl = lane & 31;
     const int nw = gridDim.x * 4;
+    const DropCtx D = drop_ctx<DROP>(P);
     const int n_items = P.meta->n_chunks[P.layer - 1];
     for (int c = blockIdx.x * 4 + (threadIdx.x >> 6); c < n_items; c += nw) {
         const KgwChunk ck = load_chunk(P.chunks, c);
@@ -251,22 +283,22 @@ __global__ void __launch_bounds__(KGW_BLK) k_agg_fwd(LayerTab T, AggPtrs P, floa
                     const int q1 = q0 + 8;
                     const bool more1 = hn - q1 > 4;
                     if (more1) grp8_load(Hb4, colv, q1, hn, nb, half, hl, x1);
-                    fwd_grp8_compute<RAW>(x0, q0, hn, nb, half, hl, u4, ad, slope, inv_temp, m, s, acc, ev);
+                    fwd_grp8_compute<RAW, DROP>(x0, q0, hn, nb, half, hl, u4, ad, slope, inv_temp, m, s, acc, ev, D, ck.e0 + b);
                     q0 = q1;
                     if (!more1) break;
                     const int q2 = q1 + 8;
                     const bool more2 = hn - q2 > 4;
                     if (more2) grp8_load(Hb4, colv, q2, hn, nb, half, hl, x0);
-                    fwd_grp8_compute<RAW>(x1, q1, hn, nb, half, hl, u4, ad, slope, inv_temp, m, s, acc, ev);
+                    fwd_grp8_compute<RAW, DROP>(x1, q1, hn, nb, half, hl, u4, ad, slope, inv_temp, m, s, acc, ev, D, ck.e0 + b);
                     q0 = q2;
                     if (!more2) break;
                 }
             }
             for (; q0 < hn;) {
                 const int rem = hn - q0;
-                if (rem > 4)      { fwd_group8<RAW>(Hb4, colv, q0, hn, nb, half, hl, u4, ad, slope, inv_temp, m, s, acc, ev); q0 += 8; }
-                else if (rem > 2) { fwd_group<4, RAW>(Hb4, colv, q0, hn, nb, half, hl, u4, ad, slope, inv_temp, m, s, acc, ev); q0 += 4; }
-                else              { fwd_group<2, RAW>(Hb4, colv, q0, hn, nb, half, hl, u4, ad, slope, inv_temp, m, s, acc, ev); q0 += 2; }
+                if (rem > 4)      { fwd_group8<RAW, DROP>(Hb4, colv, q0, hn, nb, half, hl, u4, ad, slope, inv_temp, m, s, acc, ev, D, ck.e0 + b); q0 += 8; }
+                else if (rem > 2) { fwd_group<4, RAW, DROP>(Hb4, colv, q0, hn, nb, half, hl, u4, ad, slope, inv_temp, m, s, acc, ev, D, ck.e0 + b); q0 += 4; }
+                else              { fwd_group<2, RAW, DROP>(Hb4, colv, q0, hn, nb, half, hl, u4, ad, slope, inv_temp, m, s, acc, ev, D, ck.e0 + b); q0 += 2; }
             }
             const int i = half * hn + hl;
             if (hl < hn && i < nb) P.e_edge[ck.e0 + b + i] = ev;
@@ -358,11 +390,16 @@ __global__ void __launch_bounds__(KGW_BLK) k_agg_fwd_combine(LayerTab T, AggPtrs
 // ------------------------------------------------------------------------------------------------
 // backward, dst-major pass
 // ------------------------------------------------------------------------------------------------
-template <int G>
+// DROP: attention dropout.  The stored Z is the dropped one, so cdot = <dZ_i, Z_i> = sum_k alpha_k m'_k <dZ_i, H_k> still is
+// sum_k alpha_k dalpha'_k with dalpha'_e = m'_e <dZ_i, H_j>: the edge's d alpha takes the factor, every alpha outside it (dlogit,
+// the row sums B and S) stays the undropped softmax, and the record handed to the src-major pass carries the message weight
+// alpha_e m'_e.  With m' == 1.0f the products are the plain values.
+template <int G, bool DROP>
 __device__ __forceinline__ void bwd_group(const float4* __restrict__ Hb4, int colv, float evin, int q0, int hn,
                                           int nb, int half, int hl, const float4& dz4, float cdot, float M,
                                           float inv_den, float slope, float inv_temp, float& av, float& dv,
-                                          float& dsum, float4& ua, float& esum, float& bsum, float& ssum) {
+                                          float& dsum, float4& ua, float& esum, float& bsum, float& ssum,
+                                          const DropCtx& D, int eb) {
     float4 x[G];
     float t[G];
 #pragma unroll
@@ -377,12 +414,17 @@ __device__ __forceinline__ void bwd_group(const float4* __restrict__ Hb4, int co
     }
 #pragma unroll
     for (int p = 0; p < G; ++p) {
-        const float dalpha = kgw_half_allsum(dot4(x[p], dz4));
+        float dalpha = kgw_half_allsum(dot4(x[p], dz4));
         const float alpha = __expf(t[p] * inv_temp - M) * inv_den;
+        float aw = alpha;                                          // message weight of the edge (adp.x)
+        if (DROP) {
+            const float mf = drop_factor(D, eb + half * hn + q0 + p);     // (every lane, for every edge)
+            dalpha *= mf; aw *= mf;
+        }
         const float dlogit = alpha * (dalpha - cdot);
         const float sfac = inv_temp * (t[p] > 0.f ? 1.0f : slope);
         const float dpre = dlogit * sfac;
-        av = (hl == q0 + p) ? alpha : av;
+        av = (hl == q0 + p) ? aw : av;
         dv = (hl == q0 + p) ? dpre : dv;
         dsum += dpre;
         esum += dlogit; bsum += alpha * sfac; ssum += alpha;       // (the row's consistent d a_dst: see k_agg_bwd_dst)
@@ -392,10 +434,11 @@ __device__ __forceinline__ void bwd_group(const float4* __restrict__ Hb4, int co
 
 // Eight edges per half, transposed reduction (see fwd_group8): the lane with (hl & 7) == p owns edge q0 + p.  `dsum`
 // here collects only the lane's OWN edges; the caller folds the 8 residues once per chunk (kgw_sum8).
+template <bool DROP>
 __device__ __forceinline__ void bwd_grp8_compute(const float4 (&x)[8], float evin, int q0, int hn, int nb, int half, int hl,
                                                  const float4& dz4, float cdot, float M, float inv_den, float slope,
                                                  float inv_temp, float& av, float& dv, float& dsum_own, float4& ua,
-                                                 float& esum_own, float& bsum_own, float& ssum_own) {
+                                                 float& esum_own, float& bsum_own, float& ssum_own, const DropCtx& D, int eb) {
     float part[8];
 #pragma unroll
     for (int p = 0; p < 8; ++p) part[p] = dot4(x[p], dz4);
@@ -403,13 +446,18 @@ __device__ __forceinline__ void bwd_grp8_compute(const float4 (&x)[8], float evi
     const bool valid = (qm < hn) && (half * hn + qm < nb);
     const float e = __shfl(evin, half * 32 + (qm & 31), 64);     // logit kept by lane (half, q)
     const float t = valid ? e : -INFINITY;
-    const float dalpha = kgw_half_reduce8(part, hl);
+    float dalpha = kgw_half_reduce8(part, hl);
     const float alpha = __expf(t * inv_temp - M) * inv_den;
+    float aw = alpha;                                            // message weight of the edge (adp.x)
+    if (DROP) {
+        const float mf = drop_factor(D, eb + half * hn + qm);   // the lane that owns the edge
+        dalpha *= mf; aw *= mf;
+    }
     const float dlogit = alpha * (dalpha - cdot);
     const float sfac = inv_temp * (t > 0.f ? 1.0f : slope);
     const float dpre = dlogit * sfac;
     const bool mine = (hl == qm);
-    av = mine ? alpha : av;
+    av = mine ? aw : av;
     dv = mine ? dpre : dv;
     dsum_own += (hl < 8) ? dpre : 0.f;          // one copy per edge: the 8 residues of the first 8-lane group
     esum_own += (hl < 8) ? dlogit : 0.f;
@@ -426,20 +474,23 @@ __device__ __forceinline__ void bwd_grp8_compute(const float4 (&x)[8], float evi
     }
 }
 
+template <bool DROP>
 __device__ __forceinline__ void bwd_group8(const float4* __restrict__ Hb4, int colv, float evin, int q0, int hn,
                                            int nb, int half, int hl, const float4& dz4, float cdot, float M,
                                            float inv_den, float slope, float inv_temp, float& av, float& dv,
-                                           float& dsum_own, float4& ua, float& esum_own, float& bsum_own, float& ssum_own) {
+                                           float& dsum_own, float4& ua, float& esum_own, float& bsum_own, float& ssum_own,
+                                           const DropCtx& D, int eb) {
     float4 x[8];
     grp8_load(Hb4, colv, q0, hn, nb, half, hl, x);
-    bwd_grp8_compute(x, evin, q0, hn, nb, half, hl, dz4, cdot, M, inv_den, slope, inv_temp, av, dv, dsum_own, ua,
-                     esum_own, bsum_own, ssum_own);
+    bwd_grp8_compute<DROP>(x, evin, q0, hn, nb, half, hl, dz4, cdot, M, inv_den, slope, inv_temp, av, dv, dsum_own, ua,
+                           esum_own, bsum_own, ssum_own, D, eb);
 }
 
-template <bool PIPE>
+template <bool PIPE, bool DROP>
 __global__ void __launch_bounds__(KGW_BLK) __attribute__((amdgpu_waves_per_eu(4, 4))) k_agg_bwd_dst(LayerTab T, AggPtrs P, float slope, float inv_temp) {
     const int lane = kgw_lane(), half = lane >> 5, hl = lane & 31;
     const int nw = gridDim.x * 4;
+    const DropCtx D = drop_ctx<DROP>(P);
     const int n_items = P.meta->n_chunks[P.layer - 1];
     for (int c = blockIdx.x * 4 + (threadIdx.x >> 6); c < n_items; c += nw) {
         const KgwChunk ck = load_chunk(P.chunks, c);
@@ -495,31 +546,36 @@ __global__ void __launch_bounds__(KGW_BLK) __attribute__((amdgpu_waves_per_eu(4,
                     const int q1 = q0 + 8;
                     const bool more1 = hn - q1 > 4;
                     if (more1) grp8_load(Hb4, colv, q1, hn, nb, half, hl, x1);
-                    bwd_grp8_compute(x0, evin, q0, hn, nb, half, hl, dz4, cdot, M, inv_den, slope, inv_temp, av, dv, dsum_own, ua,
-                                     esum_own, bsum_own, ssum_own);
+                    bwd_grp8_compute<DROP>(x0, evin, q0, hn, nb, half, hl, dz4, cdot, M, inv_den, slope, inv_temp, av, dv, dsum_own, ua,
+                                           esum_own, bsum_own, ssum_own, D, ck.e0 + b);
                     q0 = q1;
                     if (!more1) break;
                     const int q2 = q1 + 8;
                     const bool more2 = hn - q2 > 4;
                     if (more2) grp8_load(Hb4, colv, q2, hn, nb, half, hl, x0);
-                    bwd_grp8_compute(x1, evin, q1, hn, nb, half, hl, dz4, cdot, M, inv_den, slope, inv_temp, av, dv, dsum_own, ua,
-                                     esum_own, bsum_own, ssum_own);
+                    bwd_grp8_compute<DROP>(x1, evin, q1, hn, nb, half, hl, dz4, cdot, M, inv_den, slope, inv_temp, av, dv, dsum_own, ua,
+                                           esum_own, bsum_own, ssum_own, D, ck.e0 + b);
                     q0 = q2;
                     if (!more2) break;
                 }
             }
             for (; q0 < hn;) {
                 const int rem = hn - q0;
-                if (rem > 4)      { bwd_group8(Hb4, colv, evin, q0, hn, nb, half, hl, dz4, cdot, M, inv_den, slope, inv_temp, av, dv, dsum_own, ua, esum_own, bsum_own, ssum_own); q0 += 8; }
-                else if (rem > 2) { bwd_group<4>(Hb4, colv, evin, q0, hn, nb, half, hl, dz4, cdot, M, inv_den, slope, inv_temp, av, dv, dsum, ua, esum, bsum, ssum); q0 += 4; }
-                else              { bwd_group<2>(Hb4, colv, evin, q0, hn, nb, half, hl, dz4, cdot, M, inv_den, slope, inv_temp, av, dv, dsum, ua, esum, bsum, ssum); q0 += 2; }
+                if (rem > 4)      { bwd_group8<DROP>(Hb4, colv, evin, q0, hn, nb, half, hl, dz4, cdot, M, inv_den, slope, inv_temp, av, dv, dsum_own, ua, esum_own, bsum_own, ssum_own, D, ck.e0 + b); q0 += 8; }
+                else if (rem > 2) { bwd_group<4, DROP>(Hb4, colv, evin, q0, hn, nb, half, hl, dz4, cdot, M, inv_den, slope, inv_temp, av, dv, dsum, ua, esum, bsum, ssum, D, ck.e0 + b); q0 += 4; }
+                else              { bwd_group<2, DROP>(Hb4, colv, evin, q0, hn, nb, half, hl, dz4, cdot, M, inv_den, slope, inv_temp, av, dv, dsum, ua, esum, bsum, ssum, D, ck.e0 + b); q0 += 2; }
             }
             if (mine) ((float2*)P.adp)[ck.e0 + b + i] = make_float2(av, dv);
         }
         dsum += kgw_sum8(dsum_own);                            // lanes 0..7 of each half: the edges handled 8 at a time
         if (P.part_du) {
             ua.x += kgw_xhalf(ua.x); ua.y += kgw_xhalf(ua.y); ua.z += kgw_xhalf(ua.z); ua.w += kgw_xhalf(ua.w);
-            if (half == 0) ((float4*)(P.part_du + (int64_t)c * KGW_C))[hl] = ua;
+            // (DROP: the lane's offset into the record is formed here, from an opaque copy of hl -- hoisted into the prologue, as the
+            //  plain instantiation's is, the address is the one value that no longer fits the 128 registers of four waves per SIMD
+            //  and goes through scratch once per chunk)
+            int hls = hl;
+            if (DROP) __asm__ volatile("" : "+v"(hls));
+            if (half == 0) ((float4*)(P.part_du + (int64_t)c * KGW_C))[hls] = ua;
         }
         esum += kgw_sum8(esum_own); bsum += kgw_sum8(bsum_own); ssum += kgw_sum8(ssum_own);
         const float tot = dsum + kgw_xhalf(dsum);
@@ -1143,8 +1199,26 @@ AggPtrs build_ptrs(const KgwLayerArgs* a) {
     P.n_duv_hops = a->n_multi_hops; P.dH = a->dH; P.da_src = a->da_src; P.multi = a->multi; P.multi_cap = a->multi_cap;
     P.meta = a->meta_dev; P.layer = a->layer;
     P.lbias = a->logit_bias;
+    P.drop_word = a->drop_word_dev; P.drop_thresh = a->drop_thresh; P.drop_scale = a->drop_scale;
     return P;
 }
+
+// attention dropout (KgwLayerArgs.drop_word_dev): refused with raw-logit weights and with partial softmax states
+int check_drop(const KgwLayerArgs* a) {
+    if (!a->drop_word_dev) return KGW_OK;
+    if ((a->flags & KGW_F_RAW_WEIGHTS) || a->partial_rels) return KGW_E_UNSUPPORTED;
+    if (!(isfinite(a->drop_scale) && a->drop_scale >= 1.0f)) return KGW_E_RANGE;
+    return KGW_OK;
+}
+
+// The other PIPE value of every dst-major kernel (the host selects the forward plain and the backward pipelined, see
+// kgw_gat_aggregate_fwd): compiled only for the resource table of profiles/attn_dropout/resource_usage.txt.
+#ifdef KGW_AGG_ALL_PIPE
+template __global__ void k_agg_fwd<false, true, false>(LayerTab, AggPtrs, float, float);
+template __global__ void k_agg_fwd<false, true, true>(LayerTab, AggPtrs, float, float);
+template __global__ void k_agg_bwd_dst<false, false>(LayerTab, AggPtrs, float, float);
+template __global__ void k_agg_bwd_dst<false, true>(LayerTab, AggPtrs, float, float);
+#endif
 
 inline int grid_for_waves(int64_t n_waves) {
     int64_t g = (n_waves + 3) / 4;
@@ -1173,6 +1247,7 @@ inline int grid_fine(int64_t n_items) {
 
 extern "C" int kgw_gat_aggregate_fwd(const KgwLayerArgs* a, kgw_stream_t stream_) {
     if (!a) return KGW_E_NULL;
+    if (int rc = check_drop(a)) return rc;
     if (a->n_chunks == 0) return KGW_OK;
     if (!a->chunks || !a->col_local || !a->H || (!a->a_dst && !a->V) || !a->U || !a->Z || !a->stat || !a->e_edge || !a->part ||
         !a->meta_dev)
@@ -1186,8 +1261,9 @@ extern "C" int kgw_gat_aggregate_fwd(const KgwLayerArgs* a, kgw_stream_t stream_
     // (software-pipelined chunks -- next group's rows + next block's ids in flight -- measured at KGW_CHUNK = 128 on the layer-1
     //  launch of the benchmark: forward 55.5 us plain / 57.5 pipelined (122 VGPRs cost two wavefronts per SIMD), backward-dst
     //  56.8 plain / 53.2 pipelined => the forward plain, the dst-major backward pipelined)
-    if (P.raw) k_agg_fwd<true, false><<<grid_fine(a->n_chunks), KGW_BLK, 0, st>>>(T, P, a->neg_slope, a->inv_temp);
-    else       k_agg_fwd<false, false><<<grid_fine(a->n_chunks), KGW_BLK, 0, st>>>(T, P, a->neg_slope, a->inv_temp);
+    if (P.raw)            k_agg_fwd<true, false, false><<<grid_fine(a->n_chunks), KGW_BLK, 0, st>>>(T, P, a->neg_slope, a->inv_temp);
+    else if (P.drop_word) k_agg_fwd<false, false, true><<<grid_fine(a->n_chunks), KGW_BLK, 0, st>>>(T, P, a->neg_slope, a->inv_temp);
+    else                  k_agg_fwd<false, false, false><<<grid_fine(a->n_chunks), KGW_BLK, 0, st>>>(T, P, a->neg_slope, a->inv_temp);
     KGW_LAUNCH_CHECK();
     if (a->ev_after) KGW_HIP(hipEventRecord((hipEvent_t)a->ev_after, st));
     if (a->multi && a->multi_cap > 0) {     // hub rows: the number of multi-chunk segments is read on the device
@@ -1199,6 +1275,7 @@ extern "C" int kgw_gat_aggregate_fwd(const KgwLayerArgs* a, kgw_stream_t stream_
 
 extern "C" int kgw_gat_aggregate_bwd_dst(const KgwLayerArgs* a, kgw_stream_t stream_) {
     if (!a) return KGW_E_NULL;
+    if (int rc = check_drop(a)) return rc;
     if (a->n_chunks == 0) return KGW_OK;
     if (!a->chunks || !a->col_local || !a->H || !a->Z || !a->stat || !a->e_edge || !a->dZ || !a->adp ||
         !a->da_dst || !a->part_da || !a->meta_dev)
@@ -1209,7 +1286,8 @@ extern "C" int kgw_gat_aggregate_bwd_dst(const KgwLayerArgs* a, kgw_stream_t str
     AggPtrs P = build_ptrs(a);
     hipStream_t st = (hipStream_t)stream_;
     if (a->ev_before) KGW_HIP(hipEventRecord((hipEvent_t)a->ev_before, st));
-    k_agg_bwd_dst<true><<<grid_fine(a->n_chunks), KGW_BLK, 0, st>>>(T, P, a->neg_slope, a->inv_temp);
+    if (P.drop_word) k_agg_bwd_dst<true, true><<<grid_fine(a->n_chunks), KGW_BLK, 0, st>>>(T, P, a->neg_slope, a->inv_temp);
+    else             k_agg_bwd_dst<true, false><<<grid_fine(a->n_chunks), KGW_BLK, 0, st>>>(T, P, a->neg_slope, a->inv_temp);
     KGW_LAUNCH_CHECK();
     if (a->ev_after) KGW_HIP(hipEventRecord((hipEvent_t)a->ev_after, st));
     if (a->multi && a->multi_cap > 0) {

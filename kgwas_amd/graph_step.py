@@ -18,7 +18,7 @@ import numpy as np
 import torch
 
 from . import _lib, ops
-from .sampler import BatchBuffers, NeighborLoader, SampledBatch, check_num_neighbors, fanout_words, sample_into
+from .sampler import BatchBuffers, NeighborLoader, SampledBatch, check_num_neighbors, dropout_words, fanout_words, sample_into
 
 
 # Blocks per launch of a sampler that runs beside a step graph.  Round 6: 1 024 (256 until then).  What the side sampler costs the
@@ -144,7 +144,10 @@ class GraphTrainStep:
         """``num_neighbors`` (None = the reference's [-1] * L): PyG's list form of per-hop fan-outs.  With a finite fan-out the
         batches are redrawn every epoch from (``sample_seed``, epoch, batch index) -- ``set_epoch`` names the epoch, a step past
         the last batch moves on to the next one by itself -- the capacities of the static layout are bounds that hold for every
-        draw (NeighborLoader.measure_caps), and no batch is kept for later epochs (BatchCache off)."""
+        draw (NeighborLoader.measure_caps), and no batch is kept for later epochs (BatchCache off).
+        A model with ``gat_dropout > 0``: the step is captured in training mode (whatever mode the model is in; restored afterwards)
+        and every ``step`` copies the 8-byte word of (``sample_seed``, epoch, batch index) into ``model.drop_word`` ahead of the
+        replay -- the kernels read it when they run.  The batches themselves stay the same from epoch to epoch (BatchCache on)."""
         self.run = run
         self.model = run.model
         self.batch_size = int(batch_size)
@@ -172,6 +175,9 @@ class GraphTrainStep:
         # finite fan-out: the 64-bit sample seed the (captured) sampler reads, fed like ``seeds``; the words of an epoch's batches
         self.sample_word = torch.zeros(1, dtype=torch.int64, device=dev) if self.fanout is not None else None
         self._epoch_words = {}
+        # attention dropout: the words of an epoch's batches (like the fan-out's), copied one at a time into model.drop_word
+        self.dropout = float(getattr(self.model, 'gat_dropout', 0.0)) > 0.0
+        self._drop_words = {}
         self.ld_w = run._ld_weight_vector()             # ([N] or, per-trait weights, [N, T]: resident, read in place by the graph)
         self.capture_optimizer = capture_optimizer
         self.world = 1
@@ -250,7 +256,15 @@ class GraphTrainStep:
         self._want_cache = bool(cache_batches) and os.environ.get('KGW_EPOCH_CACHE', '1') != '0' and self.fanout is None
         # (parameter-only kernels on a parallel branch of the captured step: measured again in round 5 -- 1.397 ms against 1.081, and
         #  the branch's queue displaces the side sampler's, overlap ratio -0.14 -- HIP-graph branches are not a tool here; removed)
-        self._capture()
+        if self.dropout:
+            was_training = self.model.training
+            self.model.train()                     # (the captured step is a TRAINING step: its aggregates take the dropout kernels)
+            try:
+                self._capture()
+            finally:
+                self.model.train(was_training)
+        else:
+            self._capture()
 
     # train on the batch held by bufs[cur]; concurrently sample ``self.seeds`` into bufs[1 - cur]
     def _step_body(self, cur: int):
@@ -366,7 +380,8 @@ class GraphTrainStep:
         m = self.model
         late = set()
         for mlp in (m.snp_feat_mlp, m.gene_feat_mlp, m.go_feat_mlp):
-            mods = [mlp.FC_hidden, mlp.FC_hidden2] + ([] if getattr(m, 'fold_fc', False) else [mlp.FC_output])
+            # (a step that drops attention weights runs layer 1 unfolded: HeteroGNN._dropout)
+            mods = [mlp.FC_hidden, mlp.FC_hidden2] + ([] if getattr(m, 'fold_fc', False) and not self.dropout else [mlp.FC_output])
             for mod in mods:
                 late.update(id(p) for p in mod.parameters())
         return late
@@ -424,8 +439,14 @@ class GraphTrainStep:
                     sample_word=self.sample_word)
 
     def set_epoch(self, epoch: int):
-        """Finite fan-out: the epoch the next ``step`` calls draw for."""
+        """Finite fan-out / attention dropout: the epoch the next ``step`` calls draw for."""
         self.epoch = int(epoch)
+
+    def _feed_dropout(self, i: int, epoch: int):
+        """The dropout word of batch i of ``epoch`` into ``model.drop_word``: one 8-byte device copy on the current stream."""
+        if epoch not in self._drop_words:
+            self._drop_words = {epoch: dropout_words(self.sample_seed, epoch, self.n_batches, self.seeds.device)}
+        self.model.drop_word.copy_(self._drop_words[epoch][i:i + 1])
 
     def _key(self, i: int, epoch: int) -> int:
         """What a buffer holds: batch i -- of epoch ``epoch`` when batches are redrawn every epoch."""
@@ -586,15 +607,19 @@ class GraphTrainStep:
                 self._sampled[1 - cur].record(self._side)
             if self._twin_pending[cur]:
                 main.wait_event(self._sampled[cur])
+            if self.dropout:
+                self._feed_dropout(i, self.epoch)
             self.graphs[cur].replay()
             self._twin_pending[1 - cur] = True
             self._twin_pending[cur] = False
         else:
             self._feed(nxt, nxt_epoch)
+            if self.dropout:
+                self._feed_dropout(i, self.epoch)
             self.graphs[cur].replay()
         self._have[1 - cur] = self._key(nxt, nxt_epoch)
         self._have[cur] = -1
-        if self.fanout is not None and nxt == 0:
+        if (self.fanout is not None or self.dropout) and nxt == 0:
             self.epoch = nxt_epoch               # (a pass is over: the next one draws anew unless set_epoch says otherwise)
         if not self.capture_optimizer:
             if self.split_backward:
@@ -775,9 +800,17 @@ class GraphEvalStep:
 
     def _forward(self, cur: int):
         batch = SampledBatch(self.dg, self.bufs[cur], self.meta, self.input_type, self.batch_size, static=True)
-        with torch.no_grad():
-            out = self.model(batch.x_dict, batch.edge_index_dict, self.batch_size)
-            return out.reshape(-1) if self.T == 1 else out
+        # (evaluation never drops attention weights, whatever mode the caller left the model in)
+        drops = self.model.training and getattr(self.model, 'gat_dropout', 0.0) > 0
+        if drops:
+            self.model.eval()
+        try:
+            with torch.no_grad():
+                out = self.model(batch.x_dict, batch.edge_index_dict, self.batch_size)
+                return out.reshape(-1) if self.T == 1 else out
+        finally:
+            if drops:
+                self.model.train()
 
     def _sample_now(self, which: int, i: int):
         b = self.batch_size

@@ -24,7 +24,7 @@ import torch.nn.functional as F
 from . import dist as kdist
 from . import ops
 from .model import HeteroGNN
-from .sampler import NeighborLoader
+from .sampler import NeighborLoader, dropout_word
 from .utils import (compute_metrics, evaluate_minibatch_clean, get_network_weight, load_pretrained, print_sys, write_tsv,
                     save_model)
 
@@ -49,10 +49,12 @@ class KGWAS:
         self.exp_name = exp_name
 
     def initialize_model(self, gnn_num_layers=2, gnn_hidden_dim=128, gnn_backbone='GAT', gnn_aggr='sum',
-                         gat_num_head=1, no_relu=False, out_channels=1):
+                         gat_num_head=1, no_relu=False, out_channels=1, gat_dropout=0.0):
         """``out_channels`` (extra, default 1 = the reference, kgwas.py:52): T > 1 reads ONE shared trunk out into T label columns
         (``data['SNP'].y`` [N, T], KGWAS_Data.from_synthetic(n_traits=T)) -- a shared-trunk multi-task model, not T independent
-        models.  It enters ``config`` only when it is not 1, so the config.pkl of a single-trait run is what it always was."""
+        models.  It enters ``config`` only when it is not 1, so the config.pkl of a single-trait run is what it always was.
+        ``gat_dropout`` (extra, default 0 = the reference): attention dropout p of the GAT layers while training (HeteroGNN); it
+        enters ``config`` only when it is not 0."""
         self.config = {'gnn_num_layers': gnn_num_layers, 'gnn_hidden_dim': gnn_hidden_dim,
                        'gnn_backbone': gnn_backbone, 'gnn_aggr': gnn_aggr, 'gat_num_head': gat_num_head}
         out_channels = int(out_channels)
@@ -60,10 +62,13 @@ class KGWAS:
             raise NotImplementedError(f'out_channels = {out_channels}: the read-out kernels take 1 to 32 label columns')
         if out_channels != 1:
             self.config['out_channels'] = out_channels
+        gat_dropout = float(gat_dropout)
+        if gat_dropout != 0.0:
+            self.config['gat_dropout'] = gat_dropout
         self.gnn_num_layers = gnn_num_layers
         self.model = HeteroGNN(self.data.data, gnn_hidden_dim, out_channels, gnn_num_layers, gnn_backbone, gnn_aggr,
                                self.data.snp_init_dim_size, self.data.gene_init_dim_size,
-                               self.data.go_init_dim_size, gat_num_head, no_relu=no_relu).to(self.device)
+                               self.data.go_init_dim_size, gat_num_head, no_relu=no_relu, gat_dropout=gat_dropout).to(self.device)
 
     def load_pretrained(self, path):
         import pandas as pd
@@ -134,6 +139,9 @@ class KGWAS:
         batches of the reference's order and owns the SNPs of one id range; validation / test / inference predictions are
         computed shard-wise and summed, so every rank sees the same metrics and keeps the same best model."""
         from .shard import ShardedTrainer
+        if getattr(self.model, 'gat_dropout', 0.0) > 0:
+            raise NotImplementedError("gat_dropout > 0 is not available with parallelism='shard': it would drop inside partial "
+                                      "softmax states; use parallelism='seed'")
         if self.model.lin.out_features != 1:
             raise NotImplementedError("out_channels > 1 (multi-trait labels) is not available with parallelism='shard': the "
                                       "sharded step's read-out and loss are single-column; use parallelism='seed'")
@@ -226,11 +234,14 @@ class KGWAS:
         ld_w = self._ld_weight_vector()
         min_val = -1000
         self.best_model = deepcopy(self.model).to(self.device)
+        dropout = getattr(self.model, 'gat_dropout', 0.0) > 0
         print_sys('Start Training...')
         for ep in range(total_epoch):
             self.model.train()
             if num_neighbors is not None:                            # (a finite fan-out draws anew every epoch)
                 (graph_step if graph_step is not None else self.train_loader).set_epoch(ep)
+            elif dropout and graph_step is not None:                 # (so do the dropout masks, on the same batches)
+                graph_step.set_epoch(ep)
             steps = range(graph_step.n_batches) if graph_step is not None else enumerate(self.train_loader)
             for item in steps:
                 if graph_step is not None:
@@ -239,6 +250,8 @@ class KGWAS:
                         graph_step.poll()                    # of the epoch (no stream sync: the answer is read one poll later)
                 else:
                     step, batch = item
+                    if dropout:                              # (the word the captured step copies in: the same masks either way)
+                        self.model.set_dropout_word(dropout_word(self.seed, ep, step))
                     loss = self.train_step(batch, optimizer, ld_w, world)
                 if self.wandb:
                     self.wandb.log({'training_loss': loss.item()})

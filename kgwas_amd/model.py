@@ -37,13 +37,19 @@ import torch.nn as nn
 
 from . import ops
 from .graph import GraphSchema, HeteroGraph
-from .sampler import SampledBatch, gather_rows_multi, sample_full_graph
+from .sampler import SampledBatch, dropout_word, gather_rows_multi, sample_full_graph
 
 _RELVEC_ALL = os.environ.get('KGW_RELVEC_ALL', '1') != '0'      # (A/B: one relation-vector launch per layer as before)
 
 EdgeType = Tuple[str, str, str]
 GO_TYPES = ('CellularComponent', 'BiologicalProcess', 'MolecularFunction')
 REL_FIELDS = ('att_src', 'att_dst', 'bias', 'lin_src.weight', 'lin_dst.weight')
+
+
+def _signed64(word: int) -> int:
+    """Two's-complement int64 view of a 64-bit word (what an int64 tensor holds)."""
+    word = int(word) & ((1 << 64) - 1)
+    return word - (1 << 64) if word >> 63 else word
 
 
 def edge_key(et: EdgeType) -> str:
@@ -242,16 +248,29 @@ class SagePack(nn.Module):
 
 class HeteroGNN(nn.Module):
     """kgwas/model.py:24-86 (same ctor / forward signature).  ``pyg_data`` only needs ``.edge_types``
-    and ``.node_types``."""
+    and ``.node_types``.  ``gat_dropout`` = p (an extension: the reference's GATConv has the knob, conv.py:44,224, its HeteroGNN
+    never passes it): in training mode the softmax weight of every edge is dropped with probability p and the kept ones scaled
+    by 1 / (1 - p), inside the aggregate kernels; which edges is a pure function of (``drop_word``, layer, local edge index) --
+    kgwdrop_keep in include/kgwas_hip.h.  0 (the default) runs exactly the launches the model ran without it."""
 
     def __init__(self, pyg_data, hidden_channels, out_channels, num_layers, gnn_backbone, gnn_aggr,
-                 snp_init_dim_size, gene_init_dim_size, go_init_dim_size, gat_num_head, no_relu=False):
+                 snp_init_dim_size, gene_init_dim_size, go_init_dim_size, gat_num_head, no_relu=False, gat_dropout=0.0):
         super().__init__()
         if gnn_backbone not in ('GAT', 'SAGE'):
             raise NotImplementedError(f"backbone {gnn_backbone!r}: 'GAT' (the reference default, kgwas.py:52) and 'SAGE' "
                                       "run on the fused MI355X path; GCNConv / SGConv cannot take the bipartite "
                                       "relations HeteroConv hands them (kgwas/model.py:44-46)")
         self.backbone = gnn_backbone
+        gat_dropout = float(gat_dropout)
+        if not 0.0 <= gat_dropout < 1.0:
+            raise ValueError(f'gat_dropout {gat_dropout}: 0 <= p < 1')
+        if gat_dropout != 0.0 and gnn_backbone == 'SAGE':
+            raise ValueError("gat_dropout needs gnn_backbone='GAT': SAGE has no attention weights to drop (its aggregate merely "
+                             "reuses the kernels)")
+        self.gat_dropout = gat_dropout
+        # the 64-bit word of the step's masks, resident on the device: the kernels read it when they run, so a captured step
+        # replays with whatever the trainer copied here (set_dropout_word / GraphTrainStep).  Not part of the state_dict.
+        self.register_buffer('drop_word', torch.tensor([_signed64(dropout_word(0, 0, 0))], dtype=torch.int64), persistent=False)
         if gnn_aggr not in ('sum', 'mean', 'min', 'max'):
             raise NotImplementedError(f"gnn_aggr {gnn_aggr!r}: 'sum' (the reference default, fused), 'mean', 'min' and 'max' are "
                                       "built; 'cat' widens the hidden state to R*128 and breaks the reference's own "
@@ -548,11 +567,25 @@ class HeteroGNN(nn.Module):
             U, V, kap, Wp, gam = ops.fold_fc_output_hip(P, U, V, fc, self._fold_tab, weight=Wv)
         return tys, blocks, zws, U, V, bsum, Wv, kap, Wp, gam
 
+    def set_dropout_word(self, word: int):
+        """The word of the NEXT steps' attention-dropout masks (``dropout_word(seed, epoch, batch)``): one fill of the resident
+        tensor, no synchronisation."""
+        self.drop_word.fill_(_signed64(word))
+
+    def _dropout(self):
+        """``dropout=`` of the training forward's aggregates: (p, word) in training mode with gat_dropout > 0, else None.
+        A forward that drops does NOT fold FC_output into layer 1 (``fold_fc``): the fold moves the Linear's constant c out of the
+        messages as c * sum_j alpha_ij = c, and with dropout that sum is sum_j m'_j alpha_ij, which no kernel writes down -- so
+        the step runs the unfolded route (the one KGW_FOLD_FC=0 takes) and pays FC_output's 128 x 128 Linear over the sampled
+        nodes.  Evaluation and the attention queries never drop and keep the fold."""
+        return (self.gat_dropout, self.drop_word) if (self.training and self.gat_dropout > 0.0) else None
+
     def _fused_layers(self, batch: SampledBatch, h: Dict[str, torch.Tensor], want_attention=False, hbuf=None,
-                      last_premasked=False, folded=False, prep=None):
+                      last_premasked=False, folded=False, prep=None, dropout=None):
         """``folded``: h holds the feature MLPs' hidden state h2 (``_embed_all(fold=True)``), not their output: layer 1 runs
         with FC_output folded into its relation parameters (ops.fold_fc_output_hip).  ``prep``: per layer, what
-        ``_layer_params`` returns, computed ahead by the caller."""
+        ``_layer_params`` returns, computed ahead by the caller.  ``dropout``: see ``_dropout`` (only ``forward`` and
+        ``forward_loss`` pass it: the attention queries never drop)."""
         if self.backbone == 'SAGE':
             if want_attention:
                 raise NotImplementedError('attention weights exist for the GAT backbone only (kgwas/model.py:65-72)')
@@ -584,7 +617,8 @@ class HeteroGNN(nn.Module):
             # into this node's)
             fused = self.aggr in ('sum', 'mean')
             Z, stat, e_edge = ops.gat_aggregate(batch, l, H, U, V, self.negative_slope, self.temperature,
-                                                relu_input=((l > 1 or folded) and fused), zbuf=zws, logit_bias=kap)
+                                                relu_input=((l > 1 or folded) and fused), zbuf=zws, logit_bias=kap,
+                                                dropout=dropout)
             if want_attention:
                 attn.append(ops.edge_alpha(batch, l, stat, e_edge, self.temperature))
             if not fused:
@@ -625,8 +659,10 @@ class HeteroGNN(nn.Module):
         if batch is None:
             batch = self._block_from_coo(x_dict, edge_index_dict)
         hbuf, blocks = self._layer_input(batch, 1)
-        h = self._embed_all(batch, x_dict, blocks, fold=self.fold_fc)
-        h, attn = self._fused_layers(batch, h, hbuf=hbuf, folded=self.fold_fc)
+        drop = self._dropout()
+        fold = self.fold_fc and drop is None                    # (see _dropout: a step that drops runs layer 1 unfolded)
+        h = self._embed_all(batch, x_dict, blocks, fold=fold)
+        h, attn = self._fused_layers(batch, h, hbuf=hbuf, folded=fold, dropout=drop)
         snp = h['SNP']
         out = self._readout(snp[:batch_size])
         if return_h:                                            # model.py:78-79
@@ -673,15 +709,17 @@ class HeteroGNN(nn.Module):
         # what depends on the parameters only -- the relation vectors of all layers, the FC_output fold -- is prepared FIRST and
         # handed to the first gene Linear's kgw_gemm3 launch as rider blocks (ops.ParamRiders); whatever no launch took is
         # launched the ordinary way when the scope closes, before the layers read it
+        drop = self._dropout()
+        fold = self.fold_fc and drop is None                    # (see _dropout: a step that drops runs layer 1 unfolded)
         riders = ops.ParamRiders() if (ops._G3_RIDERS and self.backbone == 'GAT' and self.num_layers > 1 and _RELVEC_ALL) else None
         with ops.param_riders_scope(riders):
             if riders is not None:
-                prep = self._all_layer_params(batch, self.fold_fc)
-            h = self._embed_all(batch, x_dict, blocks, fold=self.fold_fc)
+                prep = self._all_layer_params(batch, fold)
+            h = self._embed_all(batch, x_dict, blocks, fold=fold)
         self.last_riders_taken = riders.taken if riders is not None else 0
         if mlp_out is not None:
             mlp_out.extend(h.values())
-        h, _ = self._fused_layers(batch, h, hbuf=hbuf, last_premasked=gat, folded=self.fold_fc, prep=prep)
+        h, _ = self._fused_layers(batch, h, hbuf=hbuf, last_premasked=gat, folded=fold, prep=prep, dropout=drop)
         return ops.readout_weighted_mse(h['SNP'], self.lin.weight, self.lin.bias, n_id, y_all, w_all, batch_size,
                                         relu=not self.no_relu, h_is_relu=gat, unit_grad=unit_grad)
 

@@ -16,6 +16,7 @@ import torch
 
 from . import _lib
 from ._lib import KGW_C, PART_STRIDE, KgwLayerArgs
+from .sampler import dropout_params
 
 
 def _p(t):
@@ -450,9 +451,16 @@ def _layer_args(batch, layer: int, neg_slope: float, inv_temp: float) -> KgwLaye
     return a
 
 
+def _set_dropout(a: KgwLayerArgs, dropout):
+    """The attention-dropout fields of one aggregate call: ``dropout`` = (thresh, scale, word tensor) or None."""
+    if dropout is not None:
+        a.drop_thresh, a.drop_scale, a.drop_word_dev = dropout[0], dropout[1], _p(dropout[2])
+
+
 class _GatAggregate(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, H, U, V, batch, layer, neg_slope, inv_temp, raw_weights=False, relu_input=False, zbuf=None, lbias=None):
+    def forward(ctx, H, U, V, batch, layer, neg_slope, inv_temp, raw_weights=False, relu_input=False, zbuf=None, lbias=None,
+                dropout=None):
         dg, m = batch.dg, batch.meta
         NT = dg.schema.NT
         z_rows = int(m.z_base[layer - 1][NT])
@@ -485,6 +493,8 @@ class _GatAggregate(torch.autograd.Function):
         a.flags = 1 if raw_weights else 0          # KGW_F_RAW_WEIGHTS
         ctx.raw_weights = raw_weights
         ctx.relu_input = relu_input
+        ctx.dropout = dropout                      # (forward and backward hand the kernels the same word, threshold and scale)
+        _set_dropout(a, dropout)
         a.Z, a.stat, a.e_edge, a.part = _p(Z), _p(stat), _p(e_edge), _p(part)
         TIMER.attach(a, 'fwd', layer, n_edges, z_rows, n_src)
         # SNP-sharded multi-GPU mode (kgwas_amd/shard.py): relations whose sources this rank holds only in part leave
@@ -506,7 +516,7 @@ class _GatAggregate(torch.autograd.Function):
         if ctx.raw_weights:
             raise RuntimeError('raw-logit aggregation (attention export) is inference only')
         if dZ is None:
-            return (None,) * 11
+            return (None,) * 12
         H, U, V, Z, stat, e_edge = ctx.saved_tensors
         batch, layer = ctx.batch, ctx.layer
         dg, m = batch.dg, batch.meta
@@ -535,6 +545,7 @@ class _GatAggregate(torch.autograd.Function):
         a.H, a.U, a.V, a.Z, a.stat, a.e_edge = _p(H), _p(U), _p(V), _p(Z), _p(stat), _p(e_edge)
         a.dZ, a.adp, a.da_dst, a.part_da = _p(dZf), _p(adp), _p(da_dst), _p(part_da)
         a.dH = _p(dH)
+        _set_dropout(a, ctx.dropout)
         if xchg is not None:
             a.partial_rels = xchg.mask[layer]      # (their rows' d a_dst stay plain sums over this rank's edges: kgw_gat_aggregate_bwd_dst)
         riders = _DUV_RIDERS and n_src > 0 and n_chunks > 0
@@ -576,7 +587,7 @@ class _GatAggregate(torch.autograd.Function):
             dU, dV = torch.zeros_like(U), torch.zeros_like(V)
         if ctx.has_lbias and not n_src:                  # (no source rows: the launch above did not run)
             _lib.check(L.kgw_relation_sums(C.byref(a), _p(da_dst), _p(dlb), _lib.stream_ptr()), 'kgw_relation_sums')
-        return dH[:n_src], dU, dV, None, None, None, None, None, None, None, dlb
+        return dH[:n_src], dU, dV, None, None, None, None, None, None, None, dlb, None
 
 
 def aggregate_workspace(batch, layer: int, device) -> torch.Tensor:
@@ -588,7 +599,7 @@ def aggregate_workspace(batch, layer: int, device) -> torch.Tensor:
 
 def gat_aggregate(batch, layer: int, H: torch.Tensor, U: torch.Tensor, V: torch.Tensor,
                   neg_slope: float = 0.2, temperature: float = 1.0, raw_weights: bool = False,
-                  relu_input: bool = False, zbuf: torch.Tensor = None, logit_bias: torch.Tensor = None):
+                  relu_input: bool = False, zbuf: torch.Tensor = None, logit_bias: torch.Tensor = None, dropout=None):
     """Z[i, r] = sum_j softmax_j(leaky_relu(<H_src[j], u_r> + <H_dst[i], v_r>) / T) H_src[j] for every live relation
     of the layer.  H [n_src_rows,128]: layer input, type-major (``meta.src_base``; a destination node is row i of
     its own type's block); U, V [n_rels,128] by relation id.  Returns (Z [z_rows,128], stat [z_rows,2] =
@@ -600,10 +611,25 @@ def gat_aggregate(batch, layer: int, H: torch.Tensor, U: torch.Tensor, V: torch.
     produced it expects its incoming gradient ALREADY multiplied by (H > 0): the source-side backward does it while
     writing dH (see layer_transform's ``premasked``).  ``zbuf``: an ``aggregate_workspace`` that is ALREADY zero.
     ``logit_bias`` [n_rels]: constant added to the pre-activation logit of every edge of a relation (FC_output folded
-    into layer 1, see fold_fc_output_hip); differentiable."""
-    stat, e_edge, Z = _GatAggregate.apply(H, U, V, batch, layer, float(neg_slope), 1.0 / float(temperature), raw_weights,
-                                          relu_input, zbuf, logit_bias)
+    into layer 1, see fold_fc_output_hip); differentiable.
+    ``dropout`` = (p, word): attention dropout, Z[i, r] = sum_j m'(e_ij) alpha_ij H_src[j] with m'(e) = 1 / (1 - p) for a kept
+    local edge and 0 for a dropped one (the rule: kgwdrop_keep in include/kgwas_hip.h); ``word`` is an int64 device tensor of
+    one element, READ WHEN THE KERNELS RUN (a captured step replays with whatever it then holds).  stat and e_edge stay those
+    of the undropped softmax.  A given ``dropout`` always takes the dropout kernels, at p = 0.0 too (the same bits as None).
+    Not with ``raw_weights`` and not in the SNP-sharded mode."""
     xchg = getattr(batch, 'exchange', None)
+    if dropout is not None:
+        if raw_weights:
+            raise ValueError('attention dropout applies to softmax weights: not with raw_weights=True')
+        if xchg is not None:
+            raise NotImplementedError('attention dropout inside partial softmax states (SNP-sharded mode) is not built')
+        p, word = dropout
+        assert word.dtype == torch.int64 and word.numel() == 1 and word.is_cuda and word.is_contiguous()
+        if not _lib.lib().kgw_has_dropout:
+            raise _lib.KgwasHipError('this libkgwas_hip.so predates attention dropout')
+        dropout = dropout_params(p) + (word,)
+    stat, e_edge, Z = _GatAggregate.apply(H, U, V, batch, layer, float(neg_slope), 1.0 / float(temperature), raw_weights,
+                                          relu_input, zbuf, logit_bias, dropout)
     if xchg is not None and xchg.staged and xchg.mask[layer] and Z.requires_grad:
         # SNP-sharded mode, step captured in segments: cut the autograd graph at the merged Z -- the trainer sums the gradient
         # of this leaf over the ranks (a collective BETWEEN two graph segments) and continues the backward from Z

@@ -539,6 +539,34 @@ def fanout_words(seed: int, epoch: int, n_batches: int, device) -> torch.Tensor:
     return torch.from_numpy(w.copy()).to(device)
 
 
+_DROPOUT_TAG = 0x64726F706F757421       # the bytes of 'dropout!'
+
+
+def dropout_word(seed: int, epoch: int, batch: int) -> int:
+    """The 64-bit attention-dropout word of batch ``batch`` of epoch ``epoch`` of a run made with ``seed``: a pure function --
+    the splitmix64 rounds of ``fanout_sample_word`` with one constant tag mixed in first, so that the masks of a step are not
+    tied to the fan-out draw of the same (seed, epoch, batch).  (The kernels' rule takes it from there: kgwdrop_keep in
+    include/kgwas_hip.h.)"""
+    z = _splitmix64(_DROPOUT_TAG)
+    z = _splitmix64(z ^ (int(seed) & _M64))
+    z = _splitmix64(z ^ (int(epoch) & _M64))
+    return _splitmix64(z ^ (int(batch) & _M64))
+
+
+def dropout_words(seed: int, epoch: int, n_batches: int, device) -> torch.Tensor:
+    """int64 device tensor [n_batches]: the dropout words of an epoch's batches (two's-complement view of the 64-bit words)."""
+    w = np.array([dropout_word(seed, epoch, i) for i in range(n_batches)], dtype=np.uint64).view(np.int64)
+    return torch.from_numpy(w.copy()).to(device)
+
+
+def dropout_params(p: float):
+    """(thresh, scale) of the kernels' rule for drop probability ``p``: floor(p * 2^32) from the double, float32(1 / (1 - p))."""
+    p = float(p)
+    if not 0.0 <= p < 1.0:
+        raise ValueError(f'attention dropout p = {p}: 0 <= p < 1')
+    return int(p * 4294967296.0), float(np.float32(1.0 / (1.0 - p)))
+
+
 def check_num_neighbors(num_neighbors) -> Optional[list]:
     """None for the reference's [-1] * L, else the list of per-hop fan-outs (each -1 or >= 1); refuses what is not built."""
     if isinstance(num_neighbors, dict):
