@@ -517,7 +517,9 @@ int kgw_mlp2w_fwd(int32_t n_jobs, const float* const* src, const int32_t* const*
  * d W1 product -- never written.  workspace: kgw_mlp2_bwd_first_workspace_floats(rows) floats.
  * Variant for a WIDE first layer computed on a resident feature matrix (the gene layer): in_ids [rows] (row r of the product
  * reads dH2[in_ids[r]], < 0: the node is not in the batch, its dh1 row is zero), dZ [rows, 128] receives the masked dh1 rows
- * (the layer's own weight gradient is a library product over them) and K1 = 0 leaves only d b1 (X, dW1 unused).        */
+ * (the layer's own weight gradient is a library product over them) and K1 = 0 leaves only d b1 (X, dW1 unused).
+ * rows_dev (see kgw_linear): rows [*rows_dev, rows) take no part in d W1 / d b1 and are not read; dZ rows at and past
+ * *rows_dev are NOT written -- they keep what the buffer held (unlike kgw_linear's Y, which gets zeros there).           */
 int64_t kgw_mlp2_bwd_first_workspace_floats(int64_t rows);
 int kgw_mlp2_bwd_first(const float* dH2, int64_t ldd, const float* W2, int64_t ldw2, const float* H1, int64_t ldh1,
                        const float* X, int64_t ldx, int32_t K1, int64_t rows, const int32_t* rows_dev, float* dW1,

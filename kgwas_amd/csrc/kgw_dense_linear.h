@@ -1033,6 +1033,11 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
     const int li = lane & 31, lk = lane >> 5;
     int64_t rows = a.rows;
     if (a.rows_dev) { const int64_t r = *a.rows_dev; rows = r < 0 ? 0 : (r < a.rows ? r : a.rows); }
+    if (rows == 0) {   // an empty batch: zero partials and out (before any barrier: the whole block leaves) -- with ntiles == 0 the
+                       // first prefetch below would form rows -32 .. -1 of dH2 / H1 / in_ids, which the clamp at rows - 1 does not catch
+        for (int f = tid; f < 4096; f += 256) a.part[(int64_t)blockIdx.x * 4096 + f] = 0.f;
+        return;
+    }
     const int ntiles = (int)((rows + 31) / 32);
     const int nw = (int)gridDim.x * 4;
     float* Tw = Tl + wave * 32 * TST;
@@ -1203,6 +1208,11 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
     const unsigned sgn = (li & 1) ? 0x80000000u : 0u;
     int64_t rows = a.rows;
     if (a.rows_dev) { const int64_t r = *a.rows_dev; rows = r < 0 ? 0 : (r < a.rows ? r : a.rows); }
+    if (rows == 0) {   // an empty batch: zero partials and out (before any barrier: the whole block leaves) -- with ntiles == 0 the
+                       // first prefetch below would form rows -32 .. -1 of dH2 / H1 / in_ids, which the clamp at rows - 1 does not catch
+        for (int f = tid; f < 4096; f += 256) a.part[(int64_t)blockIdx.x * 4096 + f] = 0.f;
+        return;
+    }
     const int ntiles = (int)((rows + 31) / 32);
     const int nw = (int)gridDim.x * 4;
     float* Tw = Tl + wave * 32 * TS2;
