@@ -4,8 +4,9 @@ A step of kgwas/kgwas.py:129-151 is ~300 short launches; issued one by one the h
 pace (5.1 ms of enqueue for 3.7 ms of kernels on MI355X).  With a *static layout* -- every per-batch row block
 padded to a capacity measured over the loader's fixed batch order, actual counts kept on the device
 (KgwBatchMeta) -- all buffer addresses and launch geometries are batch independent, so
-sampling -> feature MLPs -> fused attention layers -> loss -> backward -> Adam is captured once and replayed
-with a single launch per batch.  Padding rows carry exactly zero gradient (k_agg_bwd_src zero-fills them), so
+feature MLPs -> fused attention layers -> loss -> backward -> Adam is captured once and replayed with a single
+launch per batch, and the sampling of the NEXT batch is a second captured graph replayed beside it on a side stream (two
+batch buffers, SideSampler).  Padding rows carry exactly zero gradient (k_agg_bwd_src zero-fills them), so
 parameter gradients equal the eager path's (tests/test_gpu_graph.py).
 """
 from __future__ import annotations
@@ -29,11 +30,101 @@ from .sampler import BatchBuffers, NeighborLoader, SampledBatch, check_num_neigh
 # +43 us over 1 024).  More blocks = shorter sampler kernels: 1.060 / 1.045 / 1.041 / 1.051 ms per step at 256 / 512 / 1 024 / 2 048
 # blocks on one box, 1.068 / 1.135 / 1.48 at 128 / 64 / 32 (profiles/r6/r6_sampler_geometry.txt).
 SIDE_SAMPLER_GRID = int(os.environ.get('KGW_SIDE_SAMPLER_GRID', '1024'))       # (the knob: re-measured whenever the sampler changes)
-def side_stream(device):
-    """The stream the next batch's sampler graph is captured on and replayed on: an ordinary stream.  (Round 4 measured a CU-masked
-    stream -- the two graphs then ran strictly one after the other --, stream priorities and a timed offset at the head of the
-    sampler's graph: none helped, profiles/r4/r4_sampler_interference_experiments.txt; the knobs are gone.)"""
-    return torch.cuda.Stream(device=device)
+
+
+class SideSampler:
+    """The bookkeeping of a double-buffered sampler beside a captured step: while the step computes on one batch buffer, the next
+    batch is put into the other on ``stream``.  What "put" means -- feed seeds, replay a sampler graph, restore a cache slot --
+    is the trainer's callable; which batch a buffer holds (``holds``, a key of the trainer's choosing, -1 = nothing) and whether
+    the side stream still owes it (``pending``, with the event recorded behind the work) are kept here."""
+
+    def __init__(self, stream):
+        self.stream = stream
+        self.done = [torch.cuda.Event(), torch.cuda.Event()]
+        self.forget()
+
+    def forget(self):
+        """No buffer holds a batch anybody may rely on (the caller has seen the side stream drain)."""
+        self.holds, self.pending = [-1, -1], [False, False]
+
+    def prefetch(self, w: int, key, fill):
+        """Run ``fill()`` on the side stream, behind everything the current stream holds so far (the last reader of buffer ``w``
+        is among it); buffer ``w`` then holds ``key``."""
+        self.stream.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(self.stream):
+            fill()
+            self.done[w].record(self.stream)
+        self.holds[w], self.pending[w] = key, True
+
+    def wait(self, w: int):
+        """The current stream goes on only after an outstanding prefetch into buffer ``w``."""
+        if self.pending[w]:
+            torch.cuda.current_stream().wait_event(self.done[w])
+            self.pending[w] = False
+
+
+def keep_training_state(model, opt, stats):
+    """Snapshot of what real training steps move -- parameters, the optimiser's state tensors, its step counter, the running
+    totals -- for a caller that runs such steps without meaning them (capture warm-up, a timing measurement).  Returns the
+    function that puts it back: tensors that existed are copied back, optimiser state created since is zeroed (Adam's initial
+    state).  The caller synchronises before it restores."""
+    params = [p for p in model.parameters()]
+    snap = [p.detach().clone() for p in params]
+    ostate = {p: {k: v.clone() for k, v in st.items() if torch.is_tensor(v)} for p, st in opt.state.items()}
+    step0, stats0 = opt.step_dev.clone(), stats.clone()
+
+    def restore():
+        with torch.no_grad():
+            for p, q in zip(params, snap):
+                p.copy_(q)
+            for p, st in opt.state.items():
+                for k, v in st.items():
+                    if torch.is_tensor(v):
+                        v.copy_(ostate[p][k]) if p in ostate and k in ostate[p] else v.zero_()
+            opt.step_dev.copy_(step0)
+            stats.copy_(stats0)
+    return restore
+
+
+def time_sampler_overlap(step, step_without_sampler, sampler_alone, n: int) -> dict:
+    """``n`` calls of each of the three (after two steps, and one step without the sampler, to settle); overlap = the share of
+    the sampler's own time that did NOT show up in the step."""
+    import time
+
+    def timed(fn):
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        for i in range(n):
+            fn(i)
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t) / n * 1e3
+    for i in range(2):
+        step(i)
+    both = timed(step)
+    step_without_sampler(0)
+    alone = timed(step_without_sampler)
+    sampler = timed(sampler_alone)
+    ratio = (alone + sampler - both) / max(sampler, 1e-9)
+    return {'step_with_side_sampler_ms': both, 'step_alone_ms': alone, 'sampler_alone_ms': sampler, 'overlap_ratio': ratio,
+            'overlapped': bool(ratio > 0.5), 'steps': n}
+
+
+def grad_bucket(params, extra_numel: int = 0):
+    """One persistent flat gradient buffer for ``params`` (+ ``extra_numel`` floats behind them) and {param: its view of it}."""
+    flat = torch.empty(sum(p.numel() for p in params) + extra_numel, device=params[0].device)
+    views, off = {}, 0
+    for p in params:
+        views[p] = flat[off:off + p.numel()].view_as(p)
+        off += p.numel()
+    return flat, views
+
+
+def check_static_layout_fits(bufs):
+    """After warm-up steps on the static layout (synchronised): no sampler pass overflowed a buffer."""
+    for b in bufs:
+        err = int(b.read_meta().error)
+        if err:
+            raise _lib.KgwasHipError(f'static layout does not fit the sampler buffers (error mask {err})')
 
 
 class BatchCache:
@@ -139,8 +230,8 @@ class BatchCache:
 
 class GraphTrainStep:
     def __init__(self, run, input_nodes, batch_size: int, lr: float = 1e-4, weight_decay: float = 5e-4,
-                 margin: float = 1.03, capture_optimizer: bool = True, overlap_sampling: bool = None,
-                 shard_gene_layer: bool = None, cache_batches: bool = False, num_neighbors=None, sample_seed: int = 0):
+                 margin: float = 1.03, shard_gene_layer: bool = None, cache_batches: bool = False, num_neighbors=None,
+                 sample_seed: int = 0):
         """``num_neighbors`` (None = the reference's [-1] * L): PyG's list form of per-hop fan-outs.  With a finite fan-out the
         batches are redrawn every epoch from (``sample_seed``, epoch, batch index) -- ``set_epoch`` names the epoch, a step past
         the last batch moves on to the next one by itself -- the capacities of the static layout are bounds that hold for every
@@ -167,11 +258,10 @@ class GraphTrainStep:
         self.dg = probe.dg.with_static_caps(self.caps)
         self.seed_type = probe.seed_type
         self.ids = probe.ids
-        # two batch buffers: while the graph trains on one, its side branch samples the NEXT batch into the other
+        # two batch buffers: while the step's graph trains on one, the sampler's graph fills the other with the NEXT batch
         self.bufs = [BatchBuffers(self.dg, SIDE_SAMPLER_GRID), BatchBuffers(self.dg, SIDE_SAMPLER_GRID)]
-        self.buf = self.bufs[0]
         self.meta = self.dg.static_meta()
-        self.seeds = torch.zeros(self.batch_size, dtype=torch.int64, device=dev)        # seeds sampled by the side branch
+        self.seeds = torch.zeros(self.batch_size, dtype=torch.int64, device=dev)        # seeds the sampler's graph reads
         # finite fan-out: the 64-bit sample seed the (captured) sampler reads, fed like ``seeds``; the words of an epoch's batches
         self.sample_word = torch.zeros(1, dtype=torch.int64, device=dev) if self.fanout is not None else None
         self._epoch_words = {}
@@ -179,7 +269,6 @@ class GraphTrainStep:
         self.dropout = float(getattr(self.model, 'gat_dropout', 0.0)) > 0.0
         self._drop_words = {}
         self.ld_w = run._ld_weight_vector()             # ([N] or, per-trait weights, [N, T]: resident, read in place by the graph)
-        self.capture_optimizer = capture_optimizer
         self.world = 1
         try:
             import torch.distributed as dist
@@ -190,19 +279,17 @@ class GraphTrainStep:
         # (KGW_FORCE_MULTIRANK_PATH=1: a single rank takes the multi-rank path -- split backward, RCCL all-reduce of one rank on
         # the side stream, eager Adam -- so that a 1-GPU box exercises exactly what an 8-GPU node runs)
         self._multi = self.world > 1 or (os.environ.get('KGW_FORCE_MULTIRANK_PATH') == '1' and torch.distributed.is_initialized())
-        if self._multi:
-            self.capture_optimizer = False       # gradients are all-reduced between backward and Adam
         # multi-rank: the backward pass is captured in TWO graphs, cut at the feature MLPs' outputs.  The gradients of the
         # first half (every relation pack, the read-out, the folded FC_output: ~3.9 MB) are all-reduced on a side stream
         # while the second half (the MLPs' backward: ~45 % of the backward's time, incl. the 5120-wide gene dW product)
-        # runs; only the MLPs' own bucket (~2.7 MB) is reduced in the open.
+        # runs; only the MLPs' own bucket (~2.7 MB) is reduced in the open.  Adam follows the all-reduces, outside the graphs.
+        self.split_backward = self._multi
+        self.capture_optimizer = not self._multi
         # single GPU, optimiser inside the graph: the partial-sum folds of the weight gradients, Adam and the statistics as one launch
-        self.fused_adam = (ops._FUSED_ADAM and self.capture_optimizer and not self._multi and
+        self.fused_adam = (ops._FUSED_ADAM and not self._multi and
                            sum(1 for p in self.model.parameters() if p.requires_grad) <= _lib.ADAM_FUSED_MAX)
         self.deferred_gradients = 0
-        self.finish_fused = False          # (set below: multi-rank split backward)
         self._images, self._image_params, self._image_version, self._pack_probe = {}, [], {}, None
-        self.split_backward = self._multi
         self.finish_fused = ops._FUSED_ADAM and self.split_backward
         self.duv_pieces = ops._DUV_PIECES and self.fused_adam           # (single GPU, whole backward in one autograd pass)
         # multi-rank, optional: the first gene Linear over the resident feature matrix (forward + weight gradient: 0.27 of the
@@ -232,24 +319,18 @@ class GraphTrainStep:
         self.stats = torch.zeros(L + 2, dtype=torch.int64, device=dev)
         self.loss = [None, None]
         self._unit = ops.unit_gradient(dev)
-        self._flat = None                         # multi-rank: gradient bucket + {param: view}
-        self._flat_grads = None
+        self._flat_grads = {}                     # multi-rank: {param: its view of a gradient bucket}
         self.graphs = [None, None]
-        if overlap_sampling is None:
-            overlap_sampling = '2'
-        # '2' (default): the next batch is sampled by a graph of its own, replayed on a side stream while the step's
-        # graph runs (the sampler is ~50 short dependent launches: they hide under the step's GEMMs; measured 2.21 vs
-        # 2.31 ms/step); '0' / False: at the tail of the step's graph; '1' / True: on a forked branch of the same graph
-        # (no gain: 2.31)
-        self.overlap = overlap_sampling in (True, '1', 1)
-        self.twin = overlap_sampling in ('2', 2)
+        # the next batch is sampled by a graph of its own, replayed on a side stream while the step's graph runs (the sampler is
+        # ~50 short dependent launches: they hide under the step's GEMMs; measured 2.21 ms/step against 2.31 with the sampler at
+        # the tail of the step's graph, and 2.31 on a forked branch of it)
         self.sample_graphs = [None, None]
-        self._sampled = [torch.cuda.Event(), torch.cuda.Event()]
-        self._side = side_stream(dev)
-        self._have = [-1, -1]                      # batch index currently sampled into each buffer
+        # (an ordinary stream: a CU-masked one, stream priorities and a timed offset at the head of the sampler's graph were
+        #  measured and dropped, profiles/r4/r4_sampler_interference_experiments.txt)
+        self._side = torch.cuda.Stream(device=dev)
+        self._sampler = SideSampler(self._side)
         # (timing experiments only: train on stale batches to see what the concurrent sampler costs the step)
         self._skip_resample = False
-        self._twin_pending = [False, False]        # the side stream holds an unfinished sample of this buffer
         # ``cache_batches`` (KGWAS.train with more than one epoch; off for a bench line -- the headline samples live): the batches of
         # the first pass over the loader are kept and put back in later passes instead of being sampled again (BatchCache)
         self.cache = None
@@ -266,12 +347,12 @@ class GraphTrainStep:
         else:
             self._capture()
 
-    # train on the batch held by bufs[cur]; concurrently sample ``self.seeds`` into bufs[1 - cur]
+    # train on the batch held by bufs[cur]: the whole step on a single rank, up to the cut of the backward on several
     def _step_body(self, cur: int):
         # (the shard is active for the forward passes THIS trainer issues and for nothing else in the process; so are the operand
         #  images its optimiser launch keeps current)
         with ops.gene_shard_scope(self.gene_shard, self._probe), ops.packed_scope(self._images, self._pack_probe):
-            return self._step_body_inner(cur)
+            return self._step_body_a(cur) if self.split_backward else self._step_body_single(cur)
 
     # ---- operand images of packed weights (the first gene Linear on kgw_gemm3) ---------------------------------------------------
     # With the fused optimiser launch the image of the UPDATED weight is written by that launch, so the next step's forward does not
@@ -296,82 +377,61 @@ class GraphTrainStep:
                 ops.gemm3_pack(p.detach(), p.shape[1], False, out=self._images[p.data_ptr()])
                 self._image_version[p] = p._version
 
-    def _step_body_inner(self, cur: int):
-        bs = self.batch_size
-        main = torch.cuda.current_stream()
-        if self.overlap:
-            self._side.wait_stream(main)                               # fork
-            with torch.cuda.stream(self._side):
-                self._sample(1 - cur)
-        buf = self.bufs[cur]
-        batch = SampledBatch(self.dg, buf, self.meta, self.input_type, bs, static=True)
+    def _batch(self, cur: int):
+        return SampledBatch(self.dg, self.bufs[cur], self.meta, self.input_type, self.batch_size, static=True)
+
+    def _stats_tick(self, cur: int, step_dev):
+        """The batch's edge counts and error bits into the running totals; ``step_dev``: the optimiser's counter to advance too."""
+        _lib.check(_lib.lib().kgw_accumulate_stats_tick(self.bufs[cur].meta.data_ptr(), self.run.gnn_num_layers, self.dg.n_hops,
+                                                        self.stats.data_ptr(), step_dev, _lib.stream_ptr()), 'kgw_accumulate_stats_tick')
+
+    def _step_body_single(self, cur: int):
+        """Single rank: forward, the whole backward, the optimiser."""
+        bs, batch = self.batch_size, self._batch(cur)
         self.opt.zero_grad(set_to_none=True)
-        if self.split_backward:
-            mlp_out = []
-            with ops.readout_fold_deferred():
-                loss, _ = self.model.forward_loss(batch.x_dict, batch.edge_index_dict, bs, batch.n_id(self.input_type),
-                                                  self.dg.y[self.input_type], self.ld_w, mlp_out=mlp_out, unit_grad=True)
-            hs = [h for h in mlp_out if h.requires_grad]
-            late = self._late_params()
-            early = [p for p in self.model.parameters() if p.requires_grad and id(p) not in late]
-            g = torch.autograd.grad(loss, hs + early, grad_outputs=self._unit, allow_unused=True)
-            live = [(p, gi) for p, gi in zip(early, g[len(hs):]) if gi is not None]
-            if self._flat_a is None:
-                self._flat_a = torch.empty(sum(p.numel() for p, _ in live), device=self.seeds.device)
-                self._flat_grads, off = {}, 0
-                for p, _ in live:
-                    self._flat_grads[p] = self._flat_a[off:off + p.numel()].view_as(p)
-                    off += p.numel()
-            torch.cat([gi.reshape(-1) for _, gi in live], out=self._flat_a)
-            self._cut[cur] = (hs, list(g[:len(hs)]))
-        else:
-            with ops.readout_fold_deferred():                          # (the backward pass below always runs)
-                loss, _ = self.model.forward_loss(batch.x_dict, batch.edge_index_dict, bs, batch.n_id(self.input_type),
-                                                  self.dg.y[self.input_type], self.ld_w, unit_grad=True)      # kgwas.py:137-145
-            # fused optimiser launch: the weight-gradient products that feed only Adam stop after their first launch, their last
-            # sums, the update, the step counter and the running totals are ONE launch (ops.GradSink, kgw_adam_fused)
-            sink = ops.GradSink() if self.fused_adam else None
-            pieces = {} if self.duv_pieces else None                   # (d u_r / d v_r stay eight pieces: their consumers add them)
-            with ops.grad_sink_scope(sink), ops.duv_pieces_scope(pieces):
-                loss.backward(gradient=self._unit)                     # (a resident 1.0: no ones_like fill per step)
-            if pieces:
-                raise ops.GradSinkMismatch(f'{len(pieces)} d u_r / d v_r tensor(s) left in pieces reached no consumer that adds them')
-            if sink is not None:
-                self.deferred_gradients = sum(1 for r in sink.records.values() if r[0] is not None) + 2 * len(sink.products)   # (gradients whose last sums the optimiser launch takes)
-                self.opt.step_fused(sink, buf.meta.data_ptr(), self.run.gnn_num_layers, self.dg.n_hops, self.stats)
-                # (launches of the step that carried its parameter-only forward work as rider blocks: the gene layer's kgw_gemm3)
-                self.riders_taken = getattr(self.model, 'last_riders_taken', 0)
-                self.reduces_ridden = sink.reduces_ridden    # (second launches of product groups that rode in a later launch)
-                self.folds_ridden = sink.folds_ridden
-                self.tail_taken = sink.tail_taken          # (kgw_param_tail: the backward's parameter-only end inside the deferred products' launch)
-                if self.overlap:
-                    main.wait_stream(self._side)                       # join
-                elif not self.twin:
-                    self._sample(1 - cur)
-                return loss
-        ticked = False
-        if self.capture_optimizer:
-            self.opt.step(tick=False)                                  # (the counter advances in the statistics launch below)
-            ticked = True
-        elif self.split_backward:
-            pass                                                       # (second half: _step_body_b)
-        elif self._multi:
-            # gradients of all live tensors into ONE persistent bucket (the all-reduce and Adam run on it after the replay)
-            live = [p for p in self.model.parameters() if p.grad is not None]
-            if self._flat is None:
-                self._flat = torch.empty(sum(p.numel() for p in live), device=self.seeds.device)
-                self._flat_grads, off = {}, 0
-                for p in live:
-                    self._flat_grads[p] = self._flat[off:off + p.numel()].view_as(p)
-                    off += p.numel()
-            torch.cat([p.grad.reshape(-1) for p in live], out=self._flat)
-        _lib.check(_lib.lib().kgw_accumulate_stats_tick(buf.meta.data_ptr(), self.run.gnn_num_layers, self.dg.n_hops,
-                                                        self.stats.data_ptr(), self.opt.step_dev.data_ptr() if ticked else None,
-                                                        _lib.stream_ptr()), 'kgw_accumulate_stats_tick')
-        if self.overlap:
-            main.wait_stream(self._side)                               # join
-        elif not self.twin:
-            self._sample(1 - cur)
+        with ops.readout_fold_deferred():                          # (the backward pass below always runs)
+            loss, _ = self.model.forward_loss(batch.x_dict, batch.edge_index_dict, bs, batch.n_id(self.input_type),
+                                              self.dg.y[self.input_type], self.ld_w, unit_grad=True)      # kgwas.py:137-145
+        # fused optimiser launch: the weight-gradient products that feed only Adam stop after their first launch, their last
+        # sums, the update, the step counter and the running totals are ONE launch (ops.GradSink, kgw_adam_fused)
+        sink = ops.GradSink() if self.fused_adam else None
+        pieces = {} if self.duv_pieces else None                   # (d u_r / d v_r stay eight pieces: their consumers add them)
+        with ops.grad_sink_scope(sink), ops.duv_pieces_scope(pieces):
+            loss.backward(gradient=self._unit)                     # (a resident 1.0: no ones_like fill per step)
+        if pieces:
+            raise ops.GradSinkMismatch(f'{len(pieces)} d u_r / d v_r tensor(s) left in pieces reached no consumer that adds them')
+        if sink is None:
+            self.opt.step(tick=False)                              # (the counter advances in the statistics launch)
+            self._stats_tick(cur, self.opt.step_dev.data_ptr())
+            return loss
+        self.deferred_gradients = sum(1 for r in sink.records.values() if r[0] is not None) + 2 * len(sink.products)   # (gradients whose last sums the optimiser launch takes)
+        self.opt.step_fused(sink, self.bufs[cur].meta.data_ptr(), self.run.gnn_num_layers, self.dg.n_hops, self.stats)
+        # (launches of the step that carried its parameter-only forward work as rider blocks: the gene layer's kgw_gemm3)
+        self.riders_taken = getattr(self.model, 'last_riders_taken', 0)
+        self.reduces_ridden = sink.reduces_ridden    # (second launches of product groups that rode in a later launch)
+        self.folds_ridden = sink.folds_ridden
+        self.tail_taken = sink.tail_taken          # (kgw_param_tail: the backward's parameter-only end inside the deferred products' launch)
+        return loss
+
+    def _step_body_a(self, cur: int):
+        """Several ranks, first half: forward and the backward down to the feature MLPs' outputs; its gradients into their bucket."""
+        bs, batch = self.batch_size, self._batch(cur)
+        self.opt.zero_grad(set_to_none=True)
+        mlp_out = []
+        with ops.readout_fold_deferred():
+            loss, _ = self.model.forward_loss(batch.x_dict, batch.edge_index_dict, bs, batch.n_id(self.input_type),
+                                              self.dg.y[self.input_type], self.ld_w, mlp_out=mlp_out, unit_grad=True)
+        hs = [h for h in mlp_out if h.requires_grad]
+        late = self._late_params()
+        early = [p for p in self.model.parameters() if p.requires_grad and id(p) not in late]
+        g = torch.autograd.grad(loss, hs + early, grad_outputs=self._unit, allow_unused=True)
+        live = [(p, gi) for p, gi in zip(early, g[len(hs):]) if gi is not None]
+        if self._flat_a is None:
+            self._flat_a, views = grad_bucket([p for p, _ in live])
+            self._flat_grads.update(views)
+        torch.cat([gi.reshape(-1) for _, gi in live], out=self._flat_a)
+        self._cut[cur] = (hs, list(g[:len(hs)]))
+        self._stats_tick(cur, None)                                # (Adam runs after the all-reduces and advances its counter itself)
         return loss
 
     def _late_params(self):
@@ -403,13 +463,10 @@ class GraphTrainStep:
         w1 = gs.last[1] if staged else None            # (its gradient is NOT produced by the backward: the partial product after the
         n_live = sum(p.numel() for p in live)          #  reduce-scatter writes it straight into the bucket, _stage_dw)
         if self._flat_b is None:
-            self._flat_b = torch.empty(n_live + (w1.numel() if staged else 0), device=self.seeds.device)
-            off = 0
-            for p in live:
-                self._flat_grads[p] = self._flat_b[off:off + p.numel()].view_as(p)
-                off += p.numel()
+            self._flat_b, views = grad_bucket(live, w1.numel() if staged else 0)
+            self._flat_grads.update(views)
             if staged:
-                self._flat_grads[w1] = self._flat_b[off:off + w1.numel()].view_as(w1)
+                self._flat_grads[w1] = self._flat_b[n_live:].view_as(w1)
         if sink is not None:
             self.deferred_gradients = sum(1 for r in sink.records.values() if r[0] is not None) + 2 * len(sink.products)
             self.opt.finish_into(sink, [(p, self._flat_grads[p]) for p in live])
@@ -465,7 +522,6 @@ class GraphTrainStep:
             self.sample_word.copy_(self._epoch_words[epoch][i:i + 1])
 
     def _sample_now(self, which: int, i: int):
-        b = self.batch_size
         if self.cache is not None:
             torch.cuda.current_stream().wait_stream(self._side)    # (the cache's slot index is shared with the side stream's launches)
         if self.cache is not None and self.cache.filled[i]:
@@ -475,12 +531,11 @@ class GraphTrainStep:
             self._sample(which)
             if self.cache is not None:
                 self.cache.save(which, i)
-        self._have[which] = self._key(i, self.epoch)
+        self._sampler.holds[which] = self._key(i, self.epoch)
 
     def _capture(self):
         # warm-up on a side stream (allocator pools, one-time kernel attributes, Adam state), then undo its effect
-        params = [p for p in self.model.parameters()]
-        snap = [p.detach().clone() for p in params]
+        restore = keep_training_state(self.model, self.opt, self.stats)
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s):
@@ -520,30 +575,18 @@ class GraphTrainStep:
                 if gs is not None:
                     gs.scatter()
                     gs.weight_grad_partial(gs.last[0], out=self._flat_grads[gs.last[1]])
-                if self.twin:
-                    self._sample_now(1 - k % 2, 0)
+                self._sample_now(1 - k % 2, 0)
         torch.cuda.current_stream().wait_stream(s)
         torch.cuda.synchronize()
-        for b in self.bufs:
-            err = int(b.read_meta().error)
-            if err:
-                raise _lib.KgwasHipError(f'static layout does not fit the sampler buffers (error mask {err})')
+        check_static_layout_fits(self.bufs)
         if self.world > 1:
             # the gradient buckets hold the parameters that received a gradient in the warm-up steps: the same set on every rank
             # unless a node type is missing from one rank's batches -- agree before the first collective is sized by it
             from . import dist as kdist
-            for name, b in (('first', self._flat_a), ('second', self._flat_b), ('whole', self._flat)):
+            for name, b in (('first', self._flat_a), ('second', self._flat_b)):
                 kdist.check_same_on_all_ranks(0 if b is None else b.numel(), f'size of the {name} gradient bucket')
-        with torch.no_grad():
-            for p, q in zip(params, snap):
-                p.copy_(q)
-            for st in self.opt.state.values():
-                for v in st.values():
-                    if torch.is_tensor(v):
-                        v.zero_()
-            self.opt.step_dev.zero_()
+        restore()
         self._refresh_images(force=True)                       # (the warm-up's updates are undone: so are their images)
-        self.stats.zero_()
         self.opt.zero_grad(set_to_none=True)
         for cur in (0, 1):
             g = torch.cuda.CUDAGraph()
@@ -563,163 +606,113 @@ class GraphTrainStep:
                         gs.forward_partial(*gs.last)
                     with torch.cuda.graph(self._g_dw, pool=g.pool()):
                         gs.weight_grad_partial(gs.last[0], out=self._flat_grads[gs.last[1]])
-            if self.twin:
-                gs = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(gs, stream=self._side):
-                    self._sample(cur)
-                self.sample_graphs[cur] = gs
-        self._have = [-1, -1]
-        if self._want_cache and self.twin:
+            gs = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(gs, stream=self._side):
+                self._sample(cur)
+            self.sample_graphs[cur] = gs
+        self._sampler.forget()
+        if self._want_cache:
             try:
                 self.cache = BatchCache(self.dg, self.bufs, self.n_batches)
             except (MemoryError, ValueError) as e:
                 print(f'kgwas_amd: sampled batches are not kept for later epochs ({e})', file=sys.stderr)
 
+    def _prefetch(self, which: int, i: int, epoch: int):
+        """Batch i of ``epoch`` into bufs[which], on the current (the side) stream."""
+        cache = self.cache if not self._skip_resample else None
+        if cache is not None and cache.filled[i]:
+            cache.restore(which, i)                             # (a later epoch: one copy launch instead of the sampler's ~25)
+        else:
+            self._feed(i, epoch)
+            if not self._skip_resample:
+                self.sample_graphs[which].replay()
+                if cache is not None:
+                    cache.save(which, i)
+
     def step(self, i: int):
         """Train on batch ``i`` of the loader's fixed order (and pre-sample batch i+1); returns the (device,
         float64) loss tensor."""
-        cur = i % 2
+        cur, sam = i % 2, self._sampler
         if self._image_params:
             self._refresh_images()               # (a weight changed by anything but this trainer's own optimiser launch: re-pack)
-        if self._have[cur] != self._key(i, self.epoch):      # first call / non-sequential access: sample it now
+        if sam.holds[cur] != self._key(i, self.epoch):       # first call / non-sequential access: sample it now
+            sam.wait(cur)                        # (behind a prefetch nobody used: it writes this buffer and reads ``seeds``)
             self._sample_now(cur, i)
         nxt = (i + 1) % self.n_batches
         nxt_epoch = self.epoch + (1 if nxt == 0 else 0)      # (finite fan-out: the batch after the last one belongs to the next epoch)
-        b = self.batch_size
         if self.gene_shard is not None:
             self._g_partial.replay()               # this rank's rows of the first gene layer, then everybody's
             self.gene_shard.gather()
-        if self.twin:
-            main = torch.cuda.current_stream()
-            # (round 6, measured: the step's graph handed to its queue BEFORE the sampler's changes nothing -- 0.9825 / 0.9812 against
-            #  0.9794 / 0.9806 ms)
-            self._side.wait_stream(main)          # the previous step (reader of bufs[1 - cur], writer of nothing here) is done
-            with torch.cuda.stream(self._side):
-                cache = self.cache if not self._skip_resample else None
-                if cache is not None and cache.filled[nxt]:
-                    cache.restore(1 - cur, nxt)                     # (a later epoch: one copy launch instead of the sampler's ~25)
-                else:
-                    self._feed(nxt, nxt_epoch)
-                    if not self._skip_resample:
-                        self.sample_graphs[1 - cur].replay()
-                        if cache is not None:
-                            cache.save(1 - cur, nxt)
-                self._sampled[1 - cur].record(self._side)
-            if self._twin_pending[cur]:
-                main.wait_event(self._sampled[cur])
-            if self.dropout:
-                self._feed_dropout(i, self.epoch)
-            self.graphs[cur].replay()
-            self._twin_pending[1 - cur] = True
-            self._twin_pending[cur] = False
-        else:
-            self._feed(nxt, nxt_epoch)
-            if self.dropout:
-                self._feed_dropout(i, self.epoch)
-            self.graphs[cur].replay()
-        self._have[1 - cur] = self._key(nxt, nxt_epoch)
-        self._have[cur] = -1
+        # (round 6, measured: the step's graph handed to its queue BEFORE the sampler's changes nothing -- 0.9825 / 0.9812 against
+        #  0.9794 / 0.9806 ms)
+        sam.prefetch(1 - cur, self._key(nxt, nxt_epoch), lambda: self._prefetch(1 - cur, nxt, nxt_epoch))
+        sam.wait(cur)
+        if self.dropout:
+            self._feed_dropout(i, self.epoch)
+        self.graphs[cur].replay()
+        sam.holds[cur] = -1
         if (self.fanout is not None or self.dropout) and nxt == 0:
             self.epoch = nxt_epoch               # (a pass is over: the next one draws anew unless set_epoch says otherwise)
-        if not self.capture_optimizer:
-            if self.split_backward:
-                from . import dist as kdist
-                main = torch.cuda.current_stream()
-                self._ev_a.record(main)
-                with torch.cuda.stream(self._comm):                   # first bucket: reduced while the MLPs' backward runs
-                    self._comm.wait_event(self._ev_a)
-                    kdist.allreduce_flat(self._flat_a, self.world, 'gradients of the relation packs + read-out, under the MLPs\' backward')
-                    self._ev_ca.record(self._comm)
-                self.graphs_b[cur].replay()
-                if self.gene_shard is not None:
-                    self.gene_shard.scatter()      # dz summed over the ranks' batches, each rank its own gene rows
-                    self._g_dw.replay()            # partial weight gradient of the first gene layer -> its slot of the bucket
-                kdist.allreduce_flat(self._flat_b, self.world, 'gradients of the feature MLPs')        # second bucket: the MLPs' own gradients
-                main.wait_event(self._ev_ca)
-                self.opt.step(self._flat_grads)
-            elif self._multi:
-                from . import dist as kdist
-                kdist.allreduce_flat(self._flat, self.world)          # one RCCL collective over the bucket
-                self.opt.step(self._flat_grads)
-            else:
-                self.opt.step()
+        if self.split_backward:
+            from . import dist as kdist
+            main = torch.cuda.current_stream()
+            self._ev_a.record(main)
+            with torch.cuda.stream(self._comm):                   # first bucket: reduced while the MLPs' backward runs
+                self._comm.wait_event(self._ev_a)
+                kdist.allreduce_flat(self._flat_a, self.world, 'gradients of the relation packs + read-out, under the MLPs\' backward')
+                self._ev_ca.record(self._comm)
+            self.graphs_b[cur].replay()
+            if self.gene_shard is not None:
+                self.gene_shard.scatter()      # dz summed over the ranks' batches, each rank its own gene rows
+                self._g_dw.replay()            # partial weight gradient of the first gene layer -> its slot of the bucket
+            kdist.allreduce_flat(self._flat_b, self.world, 'gradients of the feature MLPs')        # second bucket: the MLPs' own gradients
+            main.wait_event(self._ev_ca)
+            self.opt.step(self._flat_grads)
         return self.loss[cur]
 
     def measure_overlap(self, n: int = 20) -> dict:
         """Did the next batch's sampler really run BESIDE the step?  HIP maps streams onto a few hardware queues and a replayed
         graph runs on the queue of the stream it was captured on: two streams that share a queue serialise whatever the program
-        says.  Times ``n`` steps with the side sampler, ``n`` without it (stale batches) and ``n`` sampler replays alone; overlap =
-        the share of the sampler's own time that did NOT show up in the step.  Every rank calls it (multi-rank steps contain
-        collectives).  Leaves the buffers unsampled (the next step() samples its batch itself) and the model, the optimiser state
-        and the running totals as it found them."""
-        import time
-        if not self.twin:
-            return {'overlapped': False, 'note': 'the sampler is not run beside the step in this configuration'}
+        says.  Times ``n`` steps with the side sampler, ``n`` without it (stale batches) and ``n`` sampler replays alone
+        (time_sampler_overlap).  Every rank calls it (multi-rank steps contain collectives).  Leaves the buffers unsampled (the
+        next step() samples its batch itself) and the model, the optimiser state and the running totals as it found them."""
         # the measurement runs real training steps (half of them on stale batches): parameters, optimiser state, step counter and
         # the running totals are put back afterwards -- a measurement must not move the trajectory (ADVICE r4)
-        params = [p for p in self.model.parameters()]
-        snap = [p.detach().clone() for p in params]
-        ostate = {p: {k: v.clone() for k, v in st.items() if torch.is_tensor(v)} for p, st in self.opt.state.items()}
-        step0, stats0 = self.opt.step_dev.clone(), self.stats.clone()
-
-        def timed(fn):
-            torch.cuda.synchronize()
-            t = time.perf_counter()
-            for i in range(n):
-                fn(i)
-            torch.cuda.synchronize()
-            return (time.perf_counter() - t) / n * 1e3
-
-        def samp(i):
-            with torch.cuda.stream(self._side):
-                self.sample_graphs[i % 2].replay()
-        k = [0]
+        restore = keep_training_state(self.model, self.opt, self.stats)
+        k, keep = [0], self._skip_resample
 
         def step(_):
             self.step(k[0] % self.n_batches)                  # (consecutive batch indices: no step samples in the open)
             k[0] += 1
-        keep = self._skip_resample
-        for i in range(2):
-            step(i)
-        both = timed(step)
-        self._skip_resample = True
-        step(0)
-        alone = timed(step)
-        self._skip_resample = keep
-        sampler = timed(samp)
+
+        def stale(_):
+            self._skip_resample = True
+            step(_)
+            self._skip_resample = keep
+
+        def samp(i):
+            with torch.cuda.stream(self._side):
+                self.sample_graphs[i % 2].replay()
+        res = time_sampler_overlap(step, stale, samp, n)
         torch.cuda.current_stream().wait_stream(self._side)
         torch.cuda.synchronize()
-        self._have, self._twin_pending = [-1, -1], [False, False]
-        with torch.no_grad():
-            for p, q in zip(params, snap):
-                p.copy_(q)
-            for p, st in self.opt.state.items():
-                for k, v in st.items():
-                    if torch.is_tensor(v):
-                        v.copy_(ostate[p][k]) if p in ostate and k in ostate[p] else v.zero_()
-            self.opt.step_dev.copy_(step0)
-            self.stats.copy_(stats0)
+        self._sampler.forget()
+        restore()
         self._refresh_images(force=True)                        # (the operand images follow the restored weights)
-        ratio = (alone + sampler - both) / max(sampler, 1e-9)
-        return {'step_with_side_sampler_ms': both, 'step_alone_ms': alone, 'sampler_alone_ms': sampler, 'overlap_ratio': ratio,
-                'overlapped': bool(ratio > 0.5), 'steps': n}
+        return res
 
     def describe(self) -> str:
         if self.split_backward:
             return ('HIP graphs: forward + first half of the backward | second half (feature MLPs' +
                     (', its gradients finished and written into their bucket by one launch' if self.finish_fused else '') +
                     '); the first half\'s gradient bucket '
-                    'is all-reduced (RCCL) on a side stream under the second graph, the MLPs\' bucket after it, then one Adam launch' +
-                    ('; next batch sampled by a third graph on a side stream' if self.twin else ''))
+                    'is all-reduced (RCCL) on a side stream under the second graph, the MLPs\' bucket after it, then one Adam launch'
+                    '; next batch sampled by a third graph on a side stream')
         adam = ' + Adam)'
         if self.fused_adam:
             adam = (f' + one optimiser launch that also finishes the partial sums of {self.deferred_gradients} weight gradients' +
                     (', writes the first gene Linear\'s bf16 operand image' if self._image_params else '') + ' and keeps the step counters)')
-        return ('HIP graphs: step graph (fwd + bwd' + (adam if self.capture_optimizer else '), RCCL all-reduce + Adam eager') +
-                (' with the next batch sampled by a second graph on a side stream' if self.twin else ', sampling inside it'))
-
-    def grads_ready(self):
-        return [p.grad for p in self.model.parameters() if p.grad is not None]
+        return 'HIP graphs: step graph (fwd + bwd' + adam + ' with the next batch sampled by a second graph on a side stream'
 
     def poll(self):
         """Non-blocking form of ``check`` for the middle of an epoch: looks at the sticky error bit as it was when the PREVIOUS
@@ -795,7 +788,7 @@ class GraphEvalStep:
         self.graphs = [None, None]
         self.sample_graphs = [None, None]
         self._side = torch.cuda.Stream(device=dev)
-        self._sampled = [torch.cuda.Event(), torch.cuda.Event()]
+        self._sampler = SideSampler(self._side)
         self._capture()
 
     def _forward(self, cur: int):
@@ -827,10 +820,7 @@ class GraphEvalStep:
                 self._forward(k % nb)
         torch.cuda.current_stream().wait_stream(s)
         torch.cuda.synchronize()
-        for b in self.bufs:
-            err = int(b.read_meta().error)
-            if err:
-                raise _lib.KgwasHipError(f'static layout does not fit the sampler buffers (error mask {err})')
+        check_static_layout_fits(self.bufs)
         for cur in range(nb):
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g):
@@ -843,23 +833,19 @@ class GraphEvalStep:
 
     def run(self) -> torch.Tensor:
         """Predictions of every input node, in input order (device tensor [n]; [n, T] for out_channels = T > 1)."""
-        b, main = self.batch_size, torch.cuda.current_stream()
+        b, sam = self.batch_size, self._sampler
         self._sample_now(0, 0)
         err = torch.zeros(1, dtype=torch.int32, device=self.out.device)
         meta_err = [bf.meta.view(torch.int32)[_lib.KgwBatchMeta.error.offset // 4:][:1] for bf in self.bufs]
-        pending = [False, False]
+
+        def fill(which, i):
+            self.seeds.copy_(self.ids[i * b:(i + 1) * b])
+            self.sample_graphs[which].replay()
         for i in range(self.n_batches):
             cur = i % len(self.bufs)
             if i + 1 < self.n_batches:
-                self._side.wait_stream(main)
-                with torch.cuda.stream(self._side):
-                    self.seeds.copy_(self.ids[(i + 1) * b:(i + 2) * b])
-                    self.sample_graphs[1 - cur].replay()
-                    self._sampled[1 - cur].record(self._side)
-                pending[1 - cur] = True
-            if pending[cur]:
-                main.wait_event(self._sampled[cur])
-                pending[cur] = False
+                sam.prefetch(1 - cur, i + 1, lambda: fill(1 - cur, i + 1))
+            sam.wait(cur)
             self.graphs[cur].replay()
             self.out[i * b:(i + 1) * b].copy_(self.pred[cur])
             err |= meta_err[cur]

@@ -510,9 +510,8 @@ class ShardedTrainer:
         self.dg = self.dg_eager.with_static_caps(caps)
         # two batch buffers: while the step computes on one, the NEXT batch is sampled into the other on a side stream (its
         # frontier merge is a collective of that stream's segment list)
-        self.overlap = True
-        from .graph_step import SIDE_SAMPLER_GRID               # (a sampler beside a step keeps its launches small)
-        grid = SIDE_SAMPLER_GRID if self.overlap else 0
+        from .graph_step import SIDE_SAMPLER_GRID, SideSampler, check_static_layout_fits, keep_training_state
+        grid = SIDE_SAMPLER_GRID                                # (a sampler beside a step keeps its launches small)
         self.bufs = [BatchBuffers(self.dg, grid), BatchBuffers(self.dg, grid)]
         self.buf = self.bufs[0]
         self.seeds2 = [self.seeds_dev, torch.zeros_like(self.seeds_dev)]
@@ -522,13 +521,10 @@ class ShardedTrainer:
         self.loss_dev = [None, None]
         # (the stream the step's graphs are captured on, and the one the sampler's are captured on AND replayed on)
         self._cap_stream, self._side = _streams_on_own_queues(dev, self.xchg.group, self.xchg.multi)
-        self._sampled = [torch.cuda.Event(), torch.cuda.Event()]
-        self._pending = [False, False]
-        self._have = [-1, -1]
+        self._sampler = SideSampler(self._side)
         self.stats = torch.zeros(L + 2, dtype=torch.int64, device=dev)
         # (3) warm-up, eager + staged
-        params = [p for p in self.model.parameters()]
-        snap = [p.detach().clone() for p in params]
+        restore = keep_training_state(self.model, self.opt, self.stats)
         self._skip_resample = False                                 # (measure_overlap: the step without a sampler beside it)
         for k in range(3):
             self.xchg.emu_batch = 0
@@ -544,18 +540,8 @@ class ShardedTrainer:
                 else:
                     gs.inline = False
         torch.cuda.synchronize()
-        for b in self.bufs:
-            if int(b.read_meta().error):
-                raise _lib.KgwasHipError('static layout of the sharded step does not fit its buffers')
-        with torch.no_grad():
-            for p, q in zip(params, snap):
-                p.copy_(q)
-            for st in self.opt.state.values():
-                for v in st.values():
-                    if torch.is_tensor(v):
-                        v.zero_()
-            self.opt.step_dev.zero_()
-        self.stats.zero_()
+        check_static_layout_fits(self.bufs)
+        restore()
         # (4) capture
         self.samp_seg, self.comp_seg = [], []
         torch.cuda.synchronize()
@@ -579,6 +565,12 @@ class ShardedTrainer:
         """Sampling of the seeds in ``seeds2[b]`` into ``bufs[b]`` (static layout; the frontier merge goes through
         ShardExchange._collective like every collective: run now, or a cut between two graph segments while capturing)."""
         sample_sharded(self.dg, self.bufs[b], self.seeds2[b], self.seed_type, self.xchg, record=False)
+
+    def _sample_replay(self, b: int, i: int):
+        """Batch ``i`` into ``bufs[b]`` on the current stream: its seeds in, the sampler's captured segments replayed."""
+        self.seeds2[b].copy_(self.seed_table[i])
+        self.xchg.emu_batch = i
+        self.samp_seg[b].replay()
 
     def _compute_body(self, b: int):
         """One training step on the batch held by ``bufs[b]``: static layout, staged exchange."""
@@ -628,39 +620,27 @@ class ShardedTrainer:
         it was captured on: two streams mapped to one queue serialise whatever the program says.)  Times ``n`` steps with the side
         sampler, ``n`` without it (stale batches) and ``n`` sampler replays alone; overlap = the share of the sampler's own time
         that did NOT show up in the step.  Every rank calls it (the steps contain collectives).  Leaves the buffers unsampled."""
-        import time
-        if not (self.use_graph and self.overlap):
+        from .graph_step import time_sampler_overlap
+        if not self.use_graph:
             return {'overlapped': False, 'note': 'the sampler is not run beside the step in this configuration'}
-
-        def timed(fn):
-            torch.cuda.synchronize()
-            t = time.perf_counter()
-            for i in range(n):
-                fn(i)
-            torch.cuda.synchronize()
-            return (time.perf_counter() - t) / n * 1e3
-
-        def samp(i):
-            with torch.cuda.stream(self._side):
-                self.xchg.emu_batch = i % self.n_batches
-                self.samp_seg[i % 2].replay()
         k = [0]
 
         def step(_):
             self.step(k[0])                                    # (consecutive batch indices: no step samples in the open)
             k[0] += 1
-        for i in range(2):
-            step(i)
-        both = timed(step)
-        self._skip_resample = True
-        step(0)
-        alone = timed(step)
-        self._skip_resample = False
-        sampler = timed(samp)
-        self._have, self._pending = [-1, -1], [False, False]
-        ratio = (alone + sampler - both) / max(sampler, 1e-9)
-        return {'step_with_side_sampler_ms': both, 'step_alone_ms': alone, 'sampler_alone_ms': sampler, 'overlap_ratio': ratio,
-                'overlapped': bool(ratio > 0.5), 'steps': n}
+
+        def stale(_):
+            self._skip_resample = True
+            step(_)
+            self._skip_resample = False
+
+        def samp(i):
+            with torch.cuda.stream(self._side):
+                self.xchg.emu_batch = i % self.n_batches
+                self.samp_seg[i % 2].replay()
+        res = time_sampler_overlap(step, stale, samp, n)
+        self._sampler.forget()
+        return res
 
     def describe(self) -> str:
         return (('HIP-graph segments with the collectives between them' if self.use_graph else 'eager launches') + '; per step: 1 frontier all-reduce(MIN), 1 all-gather of partial softmax states + 1 all-reduce of '
@@ -768,31 +748,20 @@ class ShardedTrainer:
 
     def step(self, i: int):
         if self.use_graph:
-            cur, nb = i % 2, self.n_batches
-            main = torch.cuda.current_stream()
-            if self._have[cur] != i % nb:                          # first call / non-sequential access: sample it now
-                self.seeds2[cur].copy_(self.seed_table[i % nb])
-                self.xchg.emu_batch = i % nb
-                self.samp_seg[cur].replay()
-                self._have[cur], self._pending[cur] = i % nb, False
+            cur, nxt, sam = i % 2, (i + 1) % self.n_batches, self._sampler
+            if sam.holds[cur] != i % self.n_batches:               # first call / non-sequential access: sample it now
+                sam.wait(cur)                                      # (behind a prefetch nobody used: it writes this buffer)
+                self._sample_replay(cur, i % self.n_batches)
+                sam.holds[cur] = i % self.n_batches
             if self._skip_resample:
-                self._have[1 - cur] = (i + 1) % nb                 # (timing only: the next step trains on a stale batch)
-            elif self.overlap:
+                sam.holds[1 - cur] = nxt                           # (timing only: the next step trains on a stale batch)
+            else:
                 # the NEXT batch, on the side stream beside this step (the previous step, reader of that buffer, is enqueued
                 # on the main stream already).  Its frontier all-reduce is issued before this step's collectives on every rank.
-                nxt = (i + 1) % nb
-                self._side.wait_stream(main)
-                with torch.cuda.stream(self._side):
-                    self.seeds2[1 - cur].copy_(self.seed_table[nxt])
-                    self.xchg.emu_batch = nxt
-                    self.samp_seg[1 - cur].replay()
-                    self._sampled[1 - cur].record(self._side)
-                self._have[1 - cur], self._pending[1 - cur] = nxt, True
-            if self._pending[cur]:
-                main.wait_event(self._sampled[cur])
-                self._pending[cur] = False
+                sam.prefetch(1 - cur, nxt, lambda: self._sample_replay(1 - cur, nxt))
+            sam.wait(cur)
             self.comp_seg[cur].replay()
-            self._have[cur] = -1
+            sam.holds[cur] = -1
             self.last_loss = self.loss_dev[cur]
             return None
         batch, part, _ = self.forward_backward(i)

@@ -231,3 +231,31 @@ def test_measure_overlap_leaves_the_training_state_alone(small_kg):
     for n in outs[0][0]:
         assert torch.equal(outs[0][0][n], outs[1][0][n]), n
     assert outs[0][1] == outs[1][1]
+
+
+def test_steps_out_of_order_return_the_loss_of_the_batch_they_name(small_kg):
+    """The two-buffer bookkeeping of the side sampler under non-sequential ``step(i)``.  lr = 0: the parameters stand still, so
+    the loss of step(i) is a function of batch i alone.  A trainer that goes through [0, 1, 2, 5, 3, 3, 0, 1] -- a prefetched
+    batch that is used (1, 2), one that is thrown away (3, when 5 is asked for), the same index again (the buffer was given up
+    after its step), the wrap to 0 -- returns for every index, bit for bit, what a trainer going 0 .. 5 in order returns."""
+    from kgwas_amd.graph_step import GraphTrainStep
+    from kgwas_amd.kgwas import KGWAS
+    bs, nb = 64, 6
+    ids = np.asarray(small_kg.train_input_nodes[1][:bs * nb])
+
+    def trainer():
+        run = KGWAS(small_kg, device='cuda:0', seed=41)
+        run.initialize_model()
+        gs = GraphTrainStep(run, ('SNP', ids), bs, lr=0.0, weight_decay=0.0)
+        assert gs.n_batches == nb
+        run.model.train()
+        return gs
+    gs = trainer()
+    ordered = [gs.step(i).detach().clone() for i in range(nb)]
+    gs.check()
+    assert all(l.dtype == torch.float64 and float(l) > 0 for l in ordered)
+    assert len({float(l) for l in ordered}) == nb              # (distinct batches, distinct losses: a stale buffer would show)
+    gs = trainer()
+    for i in [0, 1, 2, 5, 3, 3, 0, 1]:
+        assert torch.equal(gs.step(i).detach().clone(), ordered[i]), f'step({i})'
+    gs.check()

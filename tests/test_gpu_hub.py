@@ -285,7 +285,8 @@ def test_captured_training_steps_at_full_size_track_the_oracle(full_c1):
     bs, n_steps, lr, wd = 512, 8, 1e-4, 5e-4                 # the reference's training configuration (kgwas/kgwas.py:85-87,116)
     ids = np.asarray(run.data.train_input_nodes[1])[:(n_steps + 1) * bs]
     gs = GraphTrainStep(run, ('SNP', ids), bs, lr=lr, weight_decay=wd)
-    assert gs.fused_adam and gs.twin, 'the shipped single-GPU configuration: fused optimiser launch, side sampler'
+    assert gs.fused_adam and all(isinstance(g, torch.cuda.CUDAGraph) for g in gs.sample_graphs), \
+        'the shipped single-GPU configuration: fused optimiser launch, side sampler'
     oracle = oracle_from_product(model, dtype=torch.float64)
     oracle0 = oracle_from_product(model, dtype=torch.float64)          # (stays at the initial state)
     p0 = params_by_name(model)

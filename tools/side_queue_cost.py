@@ -21,7 +21,7 @@ ids = np.asarray(data.train_input_nodes[1])
 run = KGWAS(data, device='cuda:0', seed=1)
 run.initialize_model()
 gs = GraphTrainStep(run, ('SNP', ids), 512, lr=1e-4, weight_decay=5e-4)
-assert gs.twin and gs.fused_adam
+assert all(isinstance(g, torch.cuda.CUDAGraph) for g in gs.sample_graphs) and gs.fused_adam
 
 
 def timed():
