@@ -153,7 +153,24 @@ typedef struct KgwLayerArgs {
     int32_t n_src_rows;            /* rows of H / dH in the layout (src_base[n_types])         */
     float   neg_slope, inv_temp;   /* LeakyReLU slope (0.2), 1/temperature (1)                 */
     int32_t flags;                 /* KGW_F_RAW_WEIGHTS: forward weights messages by the raw logits   */
-    int32_t pad_;
+    /* Attention heads (this word was padding that callers zeroed: the struct keeps its size and offsets).  0 or 1: one head -- the
+     * kernels, layouts and bits of a call that left it zero.  NH = 2 or 4: NH heads
+     * over the SAME layer input (the aggregate gathers H and the caller applies W_src afterwards, so a head is a pair (u_r^h, v_r^h)
+     * and all heads share the one row gather per edge).  Every head-carrying array is then NH PLANES, head-major, plane h having
+     * exactly the single-head layout:
+     *      U, V, dU, dV      [NH][n_rels][128]
+     *      Z, dZ             [NH][z rows][128]          stat [NH][z rows][2]          da_dst [NH][z rows]
+     *      e_edge            [NH][n_edges]              adp  [NH][n_edges][2]
+     *      part              [NH][n_chunks][132]        part_da [NH][n_chunks][4]     part_du [NH][n_chunks][128]
+     *      duv_ws            [NH][2][n_rels][8][128]    (KGW_F_DUV_PIECES leaves the pieces there, head by head)
+     * with the plane sizes taken from the LAYOUT the caller allocated by: z rows = meta_host->z_base[layer-1][n_types], n_edges =
+     * meta_host->n_edges[layer-1], n_chunks = this struct's n_chunks.  H, dH (summed over the heads), chunks, col_local, t_* and
+     * meta_* are as with one head.  Per head, relation and destination:  e^h_ij = leaky_relu(<x_j, u_r^h> + <x_i, v_r^h>),
+     * alpha^h = softmax_j(e^h / T), Z[h][i, r] = sum_j alpha^h_ij x_j.
+     * Any other value: KGW_E_RANGE.  NH > 1 together with KGW_F_RAW_WEIGHTS, partial_rels, drop_word_dev, logit_bias / rel_sums,
+     * a_dst without V, or da_src (d u_r / d v_r come from the part_du .. dV route only): KGW_E_UNSUPPORTED -- before any launch.
+     * kgw_edge_alpha is single-head (NH > 1: KGW_E_UNSUPPORTED; call it per plane); t_rel / oct_flags are hints and ignored.      */
+    int32_t n_heads;
     const KgwGraph* graph_host;    /* host copy, passed by value to the kernels               */
     const KgwBatchMeta* meta_host; /* host struct holding the LAYOUT (z_base, src_base, t_base, lay_*) */
     const KgwBatchMeta* meta_dev;  /* device struct written by kgw_sample_batch (actual counts)        */

@@ -89,7 +89,7 @@ class KgwBatchBuf(C.Structure):
 class KgwLayerArgs(C.Structure):
     _fields_ = [
         ('layer', C.c_int32), ('n_chunks', C.c_int32), ('n_multi_hops', C.c_int32), ('n_src_rows', C.c_int32),
-        ('neg_slope', C.c_float), ('inv_temp', C.c_float), ('flags', C.c_int32), ('pad_', C.c_int32),
+        ('neg_slope', C.c_float), ('inv_temp', C.c_float), ('flags', C.c_int32), ('n_heads', C.c_int32),
         ('graph_host', C.c_void_p), ('meta_host', C.c_void_p), ('meta_dev', C.c_void_p),
         ('chunks', C.c_void_p), ('multi', C.c_void_p), ('multi_cap', C.c_int64),
         ('col_local', C.c_void_p), ('H', C.c_void_p), ('a_dst', C.c_void_p), ('V', C.c_void_p), ('U', C.c_void_p),
@@ -327,6 +327,15 @@ def lib():
 
 
 KGW_E_UNSUPPORTED = -3
+
+
+def has_heads() -> bool:
+    """Does the loaded library know KgwLayerArgs.n_heads?  (The field took the place of a padding word, so an older library named
+    by KGW_LIB_PATH for an A/B run has the same struct size and would run one head.)  n_heads = 3 is refused by value before
+    anything else is looked at; the older library sees an empty layer and returns 0.  No launch either way."""
+    a = KgwLayerArgs()
+    a.n_heads = 3
+    return lib().kgw_gat_aggregate_fwd(C.byref(a), None) == -2
 
 
 def check(status: int, what: str):

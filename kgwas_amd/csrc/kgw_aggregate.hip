@@ -1144,6 +1144,8 @@ __global__ void __launch_bounds__(KGW_BLK) k_edge_alpha(LayerTab T, AggPtrs P, f
     }
 }
 
+#include "kgw_aggregate_heads.h"      // n_heads = 2, 4: the same mapping with NH planes of every head-carrying array
+
 // ---- host side -----------------------------------------------------------------------------------
 int build_tab(const KgwLayerArgs* a, LayerTab* T) {
     const KgwGraph* G = a->graph_host;
@@ -1243,10 +1245,92 @@ inline int grid_fine(int64_t n_items) {
     return (int)((g + 7) & ~7ll);             // whole rounds over the 8 XCDs: a grid-stride step keeps a block's XCD class
 }
 
+// ---- n_heads (KgwLayerArgs.n_heads) ---------------------------------------------------------------------------------
+// 0 / 1: the single-head kernels above, untouched.  2 / 4: the kernels of kgw_aggregate_heads.h.  Anything else: KGW_E_RANGE.
+int check_heads(const KgwLayerArgs* a) {
+    const int nh = a->n_heads;
+    if (nh < 0 || nh == 3 || nh > 4) return KGW_E_RANGE;
+    if (nh <= 1) return KGW_OK;
+    // what the head kernels do not compute is refused before any launch
+    if ((a->flags & KGW_F_RAW_WEIGHTS) || a->partial_rels || a->drop_word_dev || a->logit_bias || a->rel_sums) return KGW_E_UNSUPPORTED;
+    if (a->a_dst && !a->V) return KGW_E_UNSUPPORTED;       // a_d^h is computed in-kernel from V
+    if (a->da_src) return KGW_E_UNSUPPORTED;               // d u_r^h / d v_r^h come from the rider blocks (part_du .. dV) only
+    return KGW_OK;
+}
+
+int head_dims(const KgwLayerArgs* a, HeadDims* Dm) {
+    const KgwGraph* G = a->graph_host;
+    const KgwBatchMeta* M = a->meta_host;
+    if (!G || !M) return KGW_E_NULL;
+    const int l = a->layer;
+    if (l < 1 || l > G->n_layers || G->n_types > KGW_MAX_TYPES) return KGW_E_RANGE;
+    Dm->z_rows = M->z_base[l - 1][G->n_types];
+    Dm->n_edges = M->n_edges[l - 1];
+    Dm->n_chunks = a->n_chunks;
+    return KGW_OK;
+}
+
+template <int NH>
+int heads_fwd(const KgwLayerArgs* a, const LayerTab& T, const AggPtrs& P, const HeadDims& Dm, hipStream_t st) {
+    if (a->ev_before) KGW_HIP(hipEventRecord((hipEvent_t)a->ev_before, st));
+    k_agg_fwd_heads<NH><<<grid_fine(a->n_chunks), KGW_BLK, 0, st>>>(T, P, Dm, a->neg_slope, a->inv_temp);
+    KGW_LAUNCH_CHECK();
+    if (a->ev_after) KGW_HIP(hipEventRecord((hipEvent_t)a->ev_after, st));
+    if (a->multi && a->multi_cap > 0) {
+        k_agg_fwd_combine_heads<NH><<<grid_for_waves(a->multi_cap < 1024 ? a->multi_cap : 1024), KGW_BLK, 0, st>>>(T, P, Dm, a->n_multi_hops);
+        KGW_LAUNCH_CHECK();
+    }
+    return KGW_OK;
+}
+
+template <int NH>
+int heads_bwd_dst(const KgwLayerArgs* a, const LayerTab& T, const AggPtrs& P, const HeadDims& Dm, hipStream_t st) {
+    if (a->ev_before) KGW_HIP(hipEventRecord((hipEvent_t)a->ev_before, st));
+    // heads per pass: all of them where that compiles without scratch (profiles/multihead/resource_usage.txt)
+    constexpr int HB = KGW_BWD_DST_HEADS_PER_PASS < NH ? KGW_BWD_DST_HEADS_PER_PASS : NH;
+    for (int h0 = 0; h0 < NH; h0 += HB) {
+        k_agg_bwd_dst_heads<NH, HB><<<grid_fine(a->n_chunks), KGW_BLK, 0, st>>>(T, P, Dm, h0, a->neg_slope, a->inv_temp);
+        KGW_LAUNCH_CHECK();
+    }
+    if (a->ev_after) KGW_HIP(hipEventRecord((hipEvent_t)a->ev_after, st));
+    if (a->multi && a->multi_cap > 0) {
+        k_agg_bwd_combine_heads<NH><<<grid_for_waves(a->multi_cap < 1024 ? a->multi_cap : 1024), KGW_BLK, 0, st>>>(T, P, Dm, a->n_multi_hops);
+        KGW_LAUNCH_CHECK();
+    }
+    return KGW_OK;
+}
+
+template <int NH>
+int heads_bwd_src(const KgwLayerArgs* a, const LayerTab& T, const AggPtrs& P, const HeadDims& Dm, hipStream_t st) {
+    if (a->ev_before) KGW_HIP(hipEventRecord((hipEvent_t)a->ev_before, st));
+    const int gmain = grid_fine(a->n_src_rows);
+    const int n_riders = NH * 2 * KGW_DUV_SPLIT * T.n_rels;
+    k_agg_bwd_src_heads<NH><<<gmain + n_riders, KGW_BLK, 0, st>>>(T, P, Dm, a->n_src_rows, gmain, n_riders);
+    KGW_LAUNCH_CHECK();
+    if (a->ev_after) KGW_HIP(hipEventRecord((hipEvent_t)a->ev_after, st));
+    if (!(a->flags & KGW_F_DUV_PIECES)) {
+        k_duv_fold_heads<NH><<<dim3(T.n_rels, 2, NH), KGW_C, 0, st>>>(T.n_rels, a->duv_ws, a->dU, a->dV);
+        KGW_LAUNCH_CHECK();
+    }
+    return KGW_OK;
+}
+
 }  // namespace
 
 extern "C" int kgw_gat_aggregate_fwd(const KgwLayerArgs* a, kgw_stream_t stream_) {
     if (!a) return KGW_E_NULL;
+    if (int rc = check_heads(a)) return rc;
+    if (a->n_heads > 1) {
+        if (a->n_chunks == 0) return KGW_OK;
+        if (!a->chunks || !a->col_local || !a->H || !a->V || !a->U || !a->Z || !a->stat || !a->e_edge || !a->part || !a->meta_dev)
+            return KGW_E_NULL;
+        LayerTab T;
+        HeadDims Dm;
+        if (int rc = build_tab(a, &T)) return rc;
+        if (int rc = head_dims(a, &Dm)) return rc;
+        const AggPtrs P = build_ptrs(a);
+        return a->n_heads == 2 ? heads_fwd<2>(a, T, P, Dm, (hipStream_t)stream_) : heads_fwd<4>(a, T, P, Dm, (hipStream_t)stream_);
+    }
     if (int rc = check_drop(a)) return rc;
     if (a->n_chunks == 0) return KGW_OK;
     if (!a->chunks || !a->col_local || !a->H || (!a->a_dst && !a->V) || !a->U || !a->Z || !a->stat || !a->e_edge || !a->part ||
@@ -1275,6 +1359,19 @@ extern "C" int kgw_gat_aggregate_fwd(const KgwLayerArgs* a, kgw_stream_t stream_
 
 extern "C" int kgw_gat_aggregate_bwd_dst(const KgwLayerArgs* a, kgw_stream_t stream_) {
     if (!a) return KGW_E_NULL;
+    if (int rc = check_heads(a)) return rc;
+    if (a->n_heads > 1) {
+        if (a->n_chunks == 0) return KGW_OK;
+        if (!a->chunks || !a->col_local || !a->H || !a->Z || !a->stat || !a->e_edge || !a->dZ || !a->adp || !a->da_dst ||
+            !a->part_da || !a->part_du || !a->meta_dev)
+            return KGW_E_NULL;
+        LayerTab T;
+        HeadDims Dm;
+        if (int rc = build_tab(a, &T)) return rc;
+        if (int rc = head_dims(a, &Dm)) return rc;
+        const AggPtrs P = build_ptrs(a);
+        return a->n_heads == 2 ? heads_bwd_dst<2>(a, T, P, Dm, (hipStream_t)stream_) : heads_bwd_dst<4>(a, T, P, Dm, (hipStream_t)stream_);
+    }
     if (int rc = check_drop(a)) return rc;
     if (a->n_chunks == 0) return KGW_OK;
     if (!a->chunks || !a->col_local || !a->H || !a->Z || !a->stat || !a->e_edge || !a->dZ || !a->adp ||
@@ -1299,6 +1396,19 @@ extern "C" int kgw_gat_aggregate_bwd_dst(const KgwLayerArgs* a, kgw_stream_t str
 
 extern "C" int kgw_gat_aggregate_bwd_src(const KgwLayerArgs* a, kgw_stream_t stream_) {
     if (!a) return KGW_E_NULL;
+    if (int rc = check_heads(a)) return rc;
+    if (a->n_heads > 1) {
+        if (a->n_src_rows == 0) return KGW_OK;
+        if (!a->dZ || !a->adp || !a->da_dst || !a->t_ptr || !a->t_edge || !a->t_zrow || !a->dH || !a->H || !a->U || !a->V ||
+            !a->part_du || !a->seg_chptr || !a->duv_ws || !a->dU || !a->dV || !a->meta_dev)
+            return KGW_E_NULL;
+        LayerTab T;
+        HeadDims Dm;
+        if (int rc = build_tab(a, &T)) return rc;
+        if (int rc = head_dims(a, &Dm)) return rc;
+        const AggPtrs P = build_ptrs(a);
+        return a->n_heads == 2 ? heads_bwd_src<2>(a, T, P, Dm, (hipStream_t)stream_) : heads_bwd_src<4>(a, T, P, Dm, (hipStream_t)stream_);
+    }
     if (a->n_src_rows == 0) return KGW_OK;
     if (!a->dZ || !a->adp || !a->t_ptr || !a->t_edge || !a->t_zrow || !a->dH || (!a->da_src && !a->dU) || !a->U || !a->meta_dev)
         return KGW_E_NULL;
@@ -1323,6 +1433,8 @@ extern "C" int kgw_gat_aggregate_bwd_src(const KgwLayerArgs* a, kgw_stream_t str
 
 extern "C" int kgw_edge_alpha(const KgwLayerArgs* a, float* alpha_out, kgw_stream_t stream_) {
     if (!a || !alpha_out) return KGW_E_NULL;
+    if (int rc = check_heads(a)) return rc;
+    if (a->n_heads > 1) return KGW_E_UNSUPPORTED;       // (alpha of ONE softmax: call it per head plane with n_heads = 0)
     if (a->n_chunks == 0) return KGW_OK;
     if (!a->chunks || !a->stat || !a->e_edge || !a->meta_dev) return KGW_E_NULL;
     LayerTab T;

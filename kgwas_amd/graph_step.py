@@ -286,7 +286,9 @@ class GraphTrainStep:
         self.split_backward = self._multi
         self.capture_optimizer = not self._multi
         # single GPU, optimiser inside the graph: the partial-sum folds of the weight gradients, Adam and the statistics as one launch
-        self.fused_adam = (ops._FUSED_ADAM and not self._multi and
+        # (several heads: the transform's weight gradient passes through element-wise ops -- the head masks -- before it reaches its
+        #  parameter, so no product may leave its last sums to the optimiser's launch)
+        self.fused_adam = (ops._FUSED_ADAM and not self._multi and getattr(self.model, 'heads', 1) == 1 and
                            sum(1 for p in self.model.parameters() if p.requires_grad) <= _lib.ADAM_FUSED_MAX)
         self.deferred_gradients = 0
         self._images, self._image_params, self._image_version, self._pack_probe = {}, [], {}, None

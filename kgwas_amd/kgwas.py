@@ -54,7 +54,9 @@ class KGWAS:
         (``data['SNP'].y`` [N, T], KGWAS_Data.from_synthetic(n_traits=T)) -- a shared-trunk multi-task model, not T independent
         models.  It enters ``config`` only when it is not 1, so the config.pkl of a single-trait run is what it always was.
         ``gat_dropout`` (extra, default 0 = the reference): attention dropout p of the GAT layers while training (HeteroGNN); it
-        enters ``config`` only when it is not 0."""
+        enters ``config`` only when it is not 0.
+        ``gat_num_head`` = H in (2, 4): H attention heads of width gnn_hidden_dim / H, concatenated back to gnn_hidden_dim (PyG's
+        GATConv(hidden // H, heads=H); HeteroGNN(gat_split_heads=True)) -- not the reference's literal widening to H * hidden."""
         self.config = {'gnn_num_layers': gnn_num_layers, 'gnn_hidden_dim': gnn_hidden_dim,
                        'gnn_backbone': gnn_backbone, 'gnn_aggr': gnn_aggr, 'gat_num_head': gat_num_head}
         out_channels = int(out_channels)
@@ -68,7 +70,8 @@ class KGWAS:
         self.gnn_num_layers = gnn_num_layers
         self.model = HeteroGNN(self.data.data, gnn_hidden_dim, out_channels, gnn_num_layers, gnn_backbone, gnn_aggr,
                                self.data.snp_init_dim_size, self.data.gene_init_dim_size,
-                               self.data.go_init_dim_size, gat_num_head, no_relu=no_relu, gat_dropout=gat_dropout).to(self.device)
+                               self.data.go_init_dim_size, gat_num_head, no_relu=no_relu, gat_dropout=gat_dropout,
+                               gat_split_heads=True).to(self.device)
 
     def load_pretrained(self, path):
         import pandas as pd
@@ -139,6 +142,9 @@ class KGWAS:
         batches of the reference's order and owns the SNPs of one id range; validation / test / inference predictions are
         computed shard-wise and summed, so every rank sees the same metrics and keeps the same best model."""
         from .shard import ShardedTrainer
+        if getattr(self.model, 'heads', 1) > 1:
+            raise NotImplementedError("gat_num_head > 1 is not available with parallelism='shard': the partial softmax states of "
+                                      "the SNP-sharded exchange are single-head; use parallelism='seed'")
         if getattr(self.model, 'gat_dropout', 0.0) > 0:
             raise NotImplementedError("gat_dropout > 0 is not available with parallelism='shard': it would drop inside partial "
                                       "softmax states; use parallelism='seed'")

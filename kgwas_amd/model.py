@@ -124,9 +124,9 @@ class RelationPack(nn.Module):
     """Parameters of a list of relations of one layer, packed (kgwas/conv.py:81-120 per relation):
     ``w_src_t[i]`` = lin_src.weight^T  ([in k, out c], glorot), ``w_dst_t[j]`` = lin_dst.weight^T of the
     j-th bipartite relation (same-type relations never materialise lin_dst in the reference),
-    ``att_src`` / ``att_dst`` (glorot on [1,1,C]), ``bias`` (zeros)."""
+    ``att_src`` / ``att_dst`` (glorot on [1,heads,C/heads], kept flat: column c belongs to head c // (C/heads)), ``bias`` (zeros)."""
 
-    def __init__(self, edge_types: List[EdgeType], rel_ids: List[int], C: int, c_logical: int = None):
+    def __init__(self, edge_types: List[EdgeType], rel_ids: List[int], C: int, c_logical: int = None, heads: int = 1):
         super().__init__()
         self.n_rels_total = len(edge_types)
         self.rel_ids = list(rel_ids)
@@ -137,7 +137,8 @@ class RelationPack(nn.Module):
         self.bip_pos = {i: j for j, i in enumerate(bip)}
         cl = self.cl = C if c_logical is None else c_logical      # the model's width; storage is C (= 128) wide, zero beyond cl
         a_w = math.sqrt(6.0 / (cl + cl))        # glorot on [C_out, C_in]
-        a_a = math.sqrt(6.0 / (1 + cl))         # glorot on [1, heads=1, C]
+        self.heads = heads
+        a_a = math.sqrt(6.0 / (heads + cl // heads))         # glorot on [1, heads, C / heads]: PyG's, over the last two dimensions
 
         def block(shape, a):
             if cl == C:
@@ -185,7 +186,7 @@ class RelationPack(nn.Module):
         t = pick(getattr(self, field))
         if t is None:
             return None
-        return t[i, :cl].reshape(1, 1, -1) if field.startswith('att') else t[i, :cl]
+        return t[i, :cl].reshape(1, self.heads, -1) if field.startswith('att') else t[i, :cl]
 
     def set(self, i: int, field: str, value: torch.Tensor):
         cl = self.cl
@@ -251,10 +252,14 @@ class HeteroGNN(nn.Module):
     and ``.node_types``.  ``gat_dropout`` = p (an extension: the reference's GATConv has the knob, conv.py:44,224, its HeteroGNN
     never passes it): in training mode the softmax weight of every edge is dropped with probability p and the kept ones scaled
     by 1 / (1 - p), inside the aggregate kernels; which edges is a pure function of (``drop_word``, layer, local edge index) --
-    kgwdrop_keep in include/kgwas_hip.h.  0 (the default) runs exactly the launches the model ran without it."""
+    kgwdrop_keep in include/kgwas_hip.h.  0 (the default) runs exactly the launches the model ran without it.
+    ``gat_split_heads`` (an extension too; KGWAS.initialize_model passes True): ``gat_num_head`` = H in (2, 4) means H heads of width
+    hidden / H concatenated back to hidden (PyG's GATConv(hidden // H, heads=H)).  Without it H > 1 keeps the reference's literal
+    meaning -- GATConv(hidden, heads=H), a state H * hidden wide that breaks the reference's own read-out -- and is refused."""
 
     def __init__(self, pyg_data, hidden_channels, out_channels, num_layers, gnn_backbone, gnn_aggr,
-                 snp_init_dim_size, gene_init_dim_size, go_init_dim_size, gat_num_head, no_relu=False, gat_dropout=0.0):
+                 snp_init_dim_size, gene_init_dim_size, go_init_dim_size, gat_num_head, no_relu=False, gat_dropout=0.0,
+                 gat_split_heads=False):
         super().__init__()
         if gnn_backbone not in ('GAT', 'SAGE'):
             raise NotImplementedError(f"backbone {gnn_backbone!r}: 'GAT' (the reference default, kgwas.py:52) and 'SAGE' "
@@ -274,14 +279,38 @@ class HeteroGNN(nn.Module):
         if gnn_aggr not in ('sum', 'mean', 'min', 'max'):
             raise NotImplementedError(f"gnn_aggr {gnn_aggr!r}: 'sum' (the reference default, fused), 'mean', 'min' and 'max' are "
                                       "built; 'cat' widens the hidden state to R*128 and breaks the reference's own "
-                                      "read-out (kgwas/model.py:50), like gat_num_head > 1")
+                                      "read-out (kgwas/model.py:50), like the reference's literal gat_num_head > 1")
         self.aggr = gnn_aggr
         if not 1 <= hidden_channels <= 128:
             raise NotImplementedError('gnn_hidden_dim > 128: the fused kernels are 128 wide (narrower models run on them '
                                       'zero-padded; wider ones would need a second instantiation of every kernel -- DESIGN.md section 8)')
+        # gat_num_head = H > 1 with this constructor's reference signature alone keeps the reference's literal meaning,
+        # GATConv(hidden, heads=H), which widens the state to H * hidden and breaks the reference's own read-out (model.py:50 expects
+        # hidden_channels inputs): refused, as ever.  ``gat_split_heads=True`` (an extension; KGWAS.initialize_model passes it) selects
+        # what every GAT paper and PyG example means by H heads: GATConv((-1,-1), hidden // H, heads=H) -- H heads of width hidden / H,
+        # concatenated back to hidden.
+        if gat_num_head != int(gat_num_head) or int(gat_num_head) < 1:
+            raise NotImplementedError(f'gat_num_head {gat_num_head!r}: 1, 2 or 4 heads')
+        gat_num_head = int(gat_num_head)
+        if gat_num_head != 1 and not gat_split_heads:
+            raise NotImplementedError('gat_num_head > 1 as the reference builds it (GATConv(hidden, heads=H)) widens the hidden state '
+                                      'to H * hidden and breaks the reference read-out (model.py:50 expects hidden_channels inputs); '
+                                      'gat_split_heads=True builds H heads of width hidden / H concatenated back to hidden '
+                                      '(KGWAS.initialize_model(gat_num_head=H) does)')
         if gat_num_head != 1:
-            raise NotImplementedError('gat_num_head > 1 breaks the reference read-out (model.py:50 expects '
-                                      'hidden_channels inputs); only heads=1 is supported')
+            if gnn_backbone == 'SAGE':
+                raise ValueError("gat_num_head > 1 needs gnn_backbone='GAT': SAGE has no attention heads")
+            if gat_num_head not in (2, 4):
+                raise NotImplementedError(f'gat_num_head {gat_num_head}: the aggregate kernels are built for 1, 2 and 4 heads')
+            if hidden_channels % gat_num_head:
+                raise NotImplementedError(f'gat_num_head {gat_num_head} does not divide gnn_hidden_dim {hidden_channels}: the heads '
+                                          'are hidden / H wide and concatenated back to hidden')
+            if gnn_aggr not in ('sum', 'mean'):
+                raise NotImplementedError(f"gat_num_head > 1 with gnn_aggr {gnn_aggr!r}: the multi-head route is built for the relation "
+                                          "'sum' and 'mean'")
+            if gat_dropout != 0.0:
+                raise NotImplementedError('gat_num_head > 1 with gat_dropout > 0: the dropout kernels are single-head')
+        self.heads = gat_num_head
         self.node_types = list(pyg_data.node_types)
         self.edge_types = [tuple(e) for e in pyg_data.edge_types]
         self.schema = GraphSchema(self.node_types, self.edge_types)
@@ -306,8 +335,9 @@ class HeteroGNN(nn.Module):
             order = [r for t in range(sc.NT) for r in sc.rels_by_dst[t] if r in live]   # grouped by dst type
             dead = [r for r in range(sc.NR) if r not in live]
             Pack = RelationPack if gnn_backbone == 'GAT' else SagePack
-            self.live_packs.append(Pack(self.edge_types, order, hidden_channels, cl))
-            self.dead_packs.append(Pack(self.edge_types, dead, hidden_channels, cl))
+            kw = {'heads': gat_num_head} if gnn_backbone == 'GAT' else {}
+            self.live_packs.append(Pack(self.edge_types, order, hidden_channels, cl, **kw))
+            self.dead_packs.append(Pack(self.edge_types, dead, hidden_channels, cl, **kw))
             slot = {r: ('live', i) for i, r in enumerate(order)}
             slot.update({r: ('dead', i) for i, r in enumerate(dead)})
             self._slot.append(slot)
@@ -331,6 +361,14 @@ class HeteroGNN(nn.Module):
         # min / max are not linear in the messages.
         import os
         self.fold_fc = gnn_backbone == 'GAT' and gnn_aggr in ('sum', 'mean') and os.environ.get('KGW_FOLD_FC', '1') == '1'
+        if gat_num_head > 1:
+            # several heads take the unfused route (_head_layers): no FC_output fold, no parameter riders.  head_mask[h, c] = 1 for
+            # the columns of head h (c // (cl / H) == h), 0 elsewhere and on the zero-padded columns cl..127
+            self.fold_fc = False
+            hm = torch.zeros(gat_num_head, hidden_channels)
+            for hd in range(gat_num_head):
+                hm[hd, hd * (cl // gat_num_head):(hd + 1) * (cl // gat_num_head)] = 1.0
+            self.register_buffer('head_mask', hm, persistent=False)
         if self.fold_fc:
             mlp_of = {'SNP': 0, 'Gene': 1}
             order = self.live_packs[0].rel_ids
@@ -567,6 +605,58 @@ class HeteroGNN(nn.Module):
             U, V, kap, Wp, gam = ops.fold_fc_output_hip(P, U, V, fc, self._fold_tab, weight=Wv)
         return tys, blocks, zws, U, V, bsum, Wv, kap, Wp, gam
 
+    def _head_vectors(self, P: RelationPack):
+        """u_r^h[k] = sum_{c in head h} W_src^T[k, c] att_src[c] and v_r^h likewise (W_dst of a bipartite relation, W_src of a
+        same-type one) for the pack's relations, [H, n_rels_total, 128] by relation id (zero rows for relations outside the pack):
+        element-wise products and sums over a [H, n, 128, 128] tensor -- no library GEMM."""
+        hm = self.head_mask
+        a_s = P.att_src.unsqueeze(0) * hm.unsqueeze(1)                       # [H, n, C]: att_src restricted to the head's columns
+        a_d = P.att_dst.unsqueeze(0) * hm.unsqueeze(1)
+        w_dst = P.w_src_t.index_copy(0, P.bip_t, P.w_dst_t) if len(P.bip) else P.w_src_t
+        u = (P.w_src_t.unsqueeze(0) * a_s.unsqueeze(2)).sum(3)               # [H, n, C(k)]
+        v = (w_dst.unsqueeze(0) * a_d.unsqueeze(2)).sum(3)
+        U = u.new_zeros(self.heads, self.schema.NR, self.hidden).index_copy(1, P.rel_ids_t, u)
+        V = v.new_zeros(self.heads, self.schema.NR, self.hidden).index_copy(1, P.rel_ids_t, v)
+        return U, V
+
+    def _head_layers(self, batch: SampledBatch, h: Dict[str, torch.Tensor], hbuf=None, last_premasked=False):
+        """The layers with gat_num_head = H > 1: per relation exactly GATConv((-1,-1), cl / H, heads=H, concat=True), re-associated
+        as the single-head route is -- the aggregate gathers the layer input once per edge for all heads (ops.gat_aggregate(heads=H):
+        Z[h] = sum_j alpha^h_ij x_j, full width per head), and column c of the output takes head(c)'s aggregate:
+            out_i[c] = sum_k Z[head(c)]_i[k] W_src^T[k, c] + bias[c].
+        That column-block product runs on the layer-transform kernels with the heads as H x R stacked "relations" of column-masked
+        weights W_r^T * mask_h (H times the transform's FLOPs: DESIGN.md section 8).  Unfused: no FC_output fold, no parameter
+        riders; u^h, v^h and the summed bias come from element-wise framework ops."""
+        sc, m, C, NH = self.schema, batch.meta, self.hidden, self.heads
+        for l in range(1, self.num_layers + 1):
+            P: RelationPack = self.live_packs[l - 1]
+            rng = self._dst_range[l - 1]
+            tys = [t for t in range(sc.NT) if int(m.lay_rows[l - 1][t])]
+            blocks = [(rng[t][0], rng[t][1], int(m.z_base[l - 1][t]), int(m.lay_rows[l - 1][t])) for t in tys]
+            U, V = self._head_vectors(P)
+            parts, spans = [], []
+            for t, name in enumerate(sc.node_types):
+                ns = int(m.lay_src[l - 1][t])
+                if ns:
+                    if name not in h or h[name].shape[0] < ns:
+                        raise RuntimeError(f'layer {l}: node type {name!r} takes part in the layer but has no '
+                                           f'incoming relation to produce its layer-{l - 1} state')
+                    parts.append(h[name] if h[name].shape[0] == ns else h[name][:ns])
+                    spans.append((int(m.src_base[l - 1][t]), ns))
+            if hbuf is None:
+                hbuf, _ = self._layer_input(batch, l)
+            H = ops.join_blocks(hbuf, spans, parts) if len(parts) != 1 or parts[0].shape[0] != hbuf.shape[0] else parts[0]
+            # (from layer 2 on, H is the previous layer's ReLU output and its backward is folded into this node's)
+            Z, _, _ = ops.gat_aggregate(batch, l, H, U, V, self.negative_slope, self.temperature, relu_input=(l > 1), heads=NH)
+            hbuf, nxt = self._layer_input(batch, l + 1) if l < self.num_layers else (None, {})
+            outs = ops.layer_transform_heads(P, Z, blocks, self.head_mask, [nxt.get(sc.node_types[t]) for t in tys],
+                                             premasked=(l < self.num_layers) or last_premasked)
+            if self.aggr == 'mean':
+                hbuf = None
+                outs = [o * (1.0 / (hi - lo)) for o, (lo, hi, _, _) in zip(outs, blocks)]
+            h = {sc.node_types[t]: o for t, o in zip(tys, outs)}
+        return h, []
+
     def set_dropout_word(self, word: int):
         """The word of the NEXT steps' attention-dropout masks (``dropout_word(seed, epoch, batch)``): one fill of the resident
         tensor, no synchronisation."""
@@ -590,6 +680,10 @@ class HeteroGNN(nn.Module):
             if want_attention:
                 raise NotImplementedError('attention weights exist for the GAT backbone only (kgwas/model.py:65-72)')
             return self._sage_layers(batch, h, hbuf)
+        if self.heads > 1:
+            if want_attention:
+                raise NotImplementedError('gat_num_head > 1: the attention queries are single-head (kgw_edge_alpha)')
+            return self._head_layers(batch, h, hbuf, last_premasked)
         sc = self.schema
         m = batch.meta
         C = self.hidden
@@ -654,6 +748,8 @@ class HeteroGNN(nn.Module):
     def forward(self, x_dict, edge_index_dict, batch_size, genotype=None, return_h=False,
                 return_attention_weights=False):
         if return_attention_weights and not return_h:           # model.py:65-72,80-81 (mean attention per layer)
+            if self.heads > 1:
+                raise NotImplementedError('gat_num_head > 1: forward(return_attention_weights=True) is single-head')
             return self._forward_with_attention(x_dict, edge_index_dict, batch_size)
         batch: Optional[SampledBatch] = getattr(x_dict, 'kgw_batch', None) or getattr(edge_index_dict, 'kgw_batch', None)
         if batch is None:
@@ -684,6 +780,8 @@ class HeteroGNN(nn.Module):
         """Per layer, the softmax attention weight of every edge the TRAINING path aggregates (live relations, hop-pruned
         destination rows; local edge order of ``batch``) -- what the fused kernels actually use, as opposed to the
         reference-shaped ``forward(return_attention_weights=True)`` which runs all relations over all rows."""
+        if self.heads > 1:
+            raise NotImplementedError('gat_num_head > 1: hot_path_attention is single-head (one alpha per edge)')
         hbuf, blocks = self._layer_input(batch, 1)
         h = self._embed_all(batch, batch.x_dict, blocks, fold=self.fold_fc)
         _, attn = self._fused_layers(batch, h, want_attention=True, hbuf=hbuf, folded=self.fold_fc)
@@ -711,7 +809,8 @@ class HeteroGNN(nn.Module):
         # launched the ordinary way when the scope closes, before the layers read it
         drop = self._dropout()
         fold = self.fold_fc and drop is None                    # (see _dropout: a step that drops runs layer 1 unfolded)
-        riders = ops.ParamRiders() if (ops._G3_RIDERS and self.backbone == 'GAT' and self.num_layers > 1 and _RELVEC_ALL) else None
+        riders = ops.ParamRiders() if (ops._G3_RIDERS and self.backbone == 'GAT' and self.num_layers > 1 and _RELVEC_ALL and
+                                       self.heads == 1) else None
         with ops.param_riders_scope(riders):
             if riders is not None:
                 prep = self._all_layer_params(batch, fold)
@@ -778,6 +877,9 @@ class HeteroGNN(nn.Module):
         those raw values (conv.py:227-228) plus bias, summed over relations, and -- unlike HeteroGNN.forward -- NO
         ReLU is applied between the layers (utils.py:460)."""
         from .sampler import BatchBuffers, DeviceGraph, finish_sample, sample_into
+        if self.heads > 1:
+            raise NotImplementedError('gat_num_head > 1: the attention export (raw_attention_full_graph / '
+                                      'get_disease_critical_network) is single-head')
         if self.backbone != 'GAT':
             raise NotImplementedError('attention weights exist for the GAT backbone only (kgwas/utils.py:437-461)')
         if self.aggr != 'sum':

@@ -590,6 +590,84 @@ class _GatAggregate(torch.autograd.Function):
         return dH[:n_src], dU, dV, None, None, None, None, None, None, None, dlb, None
 
 
+class _GatAggregateHeads(torch.autograd.Function):
+    """``gat_aggregate(..., heads=NH)``, NH = 2 or 4 (KgwLayerArgs.n_heads): every head-carrying array is NH planes of the
+    single-head layout.  U, V [NH, n_rels, 128] -> (stat [NH, z rows, 2], e_edge [NH, n_edges], Z [NH, z rows, 128]); dH is the sum
+    over the heads.  d u_r^h / d v_r^h come from the rider blocks of the src-major launch and one fold launch."""
+
+    @staticmethod
+    def forward(ctx, H, U, V, batch, layer, neg_slope, inv_temp, relu_input, NH):
+        dg, m = batch.dg, batch.meta
+        NT, NR = dg.schema.NT, dg.schema.NR
+        z_rows = int(m.z_base[layer - 1][NT])
+        n_edges = int(m.n_edges[layer - 1])
+        n_chunks = int(m.n_chunks[layer - 1])
+        n_src = int(m.src_base[layer - 1][NT])
+        H = H.contiguous(); U = U.contiguous(); V = V.contiguous()
+        assert H.dtype == torch.float32 and H.shape == (n_src, KGW_C), (H.shape, n_src)
+        assert U.dtype == torch.float32 and U.shape == (NH, NR, KGW_C) and V.shape == U.shape and V.dtype == U.dtype
+        dev = H.device
+        # Z, stat and the backward's d a_dst all start from zero (rows without edges are never visited): one fill, planes of
+        # exactly z_rows rows (the stride the kernels take from the layout)
+        zbuf = torch.zeros(max(NH * z_rows * (KGW_C + 3), 1), device=dev)
+        Z = zbuf[:NH * z_rows * KGW_C].view(NH, z_rows, KGW_C)
+        stat = zbuf[NH * z_rows * KGW_C:NH * z_rows * (KGW_C + 2)].view(NH, z_rows, 2)
+        ctx.da_dst = zbuf[NH * z_rows * (KGW_C + 2):NH * z_rows * (KGW_C + 3)]
+        e_edge = torch.empty(NH, n_edges, device=dev)
+        any_multi = batch.static or any(int(m.multi_cnt[h]) for h in range(dg.n_hops))
+        part = torch.empty(max(NH * n_chunks * PART_STRIDE if any_multi else 4, 4), device=dev)
+        a = _layer_args(batch, layer, neg_slope, inv_temp)
+        a.n_heads = NH
+        a.H, a.V, a.U = _p(H), _p(V), _p(U)
+        a.Z, a.stat, a.e_edge, a.part = _p(Z), _p(stat), _p(e_edge), _p(part)
+        TIMER.attach(a, 'fwd', layer, n_edges, z_rows, n_src)
+        _lib.check(_lib.lib().kgw_gat_aggregate_fwd(C.byref(a), _lib.stream_ptr()), 'kgw_gat_aggregate_fwd')
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(H, U, V, Z, stat, e_edge)
+        ctx.batch, ctx.layer, ctx.neg_slope, ctx.inv_temp, ctx.relu_input, ctx.NH = batch, layer, neg_slope, inv_temp, relu_input, NH
+        ctx.mark_non_differentiable(stat, e_edge)
+        return stat, e_edge, Z
+
+    @staticmethod
+    def backward(ctx, _dstat, _de, dZ):
+        if dZ is None:
+            return (None,) * 9
+        H, U, V, Z, stat, e_edge = ctx.saved_tensors
+        batch, layer, NH = ctx.batch, ctx.layer, ctx.NH
+        dg, m = batch.dg, batch.meta
+        NT, NR = dg.schema.NT, dg.schema.NR
+        z_rows = int(m.z_base[layer - 1][NT])
+        n_edges = int(m.n_edges[layer - 1])
+        n_chunks = int(m.n_chunks[layer - 1])
+        n_src = int(m.src_base[layer - 1][NT])
+        dev = H.device
+        if not (n_src and n_chunks and z_rows):          # an empty layer: nothing was aggregated
+            return torch.zeros_like(H), torch.zeros_like(U), torch.zeros_like(V), None, None, None, None, None, None
+        dZf = dZ.contiguous()
+        assert dZf.shape == (NH, z_rows, KGW_C)
+        adp = torch.empty(NH, n_edges, 2, device=dev)
+        da_dst, ctx.da_dst = ctx.da_dst, None            # zeroed with Z in forward; consumed once
+        if da_dst is None:
+            da_dst = torch.zeros(NH * z_rows, device=dev)
+        part_da = torch.empty(NH * n_chunks * 4, device=dev)
+        part_du = torch.empty(NH * n_chunks, KGW_C, device=dev)
+        duv_ws = torch.empty(NH * 2 * NR * 8 * KGW_C, device=dev)
+        dU, dV = torch.empty(NH, NR, KGW_C, device=dev), torch.empty(NH, NR, KGW_C, device=dev)
+        dH = torch.empty(n_src, KGW_C, device=dev)
+        a = _layer_args(batch, layer, ctx.neg_slope, ctx.inv_temp)
+        a.n_heads = NH
+        a.H, a.U, a.V, a.Z, a.stat, a.e_edge = _p(H), _p(U), _p(V), _p(Z), _p(stat), _p(e_edge)
+        a.dZ, a.adp, a.da_dst, a.part_da, a.dH = _p(dZf), _p(adp), _p(da_dst), _p(part_da), _p(dH)
+        a.part_du, a.seg_chptr, a.duv_ws, a.dU, a.dV = _p(part_du), _p(batch.buf.seg_chptr), _p(duv_ws), _p(dU), _p(dV)
+        a.flags = 2 if ctx.relu_input else 0       # KGW_F_RELU_INPUT
+        L = _lib.lib()
+        TIMER.attach(a, 'bwd_dst', layer, n_edges, z_rows, n_src)
+        _lib.check(L.kgw_gat_aggregate_bwd_dst(C.byref(a), _lib.stream_ptr()), 'kgw_gat_aggregate_bwd_dst')
+        TIMER.attach(a, 'bwd_src', layer, n_edges, z_rows, n_src)
+        _lib.check(L.kgw_gat_aggregate_bwd_src(C.byref(a), _lib.stream_ptr()), 'kgw_gat_aggregate_bwd_src')
+        return dH, dU, dV, None, None, None, None, None, None
+
+
 def aggregate_workspace(batch, layer: int, device) -> torch.Tensor:
     """UNINITIALISED Z / stat / d a_dst workspace of ``gat_aggregate(batch, layer, ...)``: hand it to ``rel_vectors(...,
     zero=ws)`` (which clears it in its own launch) and then to ``gat_aggregate(..., zbuf=ws)``."""
@@ -599,7 +677,8 @@ def aggregate_workspace(batch, layer: int, device) -> torch.Tensor:
 
 def gat_aggregate(batch, layer: int, H: torch.Tensor, U: torch.Tensor, V: torch.Tensor,
                   neg_slope: float = 0.2, temperature: float = 1.0, raw_weights: bool = False,
-                  relu_input: bool = False, zbuf: torch.Tensor = None, logit_bias: torch.Tensor = None, dropout=None):
+                  relu_input: bool = False, zbuf: torch.Tensor = None, logit_bias: torch.Tensor = None, dropout=None,
+                  heads: int = 1):
     """Z[i, r] = sum_j softmax_j(leaky_relu(<H_src[j], u_r> + <H_dst[i], v_r>) / T) H_src[j] for every live relation
     of the layer.  H [n_src_rows,128]: layer input, type-major (``meta.src_base``; a destination node is row i of
     its own type's block); U, V [n_rels,128] by relation id.  Returns (Z [z_rows,128], stat [z_rows,2] =
@@ -616,8 +695,24 @@ def gat_aggregate(batch, layer: int, H: torch.Tensor, U: torch.Tensor, V: torch.
     local edge and 0 for a dropped one (the rule: kgwdrop_keep in include/kgwas_hip.h); ``word`` is an int64 device tensor of
     one element, READ WHEN THE KERNELS RUN (a captured step replays with whatever it then holds).  stat and e_edge stay those
     of the undropped softmax.  A given ``dropout`` always takes the dropout kernels, at p = 0.0 too (the same bits as None).
-    Not with ``raw_weights`` and not in the SNP-sharded mode."""
+    Not with ``raw_weights`` and not in the SNP-sharded mode.
+    ``heads`` = NH in (2, 4): NH attention heads over the same H (KgwLayerArgs.n_heads).  U, V are [NH, n_rels, 128] and the
+    result is (Z [NH, z_rows, 128], stat [NH, z_rows, 2], e_edge [NH, n_edges]): plane h is what a single-head call with
+    (U[h], V[h]) returns, and every gathered row serves all NH heads.  Not with ``raw_weights``, ``logit_bias``, ``dropout``,
+    ``zbuf`` or the SNP-sharded mode."""
     xchg = getattr(batch, 'exchange', None)
+    if heads != 1:
+        if heads not in (2, 4):
+            raise NotImplementedError(f'heads={heads}: the aggregate kernels are built for 1, 2 and 4 heads')
+        what = [n for n, v in (('raw_weights', raw_weights), ('logit_bias', logit_bias is not None), ('dropout', dropout is not None),
+                               ('zbuf', zbuf is not None), ('the SNP-sharded mode', xchg is not None)) if v]
+        if what:
+            raise NotImplementedError(f'heads={heads} together with {", ".join(what)} is not built')
+        if not _lib.has_heads():
+            raise _lib.KgwasHipError('this libkgwas_hip.so predates KgwLayerArgs.n_heads')
+        stat, e_edge, Z = _GatAggregateHeads.apply(H, U, V, batch, layer, float(neg_slope), 1.0 / float(temperature),
+                                                   bool(relu_input), int(heads))
+        return Z, stat, e_edge
     if dropout is not None:
         if raw_weights:
             raise ValueError('attention dropout applies to softmax weights: not with raw_weights=True')
@@ -2212,6 +2307,37 @@ def layer_transform(pack, Z, blocks, out_blocks=None, premasked=False, bias_sum=
         bias_sum = (sel.unsqueeze(2) * pack.bias.detach().unsqueeze(0)).sum(1)        # [blocks, n, 1] * [1, n, C]: no GEMM for a sum
     return _LayerTransform.apply(pack.w_src_t if weight is None else weight, pack.bias, Z, blocks, bias_sum, out_blocks, premasked,
                                  gamma, stat)
+
+
+def layer_transform_heads(pack, Z, blocks, head_mask, out_blocks=None, premasked=False):
+    """The layer transform behind ``gat_aggregate(heads=NH)``: Z [NH, z_rows, C] holds one full-width aggregate per head and
+    column c of the output takes head(c)'s:  h_d = relu(sum_r sum_h Z[h][:, r] @ (W_r^T * mask_h) + sum_r bias_r)  per destination
+    type, ``head_mask`` [NH, C] being the heads' column masks.  It is ``layer_transform`` over NH x R stacked "relations" per
+    destination type -- the same kernels, NH times the reduction length: Z's planes are interleaved into [rows, NH * R, C] blocks
+    (one element-wise copy), the weights masked and stacked to match, and the real bias rides on head 0's slots (the other
+    heads' slots hold constant zeros), so the bias gradient -- the column sums of dz, per slot -- arrives once per relation."""
+    NH, _, C = Z.shape
+    n = pack.w_src_t.shape[0]
+    key = ('heads', NH) + _block_key(blocks)
+    perm = pack._sel_cache.get(key)
+    if perm is None:           # stacked slot NH * lo + h * R + (i - lo) of a block [lo, hi)  <-  row h * n + i of the [NH * n] stacks
+        idx = []
+        for lo, hi, _, _ in blocks:
+            idx += [h * n + i for h in range(NH) for i in range(lo, hi)]
+        perm = torch.tensor(idx, dtype=torch.long, device=Z.device)
+        pack._sel_cache[key] = perm
+    Wm = (pack.w_src_t.unsqueeze(0) * head_mask.view(NH, 1, 1, C)).view(NH * n, C, C).index_select(0, perm)
+    bias_v = torch.cat([pack.bias, pack.bias.new_zeros((NH - 1) * n, C)]).index_select(0, perm)
+    bsum = torch.stack([pack.bias.detach()[lo:hi].sum(0) for lo, hi, _, _ in blocks])
+    pieces, vblocks, z0v, lov = [], [], 0, 0
+    for lo, hi, z0, rows in blocks:
+        R = hi - lo
+        pieces.append(Z[:, z0:z0 + rows * R].reshape(NH, rows, R * C).transpose(0, 1).reshape(rows * NH * R, C))
+        vblocks.append((lov, lov + NH * R, z0v, rows))
+        z0v += rows * NH * R
+        lov += NH * R
+    Zv = torch.cat(pieces, 0) if len(pieces) != 1 else pieces[0].contiguous()
+    return _LayerTransform.apply(Wm, bias_v, Zv, vblocks, bsum, out_blocks, premasked, None, None)
 
 
 class _FoldFC(torch.autograd.Function):
