@@ -42,6 +42,10 @@ extern "C" {
                                          adds them: KgwRelvecJob.duv_pieces / KgwFoldArgs.duv_pieces                              */
 #define KGW_F_RELU_INPUT  2           /* bwd_src: H is the output of a ReLU (model.py:75) whose backward is folded
                                          into this pass: dH *= (H > 0)                                   */
+#define KGW_F_SIGMOID_GATE 8          /* forward and bwd_dst: every edge is weighted by sigmoid(e / T) instead of by the softmax over
+                                         its row (the reference GATConv's sigmoid_gat, kgwas/conv.py:49,219-220; the rule:
+                                         kgwgate_weight below).  bwd_src ignores it.  Together with KGW_F_RAW_WEIGHTS, n_heads > 1, a
+                                         non-zero partial_rels or a non-NULL drop_word_dev: KGW_E_UNSUPPORTED -- before any launch  */
 
 #define KGW_OK           0
 #define KGW_E_NULL      -1
@@ -322,6 +326,23 @@ KGWFAN_INLINE uint32_t kgwdrop_base(uint64_t word, int32_t layer) {
 KGWFAN_INLINE int kgwdrop_keep(uint32_t base, uint32_t local_edge, uint32_t thresh) {
     return kgwfan_mix32(base ^ local_edge) >= thresh;
 }
+
+/* Sigmoid-gated attention (KGW_F_SIGMOID_GATE): alpha = sigmoid(leaky_relu(a_j + a_i) / T) instead of the softmax over the row
+ * (kgwas/conv.py:49,219-220, the reference GATConv's sigmoid_gat; its HeteroGNN never passes it, so like the dropout this is an
+ * EXTENSION, off by default).  The gates are independent per edge and are not normalised by the row's degree.  With
+ * d_e = <H_src[j], u_r> + a_d(i, r) (+ logit_bias[r]),  e_e = d_e > 0 ? d_e : slope * d_e,  inv_temp = 1 / T:
+ *      g_e           = 1 / (1 + exp(-e_e * inv_temp))                                                        (kgwgate_weight)
+ *      Z[i, r]       = sum_j g_e H_src[j]           (no row max, no denominator; a row without in-edges stays 0)
+ *      d g_e         = <dZ[i, r], H_src[j]>
+ *      d pre_e       = g_e (1 - g_e) d g_e inv_temp (e_e > 0 ? 1 : slope)
+ *      adp[e]        = (g_e, d pre_e)               (the record of the src-major pass, which does not change)
+ *      d a_dst[i, r] = sum_e d pre_e                (a plain sum: there is no common-shift invariance to restore)
+ * e_edge keeps the leaky_relu logit e_e, as in every other mode; stat is (0, 1) on visited rows, as with KGW_F_RAW_WEIGHTS.  The
+ * backward re-forms g_e from the stored e_edge with this one expression, so both passes see the same bits.  In fp32 the gate is
+ * exactly 0 below e / T ~ -88.7 (the exponential overflows to +inf) and exactly 1 above ~ 16.7; both ends have d pre_e = 0. */
+#ifdef __HIPCC__
+static __device__ __forceinline__ float kgwgate_weight(float e, float inv_temp) { return 1.0f / (1.0f + __expf(-e * inv_temp)); }
+#endif
 
 /* Replaces: GATConv.edge_update + message + aggregate (kgwas/conv.py:200-228,182) and their
  * autograd for all relations of one layer.                                                    */

@@ -338,6 +338,18 @@ def has_heads() -> bool:
     return lib().kgw_gat_aggregate_fwd(C.byref(a), None) == -2
 
 
+KGW_F_SIGMOID_GATE = 8          # KgwLayerArgs.flags (include/kgwas_hip.h)
+
+
+def has_sigmoid_gate() -> bool:
+    """Does the loaded library know KGW_F_SIGMOID_GATE?  The gate together with KGW_F_RAW_WEIGHTS is refused by value (-3) before
+    anything else is looked at; a library that predates the flag (KGW_LIB_PATH of an A/B run) sees an empty raw-weights layer and
+    returns 0.  No launch either way."""
+    a = KgwLayerArgs()
+    a.flags = KGW_F_SIGMOID_GATE | 1
+    return lib().kgw_gat_aggregate_fwd(C.byref(a), None) == KGW_E_UNSUPPORTED
+
+
 def check(status: int, what: str):
     if status != 0:
         msg = lib().kgw_status_string(int(status))

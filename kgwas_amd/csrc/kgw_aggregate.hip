@@ -137,7 +137,9 @@ __device__ __forceinline__ KgwChunk load_chunk(const KgwChunk* chunks, int c) {
 // message() :227-228 multiplies by that alpha; kgwas/utils.py:446-461).
 // DROP: attention dropout -- the message of edge e is weighted by w * m'(e) (drop_factor; eb = the block's first local edge);
 // the running sum `s` and the logits stay those of the undropped softmax.  With m' == 1.0f the products are the plain values.
-template <int G, bool RAW, bool DROP>
+// GATE (with RAW: the same no-softmax route): the weight is the sigmoid gate of the logit (kgwgate_weight, include/kgwas_hip.h)
+// instead of the logit itself; a padding edge weighs exactly 0.
+template <int G, bool RAW, bool DROP, bool GATE = false>
 __device__ __forceinline__ void fwd_group(const float4* __restrict__ Hb4, int colv, int q0, int hn, int nb,
                                           int half, int hl, const float4& u4, float ad, float slope,
                                           float inv_temp, float& m, float& s, float4& acc, float& ev,
@@ -159,7 +161,7 @@ __device__ __forceinline__ void fwd_group(const float4* __restrict__ Hb4, int co
         float d = kgw_half_allsum(dot4(x[p], u4)) + ad;
         d = d > 0.f ? d : d * slope;
         ev = (hl == q0 + p) ? d : ev;              // lane (half, hl) keeps the logit of edge half*hn+hl
-        if (RAW) { t[p] = valid[p] ? d : 0.f; continue; }
+        if (RAW) { t[p] = valid[p] ? (GATE ? kgwgate_weight(d, inv_temp) : d) : 0.f; continue; }
         t[p] = valid[p] ? d * inv_temp : -INFINITY;
         mb = fmaxf(mb, t[p]);
     }
@@ -191,7 +193,7 @@ __device__ __forceinline__ void grp8_load(const float4* __restrict__ Hb4, int co
     }
 }
 
-template <bool RAW, bool DROP>
+template <bool RAW, bool DROP, bool GATE = false>
 __device__ __forceinline__ void fwd_grp8_compute(const float4 (&x)[8], int q0, int hn, int nb, int half, int hl,
                                                  const float4& u4, float ad, float slope, float inv_temp, float& m, float& s,
                                                  float4& acc, float& ev, const DropCtx& D, int eb) {
@@ -205,7 +207,7 @@ __device__ __forceinline__ void fwd_grp8_compute(const float4 (&x)[8], int q0, i
     ev = ((hl >> 3) == (q0 >> 3) && hl == qm) ? d : ev;        // lane (half, q) keeps the logit of edge half*hn + q
     float w;
     if (RAW) {
-        w = valid ? d : 0.f;
+        w = valid ? (GATE ? kgwgate_weight(d, inv_temp) : d) : 0.f;
     } else {
         const float t = valid ? d * inv_temp : -INFINITY;
         const float mn = fmaxf(m, kgw_max8(t));
@@ -223,23 +225,24 @@ __device__ __forceinline__ void fwd_grp8_compute(const float4 (&x)[8], int q0, i
 
 // Eight edges per half with the transposed reduction (kgw_half_reduce8): the lane with (hl & 7) == p owns edge q0 + p --
 // its logit, its softmax weight -- and hands the weight to the other lanes of its 8-lane group with one swizzle.
-template <bool RAW, bool DROP>
+template <bool RAW, bool DROP, bool GATE = false>
 __device__ __forceinline__ void fwd_group8(const float4* __restrict__ Hb4, int colv, int q0, int hn, int nb,
                                            int half, int hl, const float4& u4, float ad, float slope,
                                            float inv_temp, float& m, float& s, float4& acc, float& ev,
                                            const DropCtx& D, int eb) {
     float4 x[8];
     grp8_load(Hb4, colv, q0, hn, nb, half, hl, x);
-    fwd_grp8_compute<RAW, DROP>(x, q0, hn, nb, half, hl, u4, ad, slope, inv_temp, m, s, acc, ev, D, eb);
+    fwd_grp8_compute<RAW, DROP, GATE>(x, q0, hn, nb, half, hl, u4, ad, slope, inv_temp, m, s, acc, ev, D, eb);
 }
 
 // PIPE: software pipelining inside a chunk.  A chunk of n edges used to cost one memory round trip for the column ids of
 // every 64 edges plus one per group of 16 rows (a 256-edge chunk of a hub row: 20 dependent round trips, and the longest
 // chunks set the kernel's tail -- halving KGW_CHUNK alone took 64 -> 58 us); with PIPE the next block's column ids and
 // the next group's rows are requested before the current group is reduced.
-template <bool RAW, bool PIPE, bool DROP>
+template <bool RAW, bool PIPE, bool DROP, bool GATE = false>
 __global__ void __launch_bounds__(KGW_BLK) k_agg_fwd(LayerTab T, AggPtrs P, float slope, float inv_temp) {
     static_assert(!(RAW && DROP), "attention dropout applies to softmax weights only");
+    static_assert(!GATE || RAW, "the sigmoid gate takes the no-softmax route: partial records (0, 1), den = 1");
     const int lane = kgw_lane(), half = lane >> 5, hl = lane & 31;
     const int nw = gridDim.x * 4;
     const DropCtx D = drop_ctx<DROP>(P);
@@ -283,22 +286,22 @@ __global__ void __launch_bounds__(KGW_BLK) k_agg_fwd(LayerTab T, AggPtrs P, floa
                     const int q1 = q0 + 8;
                     const bool more1 = hn - q1 > 4;
                     if (more1) grp8_load(Hb4, colv, q1, hn, nb, half, hl, x1);
-                    fwd_grp8_compute<RAW, DROP>(x0, q0, hn, nb, half, hl, u4, ad, slope, inv_temp, m, s, acc, ev, D, ck.e0 + b);
+                    fwd_grp8_compute<RAW, DROP, GATE>(x0, q0, hn, nb, half, hl, u4, ad, slope, inv_temp, m, s, acc, ev, D, ck.e0 + b);
                     q0 = q1;
                     if (!more1) break;
                     const int q2 = q1 + 8;
                     const bool more2 = hn - q2 > 4;
                     if (more2) grp8_load(Hb4, colv, q2, hn, nb, half, hl, x0);
-                    fwd_grp8_compute<RAW, DROP>(x1, q1, hn, nb, half, hl, u4, ad, slope, inv_temp, m, s, acc, ev, D, ck.e0 + b);
+                    fwd_grp8_compute<RAW, DROP, GATE>(x1, q1, hn, nb, half, hl, u4, ad, slope, inv_temp, m, s, acc, ev, D, ck.e0 + b);
                     q0 = q2;
                     if (!more2) break;
                 }
             }
             for (; q0 < hn;) {
                 const int rem = hn - q0;
-                if (rem > 4)      { fwd_group8<RAW, DROP>(Hb4, colv, q0, hn, nb, half, hl, u4, ad, slope, inv_temp, m, s, acc, ev, D, ck.e0 + b); q0 += 8; }
-                else if (rem > 2) { fwd_group<4, RAW, DROP>(Hb4, colv, q0, hn, nb, half, hl, u4, ad, slope, inv_temp, m, s, acc, ev, D, ck.e0 + b); q0 += 4; }
-                else              { fwd_group<2, RAW, DROP>(Hb4, colv, q0, hn, nb, half, hl, u4, ad, slope, inv_temp, m, s, acc, ev, D, ck.e0 + b); q0 += 2; }
+                if (rem > 4)      { fwd_group8<RAW, DROP, GATE>(Hb4, colv, q0, hn, nb, half, hl, u4, ad, slope, inv_temp, m, s, acc, ev, D, ck.e0 + b); q0 += 8; }
+                else if (rem > 2) { fwd_group<4, RAW, DROP, GATE>(Hb4, colv, q0, hn, nb, half, hl, u4, ad, slope, inv_temp, m, s, acc, ev, D, ck.e0 + b); q0 += 4; }
+                else              { fwd_group<2, RAW, DROP, GATE>(Hb4, colv, q0, hn, nb, half, hl, u4, ad, slope, inv_temp, m, s, acc, ev, D, ck.e0 + b); q0 += 2; }
             }
             const int i = half * hn + hl;
             if (hl < hn && i < nb) P.e_edge[ck.e0 + b + i] = ev;
@@ -394,7 +397,9 @@ __global__ void __launch_bounds__(KGW_BLK) k_agg_fwd_combine(LayerTab T, AggPtrs
 // sum_k alpha_k dalpha'_k with dalpha'_e = m'_e <dZ_i, H_j>: the edge's d alpha takes the factor, every alpha outside it (dlogit,
 // the row sums B and S) stays the undropped softmax, and the record handed to the src-major pass carries the message weight
 // alpha_e m'_e.  With m' == 1.0f the products are the plain values.
-template <int G, bool DROP>
+// GATE: the sigmoid gate (kgwgate_weight, include/kgwas_hip.h), re-formed from the stored logit with the forward's expression:
+// d pre_e = g_e (1 - g_e) <dZ_i, H_j> s_e -- no cdot, no M, no inv_den, no E / B / S row sums (the callers pass and keep zeros).
+template <int G, bool DROP, bool GATE = false>
 __device__ __forceinline__ void bwd_group(const float4* __restrict__ Hb4, int colv, float evin, int q0, int hn,
                                           int nb, int half, int hl, const float4& dz4, float cdot, float M,
                                           float inv_den, float slope, float inv_temp, float& av, float& dv,
@@ -415,26 +420,26 @@ __device__ __forceinline__ void bwd_group(const float4* __restrict__ Hb4, int co
 #pragma unroll
     for (int p = 0; p < G; ++p) {
         float dalpha = kgw_half_allsum(dot4(x[p], dz4));
-        const float alpha = __expf(t[p] * inv_temp - M) * inv_den;
+        const float alpha = GATE ? kgwgate_weight(t[p], inv_temp) : __expf(t[p] * inv_temp - M) * inv_den;   // (t = -inf: 0 either way)
         float aw = alpha;                                          // message weight of the edge (adp.x)
         if (DROP) {
             const float mf = drop_factor(D, eb + half * hn + q0 + p);     // (every lane, for every edge)
             dalpha *= mf; aw *= mf;
         }
-        const float dlogit = alpha * (dalpha - cdot);
+        const float dlogit = GATE ? alpha * (1.0f - alpha) * dalpha : alpha * (dalpha - cdot);
         const float sfac = inv_temp * (t[p] > 0.f ? 1.0f : slope);
         const float dpre = dlogit * sfac;
         av = (hl == q0 + p) ? aw : av;
         dv = (hl == q0 + p) ? dpre : dv;
         dsum += dpre;
-        esum += dlogit; bsum += alpha * sfac; ssum += alpha;       // (the row's consistent d a_dst: see k_agg_bwd_dst)
+        if (!GATE) { esum += dlogit; bsum += alpha * sfac; ssum += alpha; }       // (the row's consistent d a_dst: see k_agg_bwd_dst)
         fma4(ua, dpre, x[p]);                      // d u_r += d pre-activation * h_src (every lane has the edge's dpre here)
     }
 }
 
 // Eight edges per half, transposed reduction (see fwd_group8): the lane with (hl & 7) == p owns edge q0 + p.  `dsum`
 // here collects only the lane's OWN edges; the caller folds the 8 residues once per chunk (kgw_sum8).
-template <bool DROP>
+template <bool DROP, bool GATE = false>
 __device__ __forceinline__ void bwd_grp8_compute(const float4 (&x)[8], float evin, int q0, int hn, int nb, int half, int hl,
                                                  const float4& dz4, float cdot, float M, float inv_den, float slope,
                                                  float inv_temp, float& av, float& dv, float& dsum_own, float4& ua,
@@ -447,22 +452,24 @@ __device__ __forceinline__ void bwd_grp8_compute(const float4 (&x)[8], float evi
     const float e = __shfl(evin, half * 32 + (qm & 31), 64);     // logit kept by lane (half, q)
     const float t = valid ? e : -INFINITY;
     float dalpha = kgw_half_reduce8(part, hl);
-    const float alpha = __expf(t * inv_temp - M) * inv_den;
+    const float alpha = GATE ? kgwgate_weight(t, inv_temp) : __expf(t * inv_temp - M) * inv_den;      // (t = -inf: 0 either way)
     float aw = alpha;                                            // message weight of the edge (adp.x)
     if (DROP) {
         const float mf = drop_factor(D, eb + half * hn + qm);   // the lane that owns the edge
         dalpha *= mf; aw *= mf;
     }
-    const float dlogit = alpha * (dalpha - cdot);
+    const float dlogit = GATE ? alpha * (1.0f - alpha) * dalpha : alpha * (dalpha - cdot);
     const float sfac = inv_temp * (t > 0.f ? 1.0f : slope);
     const float dpre = dlogit * sfac;
     const bool mine = (hl == qm);
     av = mine ? aw : av;
     dv = mine ? dpre : dv;
     dsum_own += (hl < 8) ? dpre : 0.f;          // one copy per edge: the 8 residues of the first 8-lane group
-    esum_own += (hl < 8) ? dlogit : 0.f;
-    bsum_own += (hl < 8) ? alpha * sfac : 0.f;
-    ssum_own += (hl < 8) ? alpha : 0.f;
+    if (!GATE) {
+        esum_own += (hl < 8) ? dlogit : 0.f;
+        bsum_own += (hl < 8) ? alpha * sfac : 0.f;
+        ssum_own += (hl < 8) ? alpha : 0.f;
+    }
     // d u_r += d pre-activation(edge) * h_src(edge): lane p of the half owns edge q0 + p's value (0 for a padding edge)
     // (two scalar lane reads + a select per edge instead of a cross-lane permute through the LDS crossbar)
     const int dbits = __builtin_bit_cast(int, dpre);
@@ -474,7 +481,7 @@ __device__ __forceinline__ void bwd_grp8_compute(const float4 (&x)[8], float evi
     }
 }
 
-template <bool DROP>
+template <bool DROP, bool GATE = false>
 __device__ __forceinline__ void bwd_group8(const float4* __restrict__ Hb4, int colv, float evin, int q0, int hn,
                                            int nb, int half, int hl, const float4& dz4, float cdot, float M,
                                            float inv_den, float slope, float inv_temp, float& av, float& dv,
@@ -482,12 +489,13 @@ __device__ __forceinline__ void bwd_group8(const float4* __restrict__ Hb4, int c
                                            const DropCtx& D, int eb) {
     float4 x[8];
     grp8_load(Hb4, colv, q0, hn, nb, half, hl, x);
-    bwd_grp8_compute<DROP>(x, evin, q0, hn, nb, half, hl, dz4, cdot, M, inv_den, slope, inv_temp, av, dv, dsum_own, ua,
-                           esum_own, bsum_own, ssum_own, D, eb);
+    bwd_grp8_compute<DROP, GATE>(x, evin, q0, hn, nb, half, hl, dz4, cdot, M, inv_den, slope, inv_temp, av, dv, dsum_own, ua,
+                                 esum_own, bsum_own, ssum_own, D, eb);
 }
 
-template <bool PIPE, bool DROP>
+template <bool PIPE, bool DROP, bool GATE = false>
 __global__ void __launch_bounds__(KGW_BLK) __attribute__((amdgpu_waves_per_eu(4, 4))) k_agg_bwd_dst(LayerTab T, AggPtrs P, float slope, float inv_temp) {
+    static_assert(!(GATE && DROP), "attention dropout applies to softmax weights only");
     const int lane = kgw_lane(), half = lane >> 5, hl = lane & 31;
     const int nw = gridDim.x * 4;
     const DropCtx D = drop_ctx<DROP>(P);
@@ -498,7 +506,6 @@ __global__ void __launch_bounds__(KGW_BLK) __attribute__((amdgpu_waves_per_eu(4,
         if (!T.live[r]) continue;
         const int zrow = T.z0[r] + ck.row * T.zstride[r];
         const float4 dz4 = ((const float4*)(P.dZ + (int64_t)zrow * KGW_C))[hl];
-        const float4 z4 = ((const float4*)(P.Z + (int64_t)zrow * KGW_C))[hl];
         // sum_k alpha_ik dalpha_ik = <dz_i, z_i>: from the STORED fp32 aggregate -- one rounding away from the sum the edges below
         // would give, which is all that is left of d a_dst = sum_e dpre_e wherever a row's logits sit on one branch of the leaky
         // ReLU (it is 0 in exact arithmetic: the softmax of conv.py:223 does not see a common shift).  Round 5: the per-edge values
@@ -506,9 +513,14 @@ __global__ void __launch_bounds__(KGW_BLK) __attribute__((amdgpu_waves_per_eu(4,
         // d alpha: with E = sum a_e (dalpha_e - c0), B = sum a_e s_e, S = sum a_e (s_e = leaky slope / T of the edge),
         //     d a_dst = sum_e a_e s_e (dalpha_e - c0) - (E / S) B  =  sum_e a_e s_e (dalpha_e - c*),  c* = sum a_e dalpha_e / sum a_e
         // -- what autograd of the reference's softmax computes, edge by edge, in differences (dalpha_e - c0) that are small.
-        const float cdot = kgw_half_allsum(dot4(dz4, z4));
-        const float M = P.stat[2 * (int64_t)zrow];
-        const float inv_den = 1.0f / P.stat[2 * (int64_t)zrow + 1];
+        // (GATE: every edge's d pre-activation is its own -- neither Z nor stat is read, and d a_dst is the plain sum `tot`)
+        float cdot = 0.f, M = 0.f, inv_den = 1.f;
+        if (!GATE) {
+            const float4 z4 = ((const float4*)(P.Z + (int64_t)zrow * KGW_C))[hl];
+            cdot = kgw_half_allsum(dot4(dz4, z4));
+            M = P.stat[2 * (int64_t)zrow];
+            inv_den = 1.0f / P.stat[2 * (int64_t)zrow + 1];
+        }
         const float4* Hb4 = (const float4*)(P.H + (int64_t)T.src_base[r] * KGW_C);
         float dsum = 0.f, dsum_own = 0.f;
         float esum = 0.f, bsum = 0.f, ssum = 0.f, esum_own = 0.f, bsum_own = 0.f, ssum_own = 0.f;
@@ -546,14 +558,14 @@ __global__ void __launch_bounds__(KGW_BLK) __attribute__((amdgpu_waves_per_eu(4,
                     const int q1 = q0 + 8;
                     const bool more1 = hn - q1 > 4;
                     if (more1) grp8_load(Hb4, colv, q1, hn, nb, half, hl, x1);
-                    bwd_grp8_compute<DROP>(x0, evin, q0, hn, nb, half, hl, dz4, cdot, M, inv_den, slope, inv_temp, av, dv, dsum_own, ua,
+                    bwd_grp8_compute<DROP, GATE>(x0, evin, q0, hn, nb, half, hl, dz4, cdot, M, inv_den, slope, inv_temp, av, dv, dsum_own, ua,
                                            esum_own, bsum_own, ssum_own, D, ck.e0 + b);
                     q0 = q1;
                     if (!more1) break;
                     const int q2 = q1 + 8;
                     const bool more2 = hn - q2 > 4;
                     if (more2) grp8_load(Hb4, colv, q2, hn, nb, half, hl, x0);
-                    bwd_grp8_compute<DROP>(x1, evin, q1, hn, nb, half, hl, dz4, cdot, M, inv_den, slope, inv_temp, av, dv, dsum_own, ua,
+                    bwd_grp8_compute<DROP, GATE>(x1, evin, q1, hn, nb, half, hl, dz4, cdot, M, inv_den, slope, inv_temp, av, dv, dsum_own, ua,
                                            esum_own, bsum_own, ssum_own, D, ck.e0 + b);
                     q0 = q2;
                     if (!more2) break;
@@ -561,9 +573,9 @@ __global__ void __launch_bounds__(KGW_BLK) __attribute__((amdgpu_waves_per_eu(4,
             }
             for (; q0 < hn;) {
                 const int rem = hn - q0;
-                if (rem > 4)      { bwd_group8<DROP>(Hb4, colv, evin, q0, hn, nb, half, hl, dz4, cdot, M, inv_den, slope, inv_temp, av, dv, dsum_own, ua, esum_own, bsum_own, ssum_own, D, ck.e0 + b); q0 += 8; }
-                else if (rem > 2) { bwd_group<4, DROP>(Hb4, colv, evin, q0, hn, nb, half, hl, dz4, cdot, M, inv_den, slope, inv_temp, av, dv, dsum, ua, esum, bsum, ssum, D, ck.e0 + b); q0 += 4; }
-                else              { bwd_group<2, DROP>(Hb4, colv, evin, q0, hn, nb, half, hl, dz4, cdot, M, inv_den, slope, inv_temp, av, dv, dsum, ua, esum, bsum, ssum, D, ck.e0 + b); q0 += 2; }
+                if (rem > 4)      { bwd_group8<DROP, GATE>(Hb4, colv, evin, q0, hn, nb, half, hl, dz4, cdot, M, inv_den, slope, inv_temp, av, dv, dsum_own, ua, esum_own, bsum_own, ssum_own, D, ck.e0 + b); q0 += 8; }
+                else if (rem > 2) { bwd_group<4, DROP, GATE>(Hb4, colv, evin, q0, hn, nb, half, hl, dz4, cdot, M, inv_den, slope, inv_temp, av, dv, dsum, ua, esum, bsum, ssum, D, ck.e0 + b); q0 += 4; }
+                else              { bwd_group<2, DROP, GATE>(Hb4, colv, evin, q0, hn, nb, half, hl, dz4, cdot, M, inv_den, slope, inv_temp, av, dv, dsum, ua, esum, bsum, ssum, D, ck.e0 + b); q0 += 2; }
             }
             if (mine) ((float2*)P.adp)[ck.e0 + b + i] = make_float2(av, dv);
         }
@@ -583,9 +595,9 @@ __global__ void __launch_bounds__(KGW_BLK) __attribute__((amdgpu_waves_per_eu(4,
         if (lane == 0) {
             // (a relation whose segments hold only THIS rank's part of the edges -- SNP-sharded mode -- keeps the plain sum: c* is
             //  a property of the whole row, and the ranks' d a_dst are added as they are)
-            const bool partial = (T.partial >> r) & 1ull;
+            const bool partial = GATE || ((T.partial >> r) & 1ull);
             if (ck.nch == 1) P.da_dst[zrow] = partial ? tot : tot - (te / ts) * tb;
-            else ((float4*)P.part_da)[c] = make_float4(tot, te, tb, ts);
+            else ((float4*)P.part_da)[c] = GATE ? make_float4(tot, 0.f, 0.f, 1.f) : make_float4(tot, te, tb, ts);   // (s.x - (0 / n) * 0)
         }
     }
 }
@@ -1213,6 +1225,13 @@ int check_drop(const KgwLayerArgs* a) {
     return KGW_OK;
 }
 
+// the sigmoid gate (KGW_F_SIGMOID_GATE): refused with raw-logit weights, several heads, partial softmax states and dropout
+int check_gate(const KgwLayerArgs* a) {
+    if (!(a->flags & KGW_F_SIGMOID_GATE)) return KGW_OK;
+    if ((a->flags & KGW_F_RAW_WEIGHTS) || a->n_heads > 1 || a->partial_rels || a->drop_word_dev) return KGW_E_UNSUPPORTED;
+    return KGW_OK;
+}
+
 // The other PIPE value of every dst-major kernel (the host selects the forward plain and the backward pipelined, see
 // kgw_gat_aggregate_fwd): compiled only for the resource table of profiles/attn_dropout/resource_usage.txt.
 #ifdef KGW_AGG_ALL_PIPE
@@ -1220,6 +1239,8 @@ template __global__ void k_agg_fwd<false, true, false>(LayerTab, AggPtrs, float,
 template __global__ void k_agg_fwd<false, true, true>(LayerTab, AggPtrs, float, float);
 template __global__ void k_agg_bwd_dst<false, false>(LayerTab, AggPtrs, float, float);
 template __global__ void k_agg_bwd_dst<false, true>(LayerTab, AggPtrs, float, float);
+template __global__ void k_agg_fwd<true, true, false, true>(LayerTab, AggPtrs, float, float);
+template __global__ void k_agg_bwd_dst<false, false, true>(LayerTab, AggPtrs, float, float);
 #endif
 
 inline int grid_for_waves(int64_t n_waves) {
@@ -1320,6 +1341,7 @@ int heads_bwd_src(const KgwLayerArgs* a, const LayerTab& T, const AggPtrs& P, co
 extern "C" int kgw_gat_aggregate_fwd(const KgwLayerArgs* a, kgw_stream_t stream_) {
     if (!a) return KGW_E_NULL;
     if (int rc = check_heads(a)) return rc;
+    if (int rc = check_gate(a)) return rc;
     if (a->n_heads > 1) {
         if (a->n_chunks == 0) return KGW_OK;
         if (!a->chunks || !a->col_local || !a->H || !a->V || !a->U || !a->Z || !a->stat || !a->e_edge || !a->part || !a->meta_dev)
@@ -1345,6 +1367,12 @@ extern "C" int kgw_gat_aggregate_fwd(const KgwLayerArgs* a, kgw_stream_t stream_
     // (software-pipelined chunks -- next group's rows + next block's ids in flight -- measured at KGW_CHUNK = 128 on the layer-1
     //  launch of the benchmark: forward 55.5 us plain / 57.5 pipelined (122 VGPRs cost two wavefronts per SIMD), backward-dst
     //  56.8 plain / 53.2 pipelined => the forward plain, the dst-major backward pipelined)
+    // (the gate: the no-softmax route with sigmoid weights; its hub rows' partial records carry (0, 1) and the combine takes den = 1)
+    const bool gate = (a->flags & KGW_F_SIGMOID_GATE) != 0;
+    if (gate) {
+        P.raw = 1;
+        k_agg_fwd<true, false, false, true><<<grid_fine(a->n_chunks), KGW_BLK, 0, st>>>(T, P, a->neg_slope, a->inv_temp);
+    } else
     if (P.raw)            k_agg_fwd<true, false, false><<<grid_fine(a->n_chunks), KGW_BLK, 0, st>>>(T, P, a->neg_slope, a->inv_temp);
     else if (P.drop_word) k_agg_fwd<false, false, true><<<grid_fine(a->n_chunks), KGW_BLK, 0, st>>>(T, P, a->neg_slope, a->inv_temp);
     else                  k_agg_fwd<false, false, false><<<grid_fine(a->n_chunks), KGW_BLK, 0, st>>>(T, P, a->neg_slope, a->inv_temp);
@@ -1360,6 +1388,7 @@ extern "C" int kgw_gat_aggregate_fwd(const KgwLayerArgs* a, kgw_stream_t stream_
 extern "C" int kgw_gat_aggregate_bwd_dst(const KgwLayerArgs* a, kgw_stream_t stream_) {
     if (!a) return KGW_E_NULL;
     if (int rc = check_heads(a)) return rc;
+    if (int rc = check_gate(a)) return rc;
     if (a->n_heads > 1) {
         if (a->n_chunks == 0) return KGW_OK;
         if (!a->chunks || !a->col_local || !a->H || !a->Z || !a->stat || !a->e_edge || !a->dZ || !a->adp || !a->da_dst ||
@@ -1383,6 +1412,8 @@ extern "C" int kgw_gat_aggregate_bwd_dst(const KgwLayerArgs* a, kgw_stream_t str
     AggPtrs P = build_ptrs(a);
     hipStream_t st = (hipStream_t)stream_;
     if (a->ev_before) KGW_HIP(hipEventRecord((hipEvent_t)a->ev_before, st));
+    if (a->flags & KGW_F_SIGMOID_GATE) k_agg_bwd_dst<true, false, true><<<grid_fine(a->n_chunks), KGW_BLK, 0, st>>>(T, P, a->neg_slope, a->inv_temp);
+    else
     if (P.drop_word) k_agg_bwd_dst<true, true><<<grid_fine(a->n_chunks), KGW_BLK, 0, st>>>(T, P, a->neg_slope, a->inv_temp);
     else             k_agg_bwd_dst<true, false><<<grid_fine(a->n_chunks), KGW_BLK, 0, st>>>(T, P, a->neg_slope, a->inv_temp);
     KGW_LAUNCH_CHECK();

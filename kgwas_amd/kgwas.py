@@ -49,14 +49,17 @@ class KGWAS:
         self.exp_name = exp_name
 
     def initialize_model(self, gnn_num_layers=2, gnn_hidden_dim=128, gnn_backbone='GAT', gnn_aggr='sum',
-                         gat_num_head=1, no_relu=False, out_channels=1, gat_dropout=0.0):
+                         gat_num_head=1, no_relu=False, out_channels=1, gat_dropout=0.0, gat_sigmoid=False, gat_temperature=1.0):
         """``out_channels`` (extra, default 1 = the reference, kgwas.py:52): T > 1 reads ONE shared trunk out into T label columns
         (``data['SNP'].y`` [N, T], KGWAS_Data.from_synthetic(n_traits=T)) -- a shared-trunk multi-task model, not T independent
         models.  It enters ``config`` only when it is not 1, so the config.pkl of a single-trait run is what it always was.
         ``gat_dropout`` (extra, default 0 = the reference): attention dropout p of the GAT layers while training (HeteroGNN); it
         enters ``config`` only when it is not 0.
         ``gat_num_head`` = H in (2, 4): H attention heads of width gnn_hidden_dim / H, concatenated back to gnn_hidden_dim (PyG's
-        GATConv(hidden // H, heads=H); HeteroGNN(gat_split_heads=True)) -- not the reference's literal widening to H * hidden."""
+        GATConv(hidden // H, heads=H); HeteroGNN(gat_split_heads=True)) -- not the reference's literal widening to H * hidden.
+        ``gat_sigmoid`` / ``gat_temperature`` (extras, defaults False / 1 = the reference's model; its GATConv's ``sigmoid_gat`` and
+        ``temperature``, conv.py:49-50): sigmoid gates instead of the softmax, and the divisor T of the attention logits (HeteroGNN).
+        Each enters ``config`` only when it is not the default."""
         self.config = {'gnn_num_layers': gnn_num_layers, 'gnn_hidden_dim': gnn_hidden_dim,
                        'gnn_backbone': gnn_backbone, 'gnn_aggr': gnn_aggr, 'gat_num_head': gat_num_head}
         out_channels = int(out_channels)
@@ -67,11 +70,16 @@ class KGWAS:
         gat_dropout = float(gat_dropout)
         if gat_dropout != 0.0:
             self.config['gat_dropout'] = gat_dropout
+        gat_sigmoid, gat_temperature = bool(gat_sigmoid), float(gat_temperature)
+        if gat_sigmoid:
+            self.config['gat_sigmoid'] = True
+        if gat_temperature != 1.0:
+            self.config['gat_temperature'] = gat_temperature
         self.gnn_num_layers = gnn_num_layers
         self.model = HeteroGNN(self.data.data, gnn_hidden_dim, out_channels, gnn_num_layers, gnn_backbone, gnn_aggr,
                                self.data.snp_init_dim_size, self.data.gene_init_dim_size,
                                self.data.go_init_dim_size, gat_num_head, no_relu=no_relu, gat_dropout=gat_dropout,
-                               gat_split_heads=True).to(self.device)
+                               gat_split_heads=True, gat_sigmoid=gat_sigmoid, gat_temperature=gat_temperature).to(self.device)
 
     def load_pretrained(self, path):
         import pandas as pd
@@ -148,6 +156,9 @@ class KGWAS:
         if getattr(self.model, 'gat_dropout', 0.0) > 0:
             raise NotImplementedError("gat_dropout > 0 is not available with parallelism='shard': it would drop inside partial "
                                       "softmax states; use parallelism='seed'")
+        if getattr(self.model, 'gat_sigmoid', False) or getattr(self.model, 'temperature', 1.0) != 1.0:
+            raise NotImplementedError("gat_sigmoid / gat_temperature are not available with parallelism='shard': the exchange of "
+                                      "partial softmax states is built for the softmax at T = 1; use parallelism='seed'")
         if self.model.lin.out_features != 1:
             raise NotImplementedError("out_channels > 1 (multi-trait labels) is not available with parallelism='shard': the "
                                       "sharded step's read-out and loss are single-column; use parallelism='seed'")

@@ -255,11 +255,16 @@ class HeteroGNN(nn.Module):
     kgwdrop_keep in include/kgwas_hip.h.  0 (the default) runs exactly the launches the model ran without it.
     ``gat_split_heads`` (an extension too; KGWAS.initialize_model passes True): ``gat_num_head`` = H in (2, 4) means H heads of width
     hidden / H concatenated back to hidden (PyG's GATConv(hidden // H, heads=H)).  Without it H > 1 keeps the reference's literal
-    meaning -- GATConv(hidden, heads=H), a state H * hidden wide that breaks the reference's own read-out -- and is refused."""
+    meaning -- GATConv(hidden, heads=H), a state H * hidden wide that breaks the reference's own read-out -- and is refused.
+    ``gat_sigmoid`` / ``gat_temperature`` (extensions, keyword only: the reference's GATConv has both switches, conv.py:49-50,
+    217-224, its HeteroGNN never passes them): ``gat_temperature`` = T > 0 divides every attention logit, in the softmax and in the
+    gate; ``gat_sigmoid=True`` weights every edge by sigmoid(e / T) instead of by the softmax over its row (independent gates, not
+    normalised by degree: ops.gat_aggregate(sigmoid_gate=True)), in training, evaluation, the attention queries and the export.
+    GAT only; not with gat_num_head > 1 or gat_dropout > 0.  A gated model does not fold FC_output into layer 1 (``fold_fc``)."""
 
     def __init__(self, pyg_data, hidden_channels, out_channels, num_layers, gnn_backbone, gnn_aggr,
                  snp_init_dim_size, gene_init_dim_size, go_init_dim_size, gat_num_head, no_relu=False, gat_dropout=0.0,
-                 gat_split_heads=False):
+                 gat_split_heads=False, *, gat_sigmoid=False, gat_temperature=1.0):
         super().__init__()
         if gnn_backbone not in ('GAT', 'SAGE'):
             raise NotImplementedError(f"backbone {gnn_backbone!r}: 'GAT' (the reference default, kgwas.py:52) and 'SAGE' "
@@ -311,6 +316,17 @@ class HeteroGNN(nn.Module):
             if gat_dropout != 0.0:
                 raise NotImplementedError('gat_num_head > 1 with gat_dropout > 0: the dropout kernels are single-head')
         self.heads = gat_num_head
+        gat_temperature = float(gat_temperature)
+        if not (math.isfinite(gat_temperature) and gat_temperature > 0.0):
+            raise ValueError(f'gat_temperature {gat_temperature}: a finite T > 0')
+        self.gat_sigmoid = bool(gat_sigmoid)
+        if self.gat_sigmoid:
+            if gnn_backbone == 'SAGE':
+                raise ValueError("gat_sigmoid needs gnn_backbone='GAT': SAGE has no attention logits to gate")
+            if gat_num_head > 1:
+                raise NotImplementedError('gat_sigmoid with gat_num_head > 1: the gate kernels are single-head')
+            if gat_dropout != 0.0:
+                raise NotImplementedError('gat_sigmoid with gat_dropout > 0: the dropout kernels weight by the softmax')
         self.node_types = list(pyg_data.node_types)
         self.edge_types = [tuple(e) for e in pyg_data.edge_types]
         self.schema = GraphSchema(self.node_types, self.edge_types)
@@ -323,7 +339,7 @@ class HeteroGNN(nn.Module):
         self.hidden_logical = cl = int(hidden_channels)
         hidden_channels = 128
         self.hidden = hidden_channels
-        self.negative_slope, self.temperature = 0.2, 1.0          # conv.py:43,50 defaults (model.py:40-42)
+        self.negative_slope, self.temperature = 0.2, gat_temperature      # conv.py:43,50 (model.py:40-42 passes neither: 0.2, 1)
         self.rel_fields = REL_FIELDS if gnn_backbone == 'GAT' else SagePack.FIELDS
         self.live_rel, self.live_types = sc.live_relations(num_layers, 'SNP')
         self.live_packs = nn.ModuleList()
@@ -369,6 +385,11 @@ class HeteroGNN(nn.Module):
             for hd in range(gat_num_head):
                 hm[hd, hd * (cl // gat_num_head):(hd + 1) * (cl // gat_num_head)] = 1.0
             self.register_buffer('head_mask', hm, persistent=False)
+        if self.gat_sigmoid:
+            # the fold moves FC_output's constant c out of the messages as c * sum_j alpha_ij = c, and the gates do not sum to 1: the
+            # gated model takes the unfolded route, as a dropping step does (_dropout).  OPEN: keeping the fold by having the forward
+            # emit sum_j g_e per row (gamma would be scaled by it in the transform) -- DESIGN.md section 8.
+            self.fold_fc = False
         if self.fold_fc:
             mlp_of = {'SNP': 0, 'Gene': 1}
             order = self.live_packs[0].rel_ids
@@ -657,6 +678,13 @@ class HeteroGNN(nn.Module):
             h = {sc.node_types[t]: o for t, o in zip(tys, outs)}
         return h, []
 
+    def _edge_weights(self, batch: SampledBatch, l: int, stat, e_edge):
+        """The weight every edge's message carried, from what the aggregate saved: the softmax's alpha (kgw_edge_alpha) or, gated,
+        sigmoid(e / T) element-wise from the stored logits."""
+        if self.gat_sigmoid:
+            return torch.sigmoid(e_edge[:int(batch.meta.n_edges[l - 1])] * (1.0 / self.temperature))
+        return ops.edge_alpha(batch, l, stat, e_edge, self.temperature)
+
     def set_dropout_word(self, word: int):
         """The word of the NEXT steps' attention-dropout masks (``dropout_word(seed, epoch, batch)``): one fill of the resident
         tensor, no synchronisation."""
@@ -712,9 +740,9 @@ class HeteroGNN(nn.Module):
             fused = self.aggr in ('sum', 'mean')
             Z, stat, e_edge = ops.gat_aggregate(batch, l, H, U, V, self.negative_slope, self.temperature,
                                                 relu_input=((l > 1 or folded) and fused), zbuf=zws, logit_bias=kap,
-                                                dropout=dropout)
+                                                dropout=dropout, sigmoid_gate=self.gat_sigmoid)
             if want_attention:
-                attn.append(ops.edge_alpha(batch, l, stat, e_edge, self.temperature))
+                attn.append(self._edge_weights(batch, l, stat, e_edge))
             if not fused:
                 # 'min' / 'max' over relations: per-relation outputs (lin_src + bias, conv.py:138-190) as one batched
                 # product per destination type, then the reduction over the relation axis and the ReLU (model.py:74-75)
@@ -828,7 +856,8 @@ class HeteroGNN(nn.Module):
         """Both layers over EVERY relation and every row of a full-graph block (no structural pruning), the way the
         reference runs a batch (kgwas/model.py:64-75): returns (final x_dict, [per layer: per-edge attention of the whole
         block, local edge order]).  ``raw``: the export's variant (kgwas/utils.py:446-461) -- raw leaky_relu logits as
-        message weights (conv.py:221-228) and no ReLU between the layers (utils.py:460)."""
+        message weights (conv.py:221-228) and no ReLU between the layers (utils.py:460).  A gated model (``gat_sigmoid``) weights
+        by its gates there too and returns them: conv.py:219-220 takes the sigmoid branch whatever return_raw_attention_weights says."""
         sc, m, C = self.schema, batch.meta, self.hidden
         dev = self.lin.weight.device
         h = self._embed_all(batch, batch.x_dict)
@@ -848,8 +877,10 @@ class HeteroGNN(nn.Module):
                         raise RuntimeError(f'layer {l}: node type {name!r} has no layer-{l - 1} state')
                     parts.append(h[name][:ns])
             H = torch.cat(parts, 0)
-            Z, stat, e_edge = ops.gat_aggregate(batch, l, H, U, V, self.negative_slope, self.temperature, raw_weights=raw)
-            per_layer.append(e_edge if raw else ops.edge_alpha(batch, l, stat, e_edge, self.temperature))
+            gate = self.gat_sigmoid
+            Z, stat, e_edge = ops.gat_aggregate(batch, l, H, U, V, self.negative_slope, self.temperature, raw_weights=raw and not gate,
+                                                sigmoid_gate=gate)
+            per_layer.append(e_edge if (raw and not gate) else self._edge_weights(batch, l, stat, e_edge))
             h_next = {}
             for t, name in enumerate(sc.node_types):
                 n, R = int(m.lay_rows[l - 1][t]), int(sc.R_dst[t])

@@ -460,7 +460,7 @@ def _set_dropout(a: KgwLayerArgs, dropout):
 class _GatAggregate(torch.autograd.Function):
     @staticmethod
     def forward(ctx, H, U, V, batch, layer, neg_slope, inv_temp, raw_weights=False, relu_input=False, zbuf=None, lbias=None,
-                dropout=None):
+                dropout=None, gate=False):
         dg, m = batch.dg, batch.meta
         NT = dg.schema.NT
         z_rows = int(m.z_base[layer - 1][NT])
@@ -491,7 +491,10 @@ class _GatAggregate(torch.autograd.Function):
             a.logit_bias = _p(lbias)
         ctx.has_lbias = lbias is not None
         a.flags = 1 if raw_weights else 0          # KGW_F_RAW_WEIGHTS
+        if gate:
+            a.flags |= _lib.KGW_F_SIGMOID_GATE     # weights sigmoid(e / T), no softmax (the rule: kgwgate_weight in kgwas_hip.h)
         ctx.raw_weights = raw_weights
+        ctx.gate = gate
         ctx.relu_input = relu_input
         ctx.dropout = dropout                      # (forward and backward hand the kernels the same word, threshold and scale)
         _set_dropout(a, dropout)
@@ -516,7 +519,7 @@ class _GatAggregate(torch.autograd.Function):
         if ctx.raw_weights:
             raise RuntimeError('raw-logit aggregation (attention export) is inference only')
         if dZ is None:
-            return (None,) * 12
+            return (None,) * 13
         H, U, V, Z, stat, e_edge = ctx.saved_tensors
         batch, layer = ctx.batch, ctx.layer
         dg, m = batch.dg, batch.meta
@@ -560,6 +563,8 @@ class _GatAggregate(torch.autograd.Function):
             da_src = torch.empty(max(n_src, 1), 2 * ld_da, device=dev)   # [node row, (d a_src | d a_dst) by relation id]
             a.da_src = _p(da_src)
         a.flags = 2 if ctx.relu_input else 0       # KGW_F_RELU_INPUT: fold the ReLU that produced H into dH
+        if ctx.gate:
+            a.flags |= _lib.KGW_F_SIGMOID_GATE     # (read by the dst-major pass; the src-major pass ignores it)
         pieces = riders and DUV_PIECES is not None
         if pieces:
             a.flags |= 4                           # KGW_F_DUV_PIECES: dU / dV stay UNWRITTEN, their consumers add the pieces
@@ -587,7 +592,7 @@ class _GatAggregate(torch.autograd.Function):
             dU, dV = torch.zeros_like(U), torch.zeros_like(V)
         if ctx.has_lbias and not n_src:                  # (no source rows: the launch above did not run)
             _lib.check(L.kgw_relation_sums(C.byref(a), _p(da_dst), _p(dlb), _lib.stream_ptr()), 'kgw_relation_sums')
-        return dH[:n_src], dU, dV, None, None, None, None, None, None, None, dlb, None
+        return dH[:n_src], dU, dV, None, None, None, None, None, None, None, dlb, None, None
 
 
 class _GatAggregateHeads(torch.autograd.Function):
@@ -678,7 +683,7 @@ def aggregate_workspace(batch, layer: int, device) -> torch.Tensor:
 def gat_aggregate(batch, layer: int, H: torch.Tensor, U: torch.Tensor, V: torch.Tensor,
                   neg_slope: float = 0.2, temperature: float = 1.0, raw_weights: bool = False,
                   relu_input: bool = False, zbuf: torch.Tensor = None, logit_bias: torch.Tensor = None, dropout=None,
-                  heads: int = 1):
+                  heads: int = 1, sigmoid_gate: bool = False):
     """Z[i, r] = sum_j softmax_j(leaky_relu(<H_src[j], u_r> + <H_dst[i], v_r>) / T) H_src[j] for every live relation
     of the layer.  H [n_src_rows,128]: layer input, type-major (``meta.src_base``; a destination node is row i of
     its own type's block); U, V [n_rels,128] by relation id.  Returns (Z [z_rows,128], stat [z_rows,2] =
@@ -699,8 +704,25 @@ def gat_aggregate(batch, layer: int, H: torch.Tensor, U: torch.Tensor, V: torch.
     ``heads`` = NH in (2, 4): NH attention heads over the same H (KgwLayerArgs.n_heads).  U, V are [NH, n_rels, 128] and the
     result is (Z [NH, z_rows, 128], stat [NH, z_rows, 2], e_edge [NH, n_edges]): plane h is what a single-head call with
     (U[h], V[h]) returns, and every gathered row serves all NH heads.  Not with ``raw_weights``, ``logit_bias``, ``dropout``,
-    ``zbuf`` or the SNP-sharded mode."""
+    ``zbuf`` or the SNP-sharded mode.
+    ``sigmoid_gate``: Z[i, r] = sum_j g_ij H_src[j] with g = sigmoid(e / T) per edge -- the reference GATConv's ``sigmoid_gat``
+    (kgwas/conv.py:49,219-220): independent gates, no softmax, nothing normalised by the row's degree (KGW_F_SIGMOID_GATE; the rule:
+    kgwgate_weight in include/kgwas_hip.h).  Differentiable; takes ``relu_input``, ``logit_bias`` and ``zbuf`` as the softmax does.
+    stat is (0, 1) on visited rows and e_edge the leaky_relu logit, as with ``raw_weights``.  Not with ``heads`` != 1, ``dropout``,
+    ``raw_weights`` or the SNP-sharded mode."""
     xchg = getattr(batch, 'exchange', None)
+    if sigmoid_gate:
+        if raw_weights:
+            raise ValueError('sigmoid_gate and raw_weights both replace the softmax: one of them')
+        what = [n for n, v in ((f'heads={heads}', heads != 1), ('dropout', dropout is not None),
+                               ('the SNP-sharded mode', xchg is not None)) if v]
+        if what:
+            raise NotImplementedError(f'sigmoid_gate together with {", ".join(what)} is not built')
+        if not _lib.has_sigmoid_gate():
+            raise _lib.KgwasHipError('this libkgwas_hip.so predates KGW_F_SIGMOID_GATE')
+        stat, e_edge, Z = _GatAggregate.apply(H, U, V, batch, layer, float(neg_slope), 1.0 / float(temperature), False,
+                                              relu_input, zbuf, logit_bias, None, True)
+        return Z, stat, e_edge
     if heads != 1:
         if heads not in (2, 4):
             raise NotImplementedError(f'heads={heads}: the aggregate kernels are built for 1, 2 and 4 heads')
