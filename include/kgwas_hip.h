@@ -241,8 +241,8 @@ typedef struct KgwLayerArgs {
 
 int kgw_version(void);
 const char* kgw_status_string(int status);
-/* sizeof() of the ABI structs in the order Graph, BatchMeta, Chunk, BatchBuf, LayerArgs -- lets a
- * binding verify its mirror structs.                                                          */
+/* sizeof() of the ABI structs in the order Graph, BatchMeta, Chunk, BatchBuf, LayerArgs, TnJob, GradSrc, EdgeAttr -- lets a
+ * binding verify its mirror structs (the first n; a library that predates an entry leaves it untouched).   */
 int kgw_struct_sizes(int64_t* out, int n);
 
 /* Replaces: NeighborLoader.__next__ (kgwas/kgwas.py:99-113,129; torch_sparse/pyg_lib
@@ -418,6 +418,46 @@ int kgw_scatter_relu_rows(const float* g, const int32_t* g2l, const float* h, in
 /* alpha_e = exp(e - max)/den per local edge of one layer (attention export,
  * kgwas/conv.py:192-196; kgwas/utils.py:446-461).                                             */
 int kgw_edge_alpha(const KgwLayerArgs* args, float* alpha_out, kgw_stream_t stream);
+
+/* Edge attributes: GATConv(edge_dim = D) (kgwas/conv.py:46,95-101,207-215; the reference's HeteroGNN never passes it and its
+ * load_kg keeps no edge evidence, so like the dropout and the gate this is an EXTENSION, off by default).  Every edge of an
+ * attributed relation r carries D floats; a bias-free lin_edge [C, D] maps them to the hidden width and <lin_edge(attr_e), att_edge>
+ * joins the attention logit BEFORE the LeakyReLU.  The messages do not change.  Re-associated the way u_r and v_r are:
+ *      w_r      = lin_edge.weight^T att_edge                 in R^D          (formed by the caller; w [n_rels][8], stride 8)
+ *      t_e      = sum_{d < D} A_r[p(e)][d] w_r[d]            fp32, fmaf, ascending d, starting from 0
+ *      pre_e    = <x_j, u_r> + <x_i, v_r> (+ kappa_r) + t_e
+ *      e_e      = leaky_relu(pre_e), then the softmax over the row of e / T, or (KGW_F_RAW_WEIGHTS) the raw weights -- unchanged
+ *      d w_r[d] = sum_{e in r} d pre_e A_r[p(e)][d]          (no gradient to the attributes)
+ * A_r [E_r][D]: row p belongs to entry p of relation r's dst-major CSR (the order of g_col: KgwGraph.col_off[r] + p; parallel edges
+ * keep their own rows).  A relation without attributes (attr_off[r] < 0) has t_e = 0.  1 <= D <= 8, one D for all relations.
+ * Where a local edge sits in the CSR is read from its chunk: gpos - col_off[rel] + (e - e0).  The chunks of a segment that a finite
+ * fan-out DREW carry no position (gpos = -1): their terms are written as quiet NaN, so that misuse cannot pass silently.
+ * The softmax still sums to one, and the backward kernels do not change: kgw_gat_aggregate_bwd_dst re-forms the weights from the
+ * STORED logits and its adp[e] = (alpha_e, d pre_e) already holds the gradient of t_e.                                             */
+typedef struct KgwEdgeAttr {
+    const float* attr;               /* [sum of E_r over the attributed relations][dim], relation after relation               */
+    int64_t attr_off[KGW_MAX_RELS];  /* first ROW of relation r inside attr; -1 = the relation has no attributes               */
+    int32_t dim, pad_;               /* D                                                                                      */
+    const float* w;                  /* [n_rels][8] w_r, zero beyond dim (rows of unattributed relations are not read)         */
+    float* term;                     /* kgw_edge_term_fwd: [n_edges] t_e per local edge of the layer                           */
+    const float* d_term;             /* kgw_edge_term_bwd: gradient of t_e, element e at d_term[e * d_term_stride] --          */
+    int64_t d_term_stride;           /*   KgwLayerArgs.adp + 1 with stride 2 reads d pre_e in place                            */
+    float* d_w;                      /* kgw_edge_term_bwd: [n_rels][8]; exact zeros for relations the layer does not compute,  */
+                                     /*   for unattributed ones and beyond dim                                                 */
+    float* workspace;                /* kgw_edge_term_bwd: kgw_edge_term_workspace_floats(args) floats                         */
+} KgwEdgeAttr;
+/* term[e] for every local edge of the layer (0.0f on relations without attributes or not live in the layer).  Reads of args:
+ * layer, n_chunks, graph_host, meta_dev, chunks.  dim outside [1, 8]: KGW_E_RANGE.  One launch.                                 */
+int kgw_edge_term_fwd(const KgwLayerArgs* args, const KgwEdgeAttr* ea, kgw_stream_t stream);
+/* d_w from d_term and the attribute rows.  No float atomics, a fixed two-level order (per-chunk sums over a wavefront's fixed tree,
+ * then one block per relation over its chunks, as part_du -> k_duv_fold): reruns are bit-identical.  Reads of args as above plus
+ * n_multi_hops and seg_chptr.  Two launches.                                                                                   */
+int kgw_edge_term_bwd(const KgwLayerArgs* args, const KgwEdgeAttr* ea, kgw_stream_t stream);
+int64_t kgw_edge_term_workspace_floats(const KgwLayerArgs* args);
+/* kgw_gat_aggregate_fwd with pre_e += term[e] (term: [n_edges], kgw_edge_term_fwd's): the softmax route, or with KGW_F_RAW_WEIGHTS
+ * the raw weights of the attention export.  Hub rows, partial records and the combine are those of the plain call.  With
+ * KGW_F_SIGMOID_GATE, n_heads > 1, drop_word_dev or partial_rels: KGW_E_UNSUPPORTED -- before any launch.                        */
+int kgw_gat_aggregate_fwd_eterm(const KgwLayerArgs* args, const float* term, kgw_stream_t stream);
 
 /* Where a gradient tensor's values are when its producer left the last reduction to the optimiser's launch
  * (kgw_adam_fused): DIRECT = in the gradient tensor itself; the other kinds = per-block partial sums in a workspace, added by

@@ -104,6 +104,12 @@ class KgwLayerArgs(C.Structure):
     ]
 
 
+class KgwEdgeAttr(C.Structure):
+    _fields_ = [('attr', C.c_void_p), ('attr_off', C.c_int64 * KGW_MAX_RELS), ('dim', C.c_int32), ('pad_', C.c_int32),
+                ('w', C.c_void_p), ('term', C.c_void_p), ('d_term', C.c_void_p), ('d_term_stride', C.c_int64),
+                ('d_w', C.c_void_p), ('workspace', C.c_void_p)]
+
+
 class KgwTnJob(C.Structure):
     _fields_ = [('A', C.c_void_p), ('lda', C.c_int64), ('B', C.c_void_p), ('ldb', C.c_int64), ('rows', C.c_int64),
                 ('C', C.c_void_p), ('ldc', C.c_int64), ('colsum_a', C.c_void_p), ('colsum_ld', C.c_int64),
@@ -167,6 +173,7 @@ class KgwFoldArgs(C.Structure):
 EXPORTS = ['kgw_version', 'kgw_status_string', 'kgw_struct_sizes', 'kgw_sample_batch', 'kgw_sample_batch_parts', 'kgw_sample_batch_fanout', 'kgw_sampler_scan_ints', 'kgw_segments_copy',
            'kgw_softmax_pack', 'kgw_softmax_merge', 'kgw_scatter_rows', 'kgw_linear_splitk', 'kgw_linear_splitk_workspace_floats', 'kgw_linear_splitk_ind', 'kgw_ind_colsum', 'kgw_linear_splitk_multi', 'kgw_ind_colsum_multi', 'kgw_fold_fwd', 'kgw_fold_bwd', 'kgw_relation_sums',
            'kgw_gat_aggregate_fwd', 'kgw_gat_aggregate_bwd_dst', 'kgw_gat_aggregate_bwd_src',
+           'kgw_edge_term_fwd', 'kgw_edge_term_bwd', 'kgw_edge_term_workspace_floats', 'kgw_gat_aggregate_fwd_eterm',
            'kgw_gather_rows', 'kgw_gather_rows_multi', 'kgw_scatter_relu_rows', 'kgw_scatter_relu_rows_workspace_floats', 'kgw_edge_alpha', 'kgw_debug_reduce', 'kgw_debug_reduce8', 'kgw_tn_gemm', 'kgw_tn_gemm_ex', 'kgw_tn_gemm_multi', 'kgw_tn_gemm_workspace_floats', 'kgw_tn_gemm_partial', 'kgw_tn_gemm_multi_partial', 'kgw_tn_split', 'kgw_tn_direct_rows', 'kgw_param_tail', 'kgw_tn_reduce_launch', 'kgw_tn_gemm_partial_ride', 'kgw_transform_bwd_ex', 'kgw_mlp2_bwd_first_partial', 'kgw_mlp2_bwd_first_packed', 'kgw_adam_fused', 'kgw_gemm3_partial', 'kgw_gemm3_flip', 'kgw_transform_bwd', 'kgw_grad_finish',
            'kgw_linear', 'kgw_mlp2_fwd', 'kgw_mlp2w_fwd', 'kgw_mlp2_bwd_first', 'kgw_mlp2_bwd_first_workspace_floats', 'kgw_gemm3', 'kgw_gemm3_riders', 'kgw_gemm3_rider_blocks', 'kgw_gemm3_pack', 'kgw_gemm3_packed_bytes', 'kgw_gemm3_workspace_floats', 'kgw_adam', 'kgw_adam_notick', 'kgw_relvec_fwd', 'kgw_relvec_bwd', 'kgw_relvec_bwd_acc', 'kgw_relvec_fwd_multi', 'kgw_relvec_bwd_multi', 'kgw_wmse_fwd', 'kgw_wmse_bwd', 'kgw_readout_wmse_fwd', 'kgw_readout_wmse_bwd', 'kgw_readout_wmse_train', 'kgw_readout_wmse_train_parts', 'kgw_readout_train_fold', 'kgw_readout_mt_pred', 'kgw_readout_mt_pred_bwd', 'kgw_readout_wmse_mt_fwd', 'kgw_readout_wmse_mt_bwd',
            'kgw_readout_wmse_mt_train', 'kgw_readout_wmse_mtw_fwd', 'kgw_readout_wmse_mtw_bwd', 'kgw_readout_wmse_mtw_train',
@@ -228,6 +235,16 @@ def lib():
     L.kgw_gather_rows_multi.argtypes = [C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_int32,
                                         C.POINTER(C.c_void_p), C.c_void_p]
     L.kgw_edge_alpha.argtypes = [C.POINTER(KgwLayerArgs), C.c_void_p, C.c_void_p]
+    if hasattr(L, 'kgw_edge_term_fwd'):             # (absent from an older library named by KGW_LIB_PATH for an A/B run)
+        L.kgw_edge_term_fwd.argtypes = [C.POINTER(KgwLayerArgs), C.POINTER(KgwEdgeAttr), C.c_void_p]
+        L.kgw_edge_term_bwd.argtypes = [C.POINTER(KgwLayerArgs), C.POINTER(KgwEdgeAttr), C.c_void_p]
+        L.kgw_edge_term_workspace_floats.argtypes = [C.POINTER(KgwLayerArgs)]
+        L.kgw_edge_term_workspace_floats.restype = C.c_int64
+        L.kgw_gat_aggregate_fwd_eterm.argtypes = [C.POINTER(KgwLayerArgs), C.c_void_p, C.c_void_p]
+        s8 = (C.c_int64 * 8)()
+        L.kgw_struct_sizes(s8, 8)
+        if s8[7] != C.sizeof(KgwEdgeAttr):
+            raise KgwasHipError(f'ABI struct size mismatch: KgwEdgeAttr library {s8[7]} vs binding {C.sizeof(KgwEdgeAttr)}')
     L.kgw_debug_reduce.argtypes = [C.c_void_p] * 5
     L.kgw_debug_reduce8.argtypes = [C.c_void_p] * 3
     L.kgw_tn_gemm_workspace_floats.restype = C.c_int64
@@ -348,6 +365,12 @@ def has_sigmoid_gate() -> bool:
     a = KgwLayerArgs()
     a.flags = KGW_F_SIGMOID_GATE | 1
     return lib().kgw_gat_aggregate_fwd(C.byref(a), None) == KGW_E_UNSUPPORTED
+
+
+def has_edge_attr() -> bool:
+    """Does the loaded library have the edge-attribute entry points (kgw_edge_term_fwd, kgw_edge_term_bwd,
+    kgw_gat_aggregate_fwd_eterm)?  An older library named by KGW_LIB_PATH for an A/B run lacks the symbols."""
+    return hasattr(lib(), 'kgw_gat_aggregate_fwd_eterm')
 
 
 def check(status: int, what: str):

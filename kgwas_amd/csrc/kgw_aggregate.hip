@@ -91,6 +91,7 @@ struct AggPtrs {
     const uint64_t* drop_word;    // attention dropout (KgwLayerArgs.drop_word_dev; NULL = off): the 64-bit word of the step,
     uint32_t drop_thresh;         // floor(p * 2^32) and
     float drop_scale;             // 1 / (1 - p)
+    const float* term;            // k_agg_fwd<.., ETERM>: [n_edges] logit term of every local edge (edge attributes; else unread)
 };
 
 // Attention dropout (include/kgwas_hip.h, kgwdrop_keep): the factor m'(e) of local edge e's message -- drop_scale if the edge is
@@ -139,11 +140,13 @@ __device__ __forceinline__ KgwChunk load_chunk(const KgwChunk* chunks, int c) {
 // the running sum `s` and the logits stay those of the undropped softmax.  With m' == 1.0f the products are the plain values.
 // GATE (with RAW: the same no-softmax route): the weight is the sigmoid gate of the logit (kgwgate_weight, include/kgwas_hip.h)
 // instead of the logit itself; a padding edge weighs exactly 0.
-template <int G, bool RAW, bool DROP, bool GATE = false>
+// ETERM: edge attributes (include/kgwas_hip.h, KgwEdgeAttr) -- termv holds the logit term of edge `lane` of the 64-edge block,
+// loaded coalesced beside colv; it is added to the pre-activation logit of its edge before the leaky ReLU.
+template <int G, bool RAW, bool DROP, bool GATE = false, bool ETERM = false>
 __device__ __forceinline__ void fwd_group(const float4* __restrict__ Hb4, int colv, int q0, int hn, int nb,
                                           int half, int hl, const float4& u4, float ad, float slope,
                                           float inv_temp, float& m, float& s, float4& acc, float& ev,
-                                          const DropCtx& D, int eb) {
+                                          const DropCtx& D, int eb, float termv = 0.f) {
     float4 x[G];
     bool valid[G];
 #pragma unroll
@@ -159,6 +162,7 @@ __device__ __forceinline__ void fwd_group(const float4* __restrict__ Hb4, int co
 #pragma unroll
     for (int p = 0; p < G; ++p) {
         float d = kgw_half_allsum(dot4(x[p], u4)) + ad;
+        if (ETERM) d += __shfl(termv, valid[p] ? half * hn + q0 + p : 0, 64);      // (every lane computes every edge's logit)
         d = d > 0.f ? d : d * slope;
         ev = (hl == q0 + p) ? d : ev;              // lane (half, hl) keeps the logit of edge half*hn+hl
         if (RAW) { t[p] = valid[p] ? (GATE ? kgwgate_weight(d, inv_temp) : d) : 0.f; continue; }
@@ -193,16 +197,17 @@ __device__ __forceinline__ void grp8_load(const float4* __restrict__ Hb4, int co
     }
 }
 
-template <bool RAW, bool DROP, bool GATE = false>
+template <bool RAW, bool DROP, bool GATE = false, bool ETERM = false>
 __device__ __forceinline__ void fwd_grp8_compute(const float4 (&x)[8], int q0, int hn, int nb, int half, int hl,
                                                  const float4& u4, float ad, float slope, float inv_temp, float& m, float& s,
-                                                 float4& acc, float& ev, const DropCtx& D, int eb) {
+                                                 float4& acc, float& ev, const DropCtx& D, int eb, float termv = 0.f) {
     float part[8];
 #pragma unroll
     for (int p = 0; p < 8; ++p) part[p] = dot4(x[p], u4);
     const int pm = hl & 7, qm = q0 + pm;
     const bool valid = (qm < hn) && (half * hn + qm < nb);
     float d = kgw_half_reduce8(part, hl) + ad;                 // logit of edge q0 + (hl & 7)
+    if (ETERM) d += __shfl(termv, valid ? half * hn + qm : 0, 64);      // the lane that owns the edge takes its term
     d = d > 0.f ? d : d * slope;
     ev = ((hl >> 3) == (q0 >> 3) && hl == qm) ? d : ev;        // lane (half, q) keeps the logit of edge half*hn + q
     float w;
@@ -225,23 +230,24 @@ __device__ __forceinline__ void fwd_grp8_compute(const float4 (&x)[8], int q0, i
 
 // Eight edges per half with the transposed reduction (kgw_half_reduce8): the lane with (hl & 7) == p owns edge q0 + p --
 // its logit, its softmax weight -- and hands the weight to the other lanes of its 8-lane group with one swizzle.
-template <bool RAW, bool DROP, bool GATE = false>
+template <bool RAW, bool DROP, bool GATE = false, bool ETERM = false>
 __device__ __forceinline__ void fwd_group8(const float4* __restrict__ Hb4, int colv, int q0, int hn, int nb,
                                            int half, int hl, const float4& u4, float ad, float slope,
                                            float inv_temp, float& m, float& s, float4& acc, float& ev,
-                                           const DropCtx& D, int eb) {
+                                           const DropCtx& D, int eb, float termv = 0.f) {
     float4 x[8];
     grp8_load(Hb4, colv, q0, hn, nb, half, hl, x);
-    fwd_grp8_compute<RAW, DROP, GATE>(x, q0, hn, nb, half, hl, u4, ad, slope, inv_temp, m, s, acc, ev, D, eb);
+    fwd_grp8_compute<RAW, DROP, GATE, ETERM>(x, q0, hn, nb, half, hl, u4, ad, slope, inv_temp, m, s, acc, ev, D, eb, termv);
 }
 
 // PIPE: software pipelining inside a chunk.  A chunk of n edges used to cost one memory round trip for the column ids of
 // every 64 edges plus one per group of 16 rows (a 256-edge chunk of a hub row: 20 dependent round trips, and the longest
 // chunks set the kernel's tail -- halving KGW_CHUNK alone took 64 -> 58 us); with PIPE the next block's column ids and
 // the next group's rows are requested before the current group is reduced.
-template <bool RAW, bool PIPE, bool DROP, bool GATE = false>
+template <bool RAW, bool PIPE, bool DROP, bool GATE = false, bool ETERM = false>
 __global__ void __launch_bounds__(KGW_BLK) k_agg_fwd(LayerTab T, AggPtrs P, float slope, float inv_temp) {
     static_assert(!(RAW && DROP), "attention dropout applies to softmax weights only");
+    static_assert(!ETERM || !(DROP || GATE), "edge attributes are built for the softmax and the raw-weights routes");
     static_assert(!GATE || RAW, "the sigmoid gate takes the no-softmax route: partial records (0, 1), den = 1");
     const int lane = kgw_lane(), half = lane >> 5, hl = lane & 31;
     const int nw = gridDim.x * 4;
@@ -267,15 +273,22 @@ __global__ void __launch_bounds__(KGW_BLK) k_agg_fwd(LayerTab T, AggPtrs P, floa
         float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
         const int n = ck.e1 - ck.e0;
         int colv_next = (PIPE && lane < min(64, n)) ? P.col_local[ck.e0 + lane] : 0;
+        float termv_next = (ETERM && PIPE && lane < min(64, n)) ? P.term[ck.e0 + lane] : 0.f;
         for (int b = 0; b < n; b += 64) {
             const int nb = min(64, n - b);
             const int hn = (nb + 1) >> 1;
             int colv;
+            float termv = 0.f;
             if (PIPE) {
                 colv = colv_next;
                 colv_next = (b + 64 < n && lane < min(64, n - b - 64)) ? P.col_local[ck.e0 + b + 64 + lane] : 0;
+                if (ETERM) {
+                    termv = termv_next;
+                    termv_next = (b + 64 < n && lane < min(64, n - b - 64)) ? P.term[ck.e0 + b + 64 + lane] : 0.f;
+                }
             } else {
                 colv = (lane < nb) ? P.col_local[ck.e0 + b + lane] : 0;
+                if (ETERM) termv = (lane < nb) ? P.term[ck.e0 + b + lane] : 0.f;
             }
             float ev = 0.f;
             int q0 = 0;
@@ -286,22 +299,22 @@ __global__ void __launch_bounds__(KGW_BLK) k_agg_fwd(LayerTab T, AggPtrs P, floa
                     const int q1 = q0 + 8;
                     const bool more1 = hn - q1 > 4;
                     if (more1) grp8_load(Hb4, colv, q1, hn, nb, half, hl, x1);
-                    fwd_grp8_compute<RAW, DROP, GATE>(x0, q0, hn, nb, half, hl, u4, ad, slope, inv_temp, m, s, acc, ev, D, ck.e0 + b);
+                    fwd_grp8_compute<RAW, DROP, GATE, ETERM>(x0, q0, hn, nb, half, hl, u4, ad, slope, inv_temp, m, s, acc, ev, D, ck.e0 + b, termv);
                     q0 = q1;
                     if (!more1) break;
                     const int q2 = q1 + 8;
                     const bool more2 = hn - q2 > 4;
                     if (more2) grp8_load(Hb4, colv, q2, hn, nb, half, hl, x0);
-                    fwd_grp8_compute<RAW, DROP, GATE>(x1, q1, hn, nb, half, hl, u4, ad, slope, inv_temp, m, s, acc, ev, D, ck.e0 + b);
+                    fwd_grp8_compute<RAW, DROP, GATE, ETERM>(x1, q1, hn, nb, half, hl, u4, ad, slope, inv_temp, m, s, acc, ev, D, ck.e0 + b, termv);
                     q0 = q2;
                     if (!more2) break;
                 }
             }
             for (; q0 < hn;) {
                 const int rem = hn - q0;
-                if (rem > 4)      { fwd_group8<RAW, DROP, GATE>(Hb4, colv, q0, hn, nb, half, hl, u4, ad, slope, inv_temp, m, s, acc, ev, D, ck.e0 + b); q0 += 8; }
-                else if (rem > 2) { fwd_group<4, RAW, DROP, GATE>(Hb4, colv, q0, hn, nb, half, hl, u4, ad, slope, inv_temp, m, s, acc, ev, D, ck.e0 + b); q0 += 4; }
-                else              { fwd_group<2, RAW, DROP, GATE>(Hb4, colv, q0, hn, nb, half, hl, u4, ad, slope, inv_temp, m, s, acc, ev, D, ck.e0 + b); q0 += 2; }
+                if (rem > 4)      { fwd_group8<RAW, DROP, GATE, ETERM>(Hb4, colv, q0, hn, nb, half, hl, u4, ad, slope, inv_temp, m, s, acc, ev, D, ck.e0 + b, termv); q0 += 8; }
+                else if (rem > 2) { fwd_group<4, RAW, DROP, GATE, ETERM>(Hb4, colv, q0, hn, nb, half, hl, u4, ad, slope, inv_temp, m, s, acc, ev, D, ck.e0 + b, termv); q0 += 4; }
+                else              { fwd_group<2, RAW, DROP, GATE, ETERM>(Hb4, colv, q0, hn, nb, half, hl, u4, ad, slope, inv_temp, m, s, acc, ev, D, ck.e0 + b, termv); q0 += 2; }
             }
             const int i = half * hn + hl;
             if (hl < hn && i < nb) P.e_edge[ck.e0 + b + i] = ev;
@@ -1157,6 +1170,7 @@ __global__ void __launch_bounds__(KGW_BLK) k_edge_alpha(LayerTab T, AggPtrs P, f
 }
 
 #include "kgw_aggregate_heads.h"      // n_heads = 2, 4: the same mapping with NH planes of every head-carrying array
+#include "kgw_edge_attr.h"            // edge attributes: the per-edge logit term and the gradient of w_r
 
 // ---- host side -----------------------------------------------------------------------------------
 int build_tab(const KgwLayerArgs* a, LayerTab* T) {
@@ -1214,6 +1228,7 @@ AggPtrs build_ptrs(const KgwLayerArgs* a) {
     P.meta = a->meta_dev; P.layer = a->layer;
     P.lbias = a->logit_bias;
     P.drop_word = a->drop_word_dev; P.drop_thresh = a->drop_thresh; P.drop_scale = a->drop_scale;
+    P.term = nullptr;
     return P;
 }
 
@@ -1241,6 +1256,8 @@ template __global__ void k_agg_bwd_dst<false, false>(LayerTab, AggPtrs, float, f
 template __global__ void k_agg_bwd_dst<false, true>(LayerTab, AggPtrs, float, float);
 template __global__ void k_agg_fwd<true, true, false, true>(LayerTab, AggPtrs, float, float);
 template __global__ void k_agg_bwd_dst<false, false, true>(LayerTab, AggPtrs, float, float);
+template __global__ void k_agg_fwd<false, true, false, false, true>(LayerTab, AggPtrs, float, float);
+template __global__ void k_agg_fwd<true, true, false, false, true>(LayerTab, AggPtrs, float, float);
 #endif
 
 inline int grid_for_waves(int64_t n_waves) {
@@ -1379,6 +1396,88 @@ extern "C" int kgw_gat_aggregate_fwd(const KgwLayerArgs* a, kgw_stream_t stream_
     KGW_LAUNCH_CHECK();
     if (a->ev_after) KGW_HIP(hipEventRecord((hipEvent_t)a->ev_after, st));
     if (a->multi && a->multi_cap > 0) {     // hub rows: the number of multi-chunk segments is read on the device
+        k_agg_fwd_combine<<<grid_for_waves(a->multi_cap < 1024 ? a->multi_cap : 1024), KGW_BLK, 0, st>>>(T, P, a->n_multi_hops);
+        KGW_LAUNCH_CHECK();
+    }
+    return KGW_OK;
+}
+
+// ---- edge attributes (KgwEdgeAttr) -------------------------------------------------------------------------------------------
+namespace {
+int build_edge_tab(const KgwLayerArgs* a, const KgwEdgeAttr* ea, EdgeTab* E) {
+    const KgwGraph* G = a->graph_host;
+    if (!G) return KGW_E_NULL;
+    if (a->layer < 1 || a->layer > G->n_layers || G->n_rels > KGW_MAX_RELS) return KGW_E_RANGE;
+    E->n_rels = G->n_rels;
+    E->dim = ea->dim;
+    for (int r = 0; r < KGW_MAX_RELS; ++r) {
+        const bool in = r < G->n_rels;
+        E->col_off[r] = in ? G->col_off[r] : 0;
+        E->attr_off[r] = in ? ea->attr_off[r] : -1;
+        E->live[r] = in ? G->rel_live[a->layer - 1][r] : 0;
+    }
+    return KGW_OK;
+}
+}  // namespace
+
+extern "C" int kgw_edge_term_fwd(const KgwLayerArgs* a, const KgwEdgeAttr* ea, kgw_stream_t stream_) {
+    if (!a || !ea) return KGW_E_NULL;
+    if (ea->dim < 1 || ea->dim > 8) return KGW_E_RANGE;
+    if (a->n_chunks == 0) return KGW_OK;
+    if (!ea->attr || !ea->w || !ea->term || !a->chunks || !a->meta_dev) return KGW_E_NULL;
+    EdgeTab E;
+    if (int rc = build_edge_tab(a, ea, &E)) return rc;
+    k_edge_term<<<grid_for_waves(a->n_chunks), KGW_BLK, 0, (hipStream_t)stream_>>>(E, a->chunks, a->meta_dev, a->layer, ea->attr,
+                                                                                  ea->w, ea->term);
+    KGW_LAUNCH_CHECK();
+    return KGW_OK;
+}
+
+extern "C" int64_t kgw_edge_term_workspace_floats(const KgwLayerArgs* a) {
+    return a ? 8 * (int64_t)(a->n_chunks > 0 ? a->n_chunks : 1) : 0;
+}
+
+extern "C" int kgw_edge_term_bwd(const KgwLayerArgs* a, const KgwEdgeAttr* ea, kgw_stream_t stream_) {
+    if (!a || !ea) return KGW_E_NULL;
+    if (ea->dim < 1 || ea->dim > 8) return KGW_E_RANGE;
+    if (!ea->d_w || !a->graph_host) return KGW_E_NULL;
+    if (a->n_chunks > 0 && (!ea->attr || !ea->d_term || !ea->workspace || !a->chunks || !a->meta_dev || !a->seg_chptr)) return KGW_E_NULL;
+    if (ea->d_term_stride < 1) return KGW_E_RANGE;
+    EdgeTab E;
+    if (int rc = build_edge_tab(a, ea, &E)) return rc;
+    hipStream_t st = (hipStream_t)stream_;
+    if (a->n_chunks == 0) {          // an empty layer: nothing was aggregated
+        KGW_HIP(hipMemsetAsync(ea->d_w, 0, sizeof(float) * 8 * E.n_rels, st));
+        return KGW_OK;
+    }
+    k_edge_term_bwd<<<grid_for_waves(a->n_chunks), KGW_BLK, 0, st>>>(E, a->chunks, a->meta_dev, a->layer, ea->attr, ea->d_term,
+                                                                     ea->d_term_stride, ea->workspace);
+    KGW_LAUNCH_CHECK();
+    k_edge_term_bwd_fold<<<E.n_rels, KGW_BLK, 0, st>>>(E, a->meta_dev, a->seg_chptr, a->n_multi_hops, ea->workspace, ea->d_w);
+    KGW_LAUNCH_CHECK();
+    return KGW_OK;
+}
+
+extern "C" int kgw_gat_aggregate_fwd_eterm(const KgwLayerArgs* a, const float* term, kgw_stream_t stream_) {
+    if (!a) return KGW_E_NULL;
+    if (int rc = check_heads(a)) return rc;
+    if ((a->flags & KGW_F_SIGMOID_GATE) || a->n_heads > 1 || a->drop_word_dev || a->partial_rels) return KGW_E_UNSUPPORTED;
+    if (a->n_chunks == 0) return KGW_OK;
+    if (!term || !a->chunks || !a->col_local || !a->H || (!a->a_dst && !a->V) || !a->U || !a->Z || !a->stat || !a->e_edge || !a->part ||
+        !a->meta_dev)
+        return KGW_E_NULL;
+    LayerTab T;
+    if (int rc = build_tab(a, &T)) return rc;
+    AggPtrs P = build_ptrs(a);
+    P.term = term;
+    hipStream_t st = (hipStream_t)stream_;
+    if (a->ev_before) KGW_HIP(hipEventRecord((hipEvent_t)a->ev_before, st));
+    // (the forward plain, as kgw_gat_aggregate_fwd selects it)
+    if (P.raw) k_agg_fwd<true, false, false, false, true><<<grid_fine(a->n_chunks), KGW_BLK, 0, st>>>(T, P, a->neg_slope, a->inv_temp);
+    else       k_agg_fwd<false, false, false, false, true><<<grid_fine(a->n_chunks), KGW_BLK, 0, st>>>(T, P, a->neg_slope, a->inv_temp);
+    KGW_LAUNCH_CHECK();
+    if (a->ev_after) KGW_HIP(hipEventRecord((hipEvent_t)a->ev_after, st));
+    if (a->multi && a->multi_cap > 0) {
         k_agg_fwd_combine<<<grid_for_waves(a->multi_cap < 1024 ? a->multi_cap : 1024), KGW_BLK, 0, st>>>(T, P, a->n_multi_hops);
         KGW_LAUNCH_CHECK();
     }
@@ -1624,10 +1723,10 @@ extern "C" const char* kgw_status_string(int status) {
 
 extern "C" int kgw_struct_sizes(int64_t* out, int n) {
     if (!out) return KGW_E_NULL;
-    const int64_t v[7] = {(int64_t)sizeof(KgwGraph), (int64_t)sizeof(KgwBatchMeta), (int64_t)sizeof(KgwChunk),
+    const int64_t v[8] = {(int64_t)sizeof(KgwGraph), (int64_t)sizeof(KgwBatchMeta), (int64_t)sizeof(KgwChunk),
                           (int64_t)sizeof(KgwBatchBuf), (int64_t)sizeof(KgwLayerArgs), (int64_t)sizeof(KgwTnJob),
-                          (int64_t)sizeof(KgwGradSrc)};
-    for (int i = 0; i < n && i < 7; ++i) out[i] = v[i];
+                          (int64_t)sizeof(KgwGradSrc), (int64_t)sizeof(KgwEdgeAttr)};
+    for (int i = 0; i < n && i < 8; ++i) out[i] = v[i];
     return KGW_OK;
 }
 

@@ -157,6 +157,30 @@ def build_csr(edge_index, n_src: int, n_dst: int):
     return rowptr, col
 
 
+def csr_order(edge_index, n_src: int, n_dst: int) -> np.ndarray:
+    """The permutation ``build_csr`` sorts a relation's edges by: entry p of the dst-major CSR is column ``order[p]`` of
+    ``edge_index`` (stable, so parallel edges keep their relative order)."""
+    ei = _as_np(edge_index)
+    return np.argsort(ei[1] * np.int64(n_src) + ei[0], kind='stable')
+
+
+def csr_edge_attr(edge_attr, edge_index, n_src: int, n_dst: int, col=None) -> np.ndarray:
+    """Edge attributes ``[E]`` or ``[E, D]`` aligned with the columns of ``edge_index`` -> float32 ``[E, D]`` in the order of the
+    relation's dst-major CSR (``build_csr``).  ``col``: the CSR's column array when it did not come from ``build_csr`` (an ingest
+    cache) -- the recomputed permutation must reproduce it."""
+    ei = _as_np(edge_index)
+    a = edge_attr.detach().cpu().numpy() if torch.is_tensor(edge_attr) else np.asarray(edge_attr)
+    a = np.asarray(a, dtype=np.float32)
+    if a.ndim == 1:
+        a = a.reshape(-1, 1)               # (conv.py:209: a 1-D edge_attr is a column)
+    if a.ndim != 2 or a.shape[0] != ei.shape[1]:
+        raise ValueError(f'edge_attr of shape {tuple(a.shape)} does not match {ei.shape[1]} edges')
+    order = csr_order(ei, n_src, n_dst)
+    if col is not None:
+        assert np.array_equal(np.asarray(col, dtype=np.int64), ei[0][order]), 'cached CSR is not the stable (dst, src) sort of edge_index'
+    return np.ascontiguousarray(a[order])
+
+
 class GraphSchema:
     """Static type-level description shared by sampler, model and kernels: node-type order,
     relation order, and for every relation its slot among the relations that share its

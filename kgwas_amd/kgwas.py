@@ -49,7 +49,8 @@ class KGWAS:
         self.exp_name = exp_name
 
     def initialize_model(self, gnn_num_layers=2, gnn_hidden_dim=128, gnn_backbone='GAT', gnn_aggr='sum',
-                         gat_num_head=1, no_relu=False, out_channels=1, gat_dropout=0.0, gat_sigmoid=False, gat_temperature=1.0):
+                         gat_num_head=1, no_relu=False, out_channels=1, gat_dropout=0.0, gat_sigmoid=False, gat_temperature=1.0,
+                         gat_edge_dim=None):
         """``out_channels`` (extra, default 1 = the reference, kgwas.py:52): T > 1 reads ONE shared trunk out into T label columns
         (``data['SNP'].y`` [N, T], KGWAS_Data.from_synthetic(n_traits=T)) -- a shared-trunk multi-task model, not T independent
         models.  It enters ``config`` only when it is not 1, so the config.pkl of a single-trait run is what it always was.
@@ -59,7 +60,11 @@ class KGWAS:
         GATConv(hidden // H, heads=H); HeteroGNN(gat_split_heads=True)) -- not the reference's literal widening to H * hidden.
         ``gat_sigmoid`` / ``gat_temperature`` (extras, defaults False / 1 = the reference's model; its GATConv's ``sigmoid_gat`` and
         ``temperature``, conv.py:49-50): sigmoid gates instead of the softmax, and the divisor T of the attention logits (HeteroGNN).
-        Each enters ``config`` only when it is not the default."""
+        Each enters ``config`` only when it is not the default.
+        ``gat_edge_dim`` = D in 1..8 (extra, default None = the reference's model, launch for launch and bit for bit): GATConv's
+        ``edge_dim`` (conv.py:46,207-215) for the relations whose ``data[edge_type].edge_attr`` is set (KGWAS_Data.set_edge_attr /
+        from_synthetic(edge_dim=D)); it enters ``config`` only when it is set.  GAT only; not with gat_num_head > 1, gat_dropout > 0
+        or gat_sigmoid; training takes whole neighbourhoods (no ``num_neighbors``) and parallelism='seed'."""
         self.config = {'gnn_num_layers': gnn_num_layers, 'gnn_hidden_dim': gnn_hidden_dim,
                        'gnn_backbone': gnn_backbone, 'gnn_aggr': gnn_aggr, 'gat_num_head': gat_num_head}
         out_channels = int(out_channels)
@@ -75,11 +80,14 @@ class KGWAS:
             self.config['gat_sigmoid'] = True
         if gat_temperature != 1.0:
             self.config['gat_temperature'] = gat_temperature
+        if gat_edge_dim is not None:
+            self.config['gat_edge_dim'] = int(gat_edge_dim)
         self.gnn_num_layers = gnn_num_layers
         self.model = HeteroGNN(self.data.data, gnn_hidden_dim, out_channels, gnn_num_layers, gnn_backbone, gnn_aggr,
                                self.data.snp_init_dim_size, self.data.gene_init_dim_size,
                                self.data.go_init_dim_size, gat_num_head, no_relu=no_relu, gat_dropout=gat_dropout,
-                               gat_split_heads=True, gat_sigmoid=gat_sigmoid, gat_temperature=gat_temperature).to(self.device)
+                               gat_split_heads=True, gat_sigmoid=gat_sigmoid, gat_temperature=gat_temperature,
+                               gat_edge_dim=gat_edge_dim).to(self.device)
 
     def load_pretrained(self, path):
         import pandas as pd
@@ -159,6 +167,9 @@ class KGWAS:
         if getattr(self.model, 'gat_sigmoid', False) or getattr(self.model, 'temperature', 1.0) != 1.0:
             raise NotImplementedError("gat_sigmoid / gat_temperature are not available with parallelism='shard': the exchange of "
                                       "partial softmax states is built for the softmax at T = 1; use parallelism='seed'")
+        if getattr(self.model, 'edge_dim', None) is not None:
+            raise NotImplementedError("gat_edge_dim is not available with parallelism='shard': the edge-attribute forward does not "
+                                      "leave partial softmax states; use parallelism='seed'")
         if self.model.lin.out_features != 1:
             raise NotImplementedError("out_channels > 1 (multi-trait labels) is not available with parallelism='shard': the "
                                       "sharded step's read-out and loss are single-column; use parallelism='seed'")
@@ -222,6 +233,9 @@ class KGWAS:
             elif parallelism == 'shard':
                 raise NotImplementedError("a finite fan-out is not available with parallelism='shard': the ranks would have "
                                           "to agree on the draw of every replicated row")
+            elif getattr(self.model, 'edge_dim', None) is not None:
+                raise NotImplementedError('gat_edge_dim with a finite num_neighbors: a drawn segment keeps no record of which '
+                                          'entries of its row it holds, so its edges cannot find their attributes')
         if save_name is None:
             save_name = self.exp_name
         self.save_name = save_name

@@ -139,11 +139,41 @@ class KGWAS_Data:
             data[et].edge_index = torch.from_numpy(np.ascontiguousarray(ei))
         self.data = data
 
+    def set_edge_attr(self, attrs):
+        """Edge attributes for KGWAS.initialize_model(gat_edge_dim=D) (GATConv's ``edge_dim``, kgwas/conv.py:46,207-215; the
+        reference's load_kg keeps no edge evidence: an extension).  ``attrs``: {edge type: array [E] or [E, D]}, row e belonging to
+        column e of ``data[edge_type].edge_index`` of the FINAL graph -- after ToUndirected / AddSelfLoops, so a ``rev_<rel>``
+        mirror, the symmetrised half of a same-type relation and the self-loops are edge types / columns of their own and which
+        values they carry is the caller's choice.  Checked: the edge type exists, one row per edge, finite values, one width D
+        for every attributed relation of the graph.  Stored as float32 [E, D] in ``data[edge_type].edge_attr``."""
+        new = {}
+        for et, a in attrs.items():
+            et = tuple(et)
+            if et not in self.data.edge_types:
+                raise ValueError(f'edge type {et} is not in the graph')
+            a = torch.as_tensor(np.asarray(a.detach().cpu() if torch.is_tensor(a) else a), dtype=torch.float32)
+            if a.dim() == 1:
+                a = a.view(-1, 1)
+            E = int(self.data[et].edge_index.shape[1])
+            if a.dim() != 2 or a.shape[0] != E:
+                raise ValueError(f'edge_attr of {et}: shape {tuple(a.shape)}, the relation has {E} edges')
+            if not bool(torch.isfinite(a).all()):
+                raise ValueError(f'edge_attr of {et} holds non-finite values')
+            new[et] = a.contiguous()
+        widths = {int(a.shape[1]) for a in new.values()}
+        widths |= {int(self.data[et].edge_attr.shape[1]) for et in self.data.edge_types
+                   if et not in new and self.data[et].get('edge_attr') is not None}
+        if len(widths) > 1:
+            raise ValueError(f'edge attributes of widths {sorted(widths)}: one width D for all relations')
+        for et, a in new.items():
+            self.data[et].edge_attr = a
+        self.data._extra.pop('_device_graphs', None)          # (resident graphs built before this do not hold the attributes)
+
     @classmethod
     def from_synthetic(cls, scale=1.0, seed=1, mode='fast', data_path='/tmp/kgwas_synth', n_labelled=None,
                        gwas_kind='causal', sample_size=None, feat_dims=None, split=True, snp_scale=1.0,
                        sample_edges=False, sample_ratio=1.0, node_counts=None, n_traits=1, trait_sample_sizes=None,
-                       trait_coverage=None):
+                       trait_coverage=None, edge_dim=None, edge_attr_relations=None):
         """SynthKG + synthetic summary statistics through the same pipeline as the real files.
         ``gwas_kind`` mirrors the reference's four label sources (BASELINE.json configs): 'causal' / 'null' = the
         simulations of load_simulation_gwas (N = 5000, kgwas_data.py:275-294), 'subsample' = load_gwas_subsample
@@ -158,7 +188,11 @@ class KGWAS_Data:
         ceil(c_t * n_labelled) of the labelled SNPs (drawn under ``seed + 7919 * t``); its weights are
         ldsc_regression_weights(ld, w_ld, N_t, M, 0.5) divided by their mean over the SNPs it observes and 0 elsewhere:
         ``ldsc_weight_traits`` float64 [len(all_ids), T] and ``trait_observed`` bool [len(all_ids), T], rows as ``all_ids``;
-        ``data['SNP'].y[:, t]`` is 0 where trait t is not observed.  One list alone leaves the other at ``sample_size`` / 1."""
+        ``data['SNP'].y[:, t]`` is 0 where trait t is not observed.  One list alone leaves the other at ``sample_size`` / 1.
+        ``edge_dim`` = D (None: no edge attributes, the graph as ever): seeded N(0, 1) attributes [E, D] on the relations named by
+        ``edge_attr_relations`` (relation names or edge types of the ORIGINAL relations; None = all of them) through
+        ``set_edge_attr``; the ``rev_<rel>`` mirror of a bipartite relation repeats its forward relation's values edge by edge,
+        the columns of a symmetrised same-type relation (mirrors and self-loops included) draw their own."""
         import pandas as pd
         from .synth import FEAT_DIMS, make_synth_edges, make_synth_gwas
         self = cls(data_path)
@@ -216,6 +250,24 @@ class KGWAS_Data:
                 k = int(np.ceil(c * n_lab))
                 observed[np.random.default_rng(seed + 7919 * t).choice(n_lab, size=k, replace=False), t] = True
             self._set_trait_weights(g['ld_score'], g['w_ld_score'], sizes, observed)
+        if edge_dim is not None:
+            D = int(edge_dim)
+            if not 1 <= D <= 8:
+                raise ValueError(f'edge_dim {edge_dim}: 1 to 8')
+            names = None if edge_attr_relations is None else {tuple(x) if not isinstance(x, str) else x for x in edge_attr_relations}
+            attrs = {}
+            for k, et in enumerate(edges.keys()):
+                et = tuple(et)
+                if names is not None and et not in names and et[1] not in names:
+                    continue
+                rng = np.random.default_rng([int(seed), 0x0ED6E, k])
+                a = rng.standard_normal((int(self.data[et].edge_index.shape[1]), D)).astype(np.float32)
+                attrs[et] = a
+                if et[0] != et[2]:
+                    attrs[(et[2], 'rev_' + et[1], et[0])] = a
+            if not attrs:
+                raise ValueError('edge_attr_relations names no relation of the graph')
+            self.set_edge_attr(attrs)
         if split:
             self.prepare_split()
         return self

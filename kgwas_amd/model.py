@@ -44,6 +44,7 @@ _RELVEC_ALL = os.environ.get('KGW_RELVEC_ALL', '1') != '0'      # (A/B: one rela
 EdgeType = Tuple[str, str, str]
 GO_TYPES = ('CellularComponent', 'BiologicalProcess', 'MolecularFunction')
 REL_FIELDS = ('att_src', 'att_dst', 'bias', 'lin_src.weight', 'lin_dst.weight')
+EDGE_FIELDS = ('lin_edge.weight', 'att_edge')        # relations that carry edge attributes only (gat_edge_dim)
 
 
 def _signed64(word: int) -> int:
@@ -124,9 +125,12 @@ class RelationPack(nn.Module):
     """Parameters of a list of relations of one layer, packed (kgwas/conv.py:81-120 per relation):
     ``w_src_t[i]`` = lin_src.weight^T  ([in k, out c], glorot), ``w_dst_t[j]`` = lin_dst.weight^T of the
     j-th bipartite relation (same-type relations never materialise lin_dst in the reference),
-    ``att_src`` / ``att_dst`` (glorot on [1,heads,C/heads], kept flat: column c belongs to head c // (C/heads)), ``bias`` (zeros)."""
+    ``att_src`` / ``att_dst`` (glorot on [1,heads,C/heads], kept flat: column c belongs to head c // (C/heads)), ``bias`` (zeros).
+    ``edge_dim`` = D with ``attr_rels`` (relation ids that carry edge attributes; conv.py:95-101): for the j-th attributed relation
+    of the pack ``w_edge_t[j]`` = lin_edge.weight^T ([D, out c], glorot on [C, D]) and ``att_edge[j]`` (glorot on [1, 1, C])."""
 
-    def __init__(self, edge_types: List[EdgeType], rel_ids: List[int], C: int, c_logical: int = None, heads: int = 1):
+    def __init__(self, edge_types: List[EdgeType], rel_ids: List[int], C: int, c_logical: int = None, heads: int = 1,
+                 edge_dim: int = None, attr_rels=()):
         super().__init__()
         self.n_rels_total = len(edge_types)
         self.rel_ids = list(rel_ids)
@@ -167,6 +171,17 @@ class RelationPack(nn.Module):
         self.register_buffer('live_of_rel_i32', torch.tensor(live_of, dtype=torch.int32), persistent=False)
         self.register_buffer('bip_pos_i32', torch.tensor([self.bip_pos.get(i, -1) for i in range(n)], dtype=torch.int32),
                              persistent=False)
+        # edge attributes: created only when asked for, after everything else (a model without them draws what it always drew)
+        self.edge_dim = edge_dim
+        self.attr = [i for i, r in enumerate(rel_ids) if r in set(attr_rels)] if edge_dim else []
+        self.attr_pos = {i: j for j, i in enumerate(self.attr)}
+        if edge_dim:
+            w = torch.zeros(len(self.attr), edge_dim, C)
+            with torch.no_grad():
+                w[:, :, :cl].uniform_(-math.sqrt(6.0 / (cl + edge_dim)), math.sqrt(6.0 / (cl + edge_dim)))
+            self.w_edge_t = nn.Parameter(w)
+            self.att_edge = nn.Parameter(block((len(self.attr), C), math.sqrt(6.0 / (1 + cl))))
+            self.register_buffer('attr_rel_ids_t', torch.tensor([rel_ids[i] for i in self.attr], dtype=torch.long), persistent=False)
 
     # reference-named view of one tensor of relation slot i (value or gradient)
     def get(self, i: int, field: str, grad: bool = False):
@@ -175,6 +190,12 @@ class RelationPack(nn.Module):
                 return None if p.grad is None else p.grad
             return p.detach()
         cl = self.cl
+        if field in EDGE_FIELDS:
+            j = self.attr_pos[i]
+            t = pick(self.w_edge_t if field == 'lin_edge.weight' else self.att_edge)
+            if t is None:
+                return None
+            return t[j, :, :cl].t() if field == 'lin_edge.weight' else t[j, :cl].reshape(1, 1, -1)
         if field == 'lin_src.weight':
             t = pick(self.w_src_t)
             return None if t is None else t[i, :cl, :cl].t()
@@ -191,7 +212,11 @@ class RelationPack(nn.Module):
     def set(self, i: int, field: str, value: torch.Tensor):
         cl = self.cl
         with torch.no_grad():
-            if field == 'lin_src.weight':
+            if field == 'lin_edge.weight':
+                self.w_edge_t[self.attr_pos[i], :, :cl].copy_(value.t())
+            elif field == 'att_edge':
+                self.att_edge[self.attr_pos[i], :cl].copy_(value.reshape(-1))
+            elif field == 'lin_src.weight':
                 self.w_src_t[i, :cl, :cl].copy_(value.t())
             elif field == 'lin_dst.weight':
                 if i in self.bip_pos:
@@ -260,11 +285,18 @@ class HeteroGNN(nn.Module):
     217-224, its HeteroGNN never passes them): ``gat_temperature`` = T > 0 divides every attention logit, in the softmax and in the
     gate; ``gat_sigmoid=True`` weights every edge by sigmoid(e / T) instead of by the softmax over its row (independent gates, not
     normalised by degree: ops.gat_aggregate(sigmoid_gate=True)), in training, evaluation, the attention queries and the export.
-    GAT only; not with gat_num_head > 1 or gat_dropout > 0.  A gated model does not fold FC_output into layer 1 (``fold_fc``)."""
+    GAT only; not with gat_num_head > 1 or gat_dropout > 0.  A gated model does not fold FC_output into layer 1 (``fold_fc``).
+    ``gat_edge_dim`` = D in 1..8 (an extension, keyword only: the reference's GATConv has ``edge_dim``, conv.py:46,95-101,207-215, its
+    HeteroGNN never passes it): every relation whose ``pyg_data[edge_type].edge_attr`` ([E] or [E, D], aligned with the columns of
+    its ``edge_index``) is set gets a bias-free ``lin_edge`` [hidden, D] and an ``att_edge``, and <lin_edge(attr_e), att_edge> joins
+    the attention logit of its edges before the LeakyReLU, in every layer (state-dict keys ``convs.<l>.convs.<key>.lin_edge.weight``
+    / ``.att_edge``).  The other relations are what they were.  The softmax still sums to one: the model keeps the FC_output fold
+    and the fused optimiser launch.  GAT only; not with gat_num_head > 1, gat_dropout > 0 or gat_sigmoid; ``None`` (the default) is
+    the model as ever, launch for launch."""
 
     def __init__(self, pyg_data, hidden_channels, out_channels, num_layers, gnn_backbone, gnn_aggr,
                  snp_init_dim_size, gene_init_dim_size, go_init_dim_size, gat_num_head, no_relu=False, gat_dropout=0.0,
-                 gat_split_heads=False, *, gat_sigmoid=False, gat_temperature=1.0):
+                 gat_split_heads=False, *, gat_sigmoid=False, gat_temperature=1.0, gat_edge_dim=None):
         super().__init__()
         if gnn_backbone not in ('GAT', 'SAGE'):
             raise NotImplementedError(f"backbone {gnn_backbone!r}: 'GAT' (the reference default, kgwas.py:52) and 'SAGE' "
@@ -331,6 +363,29 @@ class HeteroGNN(nn.Module):
         self.edge_types = [tuple(e) for e in pyg_data.edge_types]
         self.schema = GraphSchema(self.node_types, self.edge_types)
         sc = self.schema
+        self.edge_dim, self.attr_rels = None, []
+        if gat_edge_dim is not None:
+            if gnn_backbone == 'SAGE':
+                raise ValueError("gat_edge_dim needs gnn_backbone='GAT': SAGE has no attention logits for the attributes to enter")
+            what = [n for n, v in (('gat_num_head > 1', gat_num_head > 1), ('gat_dropout > 0', gat_dropout != 0.0),
+                                   ('gat_sigmoid', self.gat_sigmoid)) if v]
+            if what:
+                raise NotImplementedError(f'gat_edge_dim with {", ".join(what)}: the edge-attribute forward is built for one head of '
+                                          'undropped softmax weights')
+            if gat_edge_dim != int(gat_edge_dim) or not 1 <= int(gat_edge_dim) <= 8:
+                raise ValueError(f'gat_edge_dim {gat_edge_dim!r}: 1 to 8 attribute columns')
+            self.edge_dim = int(gat_edge_dim)
+            widths = {}
+            for r, et in enumerate(self.edge_types):
+                a = getattr(pyg_data[et], 'edge_attr', None)
+                if a is not None:
+                    widths[r] = 1 if a.dim() == 1 else int(a.shape[1])
+            if not widths:
+                raise ValueError('gat_edge_dim is set but no relation of the graph carries edge_attr (KGWAS_Data.set_edge_attr)')
+            if set(widths.values()) != {self.edge_dim}:
+                raise ValueError(f'gat_edge_dim {self.edge_dim} but the relations carry attributes of width '
+                                 f'{sorted(set(widths.values()))}: one width for all relations')
+            self.attr_rels = sorted(widths)
         self.num_layers = num_layers
         # gnn_hidden_dim < 128 (kgwas/kgwas.py:52): the model is embedded in the 128-wide kernels -- every hidden tensor and
         # parameter zero-padded to 128.  Exact: padded channels are 0 after every Linear / ReLU, padded parameters receive a
@@ -352,6 +407,8 @@ class HeteroGNN(nn.Module):
             dead = [r for r in range(sc.NR) if r not in live]
             Pack = RelationPack if gnn_backbone == 'GAT' else SagePack
             kw = {'heads': gat_num_head} if gnn_backbone == 'GAT' else {}
+            if self.edge_dim is not None:
+                kw.update(edge_dim=self.edge_dim, attr_rels=self.attr_rels)
             self.live_packs.append(Pack(self.edge_types, order, hidden_channels, cl, **kw))
             self.dead_packs.append(Pack(self.edge_types, dead, hidden_channels, cl, **kw))
             slot = {r: ('live', i) for i, r in enumerate(order)}
@@ -624,7 +681,32 @@ class HeteroGNN(nn.Module):
                 fc += [mm.FC_output.weight if used else mm.FC_output.weight.detach(),
                        mm.FC_output.bias if used else mm.FC_output.bias.detach()]
             U, V, kap, Wp, gam = ops.fold_fc_output_hip(P, U, V, fc, self._fold_tab, weight=Wv)
-        return tys, blocks, zws, U, V, bsum, Wv, kap, Wp, gam
+        return tys, blocks, zws, U, V, bsum, Wv, kap, Wp, gam, self._edge_term(batch, l, (P,))
+
+    def _edge_term(self, batch: SampledBatch, l: int, packs):
+        """The per-edge logit term of layer l's attributed relations (ops.edge_logit_term), or None for a model without edge
+        attributes / a layer that computes no attributed relation.  w_r = lin_edge.weight^T att_edge [n_rels, 8] by relation id is
+        formed by element-wise framework ops (as ``_head_vectors`` forms u^h, v^h): a product, a sum, the padding to 8 columns and the
+        scatter to relation ids."""
+        if self.edge_dim is None:
+            return None
+        dg = batch.dg
+        if dg.eattr_rels != self.attr_rels or dg.eattr_dim != self.edge_dim:      # (both fixed when the graph / the model was built)
+            have = dg.eattr_rels
+            missing = [self.edge_types[r] for r in self.attr_rels if r not in have]
+            raise ValueError(f'the model was built with edge attributes of width {self.edge_dim} on {len(self.attr_rels)} relations; the '
+                             f'batch\'s graph carries width {dg.eattr_dim} on {len(have)}' +
+                             (f' (no edge_attr for {missing[:3]})' if missing else ''))
+        W = None
+        for P in packs:
+            if not len(P.attr):
+                continue
+            w = (P.w_edge_t * P.att_edge.unsqueeze(1)).sum(2)                  # [n_attr, D]
+            if self.edge_dim < 8:
+                w = torch.nn.functional.pad(w, (0, 8 - self.edge_dim))
+            w = w.new_zeros(self.schema.NR, 8).index_copy(0, P.attr_rel_ids_t, w)
+            W = w if W is None else W + w
+        return None if W is None else ops.edge_logit_term(batch, l, W)
 
     def _head_vectors(self, P: RelationPack):
         """u_r^h[k] = sum_{c in head h} W_src^T[k, c] att_src[c] and v_r^h likewise (W_dst of a bipartite relation, W_src of a
@@ -721,7 +803,7 @@ class HeteroGNN(nn.Module):
             prep = self._all_layer_params(batch, folded)
         for l in range(1, self.num_layers + 1):
             P: RelationPack = self.live_packs[l - 1]
-            tys, blocks, zws, U, V, bsum, Wv, kap, Wp, gam = prep[l - 1] if prep is not None else self._layer_params(batch, l, folded)
+            tys, blocks, zws, U, V, bsum, Wv, kap, Wp, gam, term = prep[l - 1] if prep is not None else self._layer_params(batch, l, folded)
             # layer input, type-major (src_base): every type that sends or receives messages in this layer
             parts, spans = [], []
             for t, name in enumerate(sc.node_types):
@@ -740,7 +822,7 @@ class HeteroGNN(nn.Module):
             fused = self.aggr in ('sum', 'mean')
             Z, stat, e_edge = ops.gat_aggregate(batch, l, H, U, V, self.negative_slope, self.temperature,
                                                 relu_input=((l > 1 or folded) and fused), zbuf=zws, logit_bias=kap,
-                                                dropout=dropout, sigmoid_gate=self.gat_sigmoid)
+                                                dropout=dropout, sigmoid_gate=self.gat_sigmoid, edge_term=term)
             if want_attention:
                 attn.append(self._edge_weights(batch, l, stat, e_edge))
             if not fused:
@@ -774,14 +856,19 @@ class HeteroGNN(nn.Module):
         return h, attn
 
     def forward(self, x_dict, edge_index_dict, batch_size, genotype=None, return_h=False,
-                return_attention_weights=False):
+                return_attention_weights=False, edge_attr_dict=None):
+        """``edge_attr_dict`` (a model with ``gat_edge_dim``, plain COO inputs): {edge type: [E] or [E, D]} aligned with the columns
+        of ``edge_index_dict``; every attributed relation needs its entry.  The dicts of a sampled batch bring their own
+        (``batch.edge_attr_dict``)."""
         if return_attention_weights and not return_h:           # model.py:65-72,80-81 (mean attention per layer)
             if self.heads > 1:
                 raise NotImplementedError('gat_num_head > 1: forward(return_attention_weights=True) is single-head')
-            return self._forward_with_attention(x_dict, edge_index_dict, batch_size)
+            if edge_attr_dict is None and self.edge_dim is not None and getattr(edge_index_dict, 'kgw_batch', None) is not None:
+                edge_attr_dict = edge_index_dict.kgw_batch.edge_attr_dict
+            return self._forward_with_attention(x_dict, edge_index_dict, batch_size, edge_attr_dict)
         batch: Optional[SampledBatch] = getattr(x_dict, 'kgw_batch', None) or getattr(edge_index_dict, 'kgw_batch', None)
         if batch is None:
-            batch = self._block_from_coo(x_dict, edge_index_dict)
+            batch = self._block_from_coo(x_dict, edge_index_dict, edge_attr_dict)
         hbuf, blocks = self._layer_input(batch, 1)
         drop = self._dropout()
         fold = self.fold_fc and drop is None                    # (see _dropout: a step that drops runs layer 1 unfolded)
@@ -815,7 +902,8 @@ class HeteroGNN(nn.Module):
         _, attn = self._fused_layers(batch, h, want_attention=True, hbuf=hbuf, folded=self.fold_fc)
         return attn
 
-    def forward_loss(self, x_dict, edge_index_dict, batch_size, n_id, y_all, w_all, mlp_out=None, unit_grad=False):
+    def forward_loss(self, x_dict, edge_index_dict, batch_size, n_id, y_all, w_all, mlp_out=None, unit_grad=False,
+                     edge_attr_dict=None):
         """The training step's forward (kgwas/kgwas.py:137-145): HeteroGNN.forward followed by
         mean(w_all[n_id] * (pred - y_all[n_id])**2), with the read-out Linear + ReLU (model.py:86) and the loss fused
         into one node.  Returns (loss [float64 scalar], pred [batch_size]) -- with ``out_channels = T > 1`` (a shared trunk read out
@@ -826,7 +914,7 @@ class HeteroGNN(nn.Module):
         ``loss.backward()`` (gradient 1): the read-out node then does its forward and backward in two launches."""
         batch: Optional[SampledBatch] = getattr(x_dict, 'kgw_batch', None) or getattr(edge_index_dict, 'kgw_batch', None)
         if batch is None:
-            batch = self._block_from_coo(x_dict, edge_index_dict)
+            batch = self._block_from_coo(x_dict, edge_index_dict, edge_attr_dict)
         if not 1 <= self.lin.out_features <= 32:
             raise NotImplementedError('the fused read-out + loss takes out_channels from 1 (kgwas/kgwas.py:52) to 32')
         hbuf, blocks = self._layer_input(batch, 1)
@@ -879,7 +967,8 @@ class HeteroGNN(nn.Module):
             H = torch.cat(parts, 0)
             gate = self.gat_sigmoid
             Z, stat, e_edge = ops.gat_aggregate(batch, l, H, U, V, self.negative_slope, self.temperature, raw_weights=raw and not gate,
-                                                sigmoid_gate=gate)
+                                                sigmoid_gate=gate,
+                                                edge_term=self._edge_term(batch, l, (self.live_packs[l - 1], self.dead_packs[l - 1])))
             per_layer.append(e_edge if (raw and not gate) else self._edge_weights(batch, l, stat, e_edge))
             h_next = {}
             for t, name in enumerate(sc.node_types):
@@ -935,8 +1024,19 @@ class HeteroGNN(nn.Module):
             layers.append(att)
         return layers
 
+    def _coo_edge_attrs(self, g: HeteroGraph, edge_attr_dict):
+        """``edge_attr_dict`` onto the relations of a graph built from plain COO inputs (a model with ``gat_edge_dim``)."""
+        if self.edge_dim is None:
+            return
+        for r in self.attr_rels:
+            et = self.edge_types[r]
+            a = None if edge_attr_dict is None else edge_attr_dict.get(et)
+            if a is None:
+                raise ValueError(f'the model has edge attributes on {et}: edge_attr_dict needs an entry for it')
+            g[et].edge_attr = a
+
     @torch.no_grad()
-    def _forward_with_attention(self, x_dict, edge_index_dict, batch_size):
+    def _forward_with_attention(self, x_dict, edge_index_dict, batch_size, edge_attr_dict=None):
         """forward(return_attention_weights=True) (kgwas/model.py:65-72,80-81): the reference runs EVERY edge type over
         every edge of the batch in both layers and returns the mean attention of all of them per layer, so this path
         does too -- the batch's subgraph as a full block with all relations live, no hop pruning (inference only)."""
@@ -955,6 +1055,7 @@ class HeteroGNN(nn.Module):
         for et in self.edge_types:
             ei = edge_index_dict.get(et)
             g[et].edge_index = ei if ei is not None else torch.zeros(2, 0, dtype=torch.long)
+        self._coo_edge_attrs(g, edge_attr_dict)
         dg = DeviceGraph(g, self.num_layers, dev, full_graph=True).with_all_relations_live()
         buf = BatchBuffers(dg)
         sample_into(dg, buf, None, 0)
@@ -966,7 +1067,7 @@ class HeteroGNN(nn.Module):
         return out, [a.mean() if a.numel() else a.sum() for a in per_layer]
 
     # ------------------------------------------------------------------------------------------
-    def _block_from_coo(self, x_dict, edge_index_dict) -> SampledBatch:
+    def _block_from_coo(self, x_dict, edge_index_dict, edge_attr_dict=None) -> SampledBatch:
         """Plain (x_dict, edge_index_dict) inputs: every row of every type is computed in every layer,
         exactly like the reference on a PyG batch / the full graph (kgwas/utils.py:446-461)."""
         dev = next(iter(x_dict.values())).device
@@ -976,6 +1077,7 @@ class HeteroGNN(nn.Module):
         for et in self.edge_types:
             ei = edge_index_dict.get(et)
             g[et].edge_index = ei if ei is not None else torch.zeros(2, 0, dtype=torch.long)
+        self._coo_edge_attrs(g, edge_attr_dict)
         return sample_full_graph(g, self.num_layers, dev)
 
     # --- reference-named parameters (checkpoints, tests) ------------------------------------------
@@ -985,8 +1087,12 @@ class HeteroGNN(nn.Module):
             for r, et in enumerate(self.edge_types):
                 which, i = self._slot[l][r]
                 pack = self.live_packs[l] if which == 'live' else self.dead_packs[l]
-                for f in self.rel_fields:
+                for f in self._fields_of(r):
                     yield f'convs.{l}.convs.{edge_key(et)}.{f}', pack.get(i, f, grad)
+
+    def _fields_of(self, r: int):
+        """Reference names of relation r's tensors: an attributed relation (``gat_edge_dim``) also has lin_edge.weight / att_edge."""
+        return self.rel_fields + EDGE_FIELDS if r in self.attr_rels else self.rel_fields
 
     def _dense_items(self, grad: bool = False, keep_vars: bool = False):
         """(reference key, tensor at the model's own width) of the feature MLPs and the read-out."""
@@ -1030,7 +1136,7 @@ class HeteroGNN(nn.Module):
         want = {}
         for l in range(self.num_layers):
             for r, et in enumerate(self.edge_types):
-                for f in self.rel_fields:
+                for f in self._fields_of(r):
                     want[f'convs.{l}.convs.{edge_key(et)}.{f}'] = (l, r, f)
         rest = OrderedDict()
         seen = set()

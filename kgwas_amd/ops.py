@@ -460,7 +460,7 @@ def _set_dropout(a: KgwLayerArgs, dropout):
 class _GatAggregate(torch.autograd.Function):
     @staticmethod
     def forward(ctx, H, U, V, batch, layer, neg_slope, inv_temp, raw_weights=False, relu_input=False, zbuf=None, lbias=None,
-                dropout=None, gate=False):
+                dropout=None, gate=False, eterm=None):
         dg, m = batch.dg, batch.meta
         NT = dg.schema.NT
         z_rows = int(m.z_base[layer - 1][NT])
@@ -505,7 +505,13 @@ class _GatAggregate(torch.autograd.Function):
         xchg = getattr(batch, 'exchange', None)
         if xchg is not None and not raw_weights:
             a.partial_rels = xchg.mask[layer]
-        _lib.check(_lib.lib().kgw_gat_aggregate_fwd(C.byref(a), _lib.stream_ptr()), 'kgw_gat_aggregate_fwd')
+        ctx.has_eterm = eterm is not None
+        if eterm is not None:                      # edge attributes: pre_e += term[e] (kgw_edge_term_fwd's; KgwEdgeAttr in kgwas_hip.h)
+            eterm = eterm.contiguous()
+            assert eterm.dtype == torch.float32 and eterm.numel() >= n_edges and eterm.device == dev
+            _lib.check(_lib.lib().kgw_gat_aggregate_fwd_eterm(C.byref(a), _p(eterm), _lib.stream_ptr()), 'kgw_gat_aggregate_fwd_eterm')
+        else:
+            _lib.check(_lib.lib().kgw_gat_aggregate_fwd(C.byref(a), _lib.stream_ptr()), 'kgw_gat_aggregate_fwd')
         if xchg is not None and not raw_weights and xchg.mask[layer]:
             xchg.forward(batch, layer, Z, stat)
         ctx.set_materialize_grads(False)          # no zero tensors for the (non-differentiable) stat / e_edge outputs
@@ -519,7 +525,7 @@ class _GatAggregate(torch.autograd.Function):
         if ctx.raw_weights:
             raise RuntimeError('raw-logit aggregation (attention export) is inference only')
         if dZ is None:
-            return (None,) * 13
+            return (None,) * 14
         H, U, V, Z, stat, e_edge = ctx.saved_tensors
         batch, layer = ctx.batch, ctx.layer
         dg, m = batch.dg, batch.meta
@@ -592,7 +598,8 @@ class _GatAggregate(torch.autograd.Function):
             dU, dV = torch.zeros_like(U), torch.zeros_like(V)
         if ctx.has_lbias and not n_src:                  # (no source rows: the launch above did not run)
             _lib.check(L.kgw_relation_sums(C.byref(a), _p(da_dst), _p(dlb), _lib.stream_ptr()), 'kgw_relation_sums')
-        return dH[:n_src], dU, dV, None, None, None, None, None, None, None, dlb, None, None
+        # (edge attributes: adp[e] = (alpha_e, d pre_e), and d pre_e is the gradient of the edge's logit term -- handed on in place)
+        return dH[:n_src], dU, dV, None, None, None, None, None, None, None, dlb, None, None, (adp[:, 1] if ctx.has_eterm else None)
 
 
 class _GatAggregateHeads(torch.autograd.Function):
@@ -673,6 +680,81 @@ class _GatAggregateHeads(torch.autograd.Function):
         return dH, dU, dV, None, None, None, None, None, None
 
 
+def _edge_attr_args(batch, w8=None) -> "_lib.KgwEdgeAttr":
+    dg = batch.dg
+    ea = _lib.KgwEdgeAttr()
+    ea.attr = _p(dg.g_eattr)
+    ea.dim = dg.eattr_dim
+    for r in range(_lib.KGW_MAX_RELS):
+        ea.attr_off[r] = dg.eattr_off[r] if r < dg.schema.NR else -1
+    if w8 is not None:
+        ea.w = _p(w8)
+    return ea
+
+
+class _EdgeLogitTerm(torch.autograd.Function):
+    """``edge_logit_term``: k_edge_term forward, k_edge_term_bwd + its fold backward."""
+
+    @staticmethod
+    def forward(ctx, w_edge, batch, layer):
+        dg, m = batch.dg, batch.meta
+        n_edges = int(m.n_edges[layer - 1])
+        D = dg.eattr_dim
+        assert w_edge.dtype == torch.float32 and w_edge.dim() == 2 and w_edge.shape[0] == dg.schema.NR and w_edge.shape[1] in (D, 8), \
+            (tuple(w_edge.shape), dg.schema.NR, D)
+        if w_edge.shape[1] == 8:
+            w8 = w_edge.contiguous()
+        else:                                       # the kernels read rows of 8
+            w8 = w_edge.new_zeros(dg.schema.NR, 8)
+            w8[:, :D] = w_edge
+        term = torch.empty(max(n_edges, 1), device=w_edge.device)
+        a = _layer_args(batch, layer, 0.2, 1.0)
+        ea = _edge_attr_args(batch, w8)
+        ea.term = _p(term)
+        _lib.check(_lib.lib().kgw_edge_term_fwd(C.byref(a), C.byref(ea), _lib.stream_ptr()), 'kgw_edge_term_fwd')
+        ctx.batch, ctx.layer, ctx.width = batch, layer, int(w_edge.shape[1])
+        return term
+
+    @staticmethod
+    def backward(ctx, d_term):
+        batch, layer = ctx.batch, ctx.layer
+        dg = batch.dg
+        if d_term.dim() != 1 or d_term.stride(0) < 1:
+            d_term = d_term.reshape(-1).contiguous()
+        assert d_term.dtype == torch.float32 and d_term.numel() >= int(batch.meta.n_edges[layer - 1])
+        a = _layer_args(batch, layer, 0.2, 1.0)
+        a.seg_chptr = _p(batch.buf.seg_chptr)
+        L = _lib.lib()
+        ea = _edge_attr_args(batch)
+        ws = torch.empty(int(L.kgw_edge_term_workspace_floats(C.byref(a))), device=d_term.device)
+        d_w = torch.empty(dg.schema.NR, 8, device=d_term.device)
+        ea.d_term, ea.d_term_stride, ea.d_w, ea.workspace = _p(d_term), int(d_term.stride(0)), _p(d_w), _p(ws)
+        _lib.check(L.kgw_edge_term_bwd(C.byref(a), C.byref(ea), _lib.stream_ptr()), 'kgw_edge_term_bwd')
+        return (d_w if ctx.width == 8 else d_w[:, :ctx.width]), None, None
+
+
+def _check_edge_attr(batch):
+    dg = batch.dg
+    if getattr(dg, 'g_eattr', None) is None:
+        raise ValueError('the graph carries no edge attributes (data[edge_type].edge_attr)')
+    if getattr(batch, 'exchange', None) is not None:
+        raise NotImplementedError('edge attributes in the SNP-sharded mode are not built')
+    if not _lib.has_edge_attr():
+        raise _lib.KgwasHipError('this libkgwas_hip.so predates the edge-attribute entry points')
+
+
+def edge_logit_term(batch, layer: int, w_edge: torch.Tensor) -> torch.Tensor:
+    """t_e = sum_d A_r[p(e)][d] w_r[d] for every local edge of the layer (the rule: KgwEdgeAttr in include/kgwas_hip.h): the
+    contribution of GATConv's ``edge_dim`` to the attention logit (kgwas/conv.py:207-215 with w_r = lin_edge.weight^T att_edge),
+    to be passed to ``gat_aggregate(..., edge_term=)``.  ``w_edge`` [n_rels, D] or [n_rels, 8] (zero beyond D) by relation id, D =
+    the width of the graph's attributes; rows of relations without attributes are not read and get a zero gradient.
+    Differentiable in ``w_edge`` (k_edge_term_bwd: no atomics, reruns are bit-identical); the attributes get no gradient.
+    Returns [max(n_edges, 1)].  Not in the SNP-sharded mode; the segments a finite fan-out DREW carry no CSR position and get quiet
+    NaN terms (the trainers refuse that combination before it gets here)."""
+    _check_edge_attr(batch)
+    return _EdgeLogitTerm.apply(w_edge, batch, layer)
+
+
 def aggregate_workspace(batch, layer: int, device) -> torch.Tensor:
     """UNINITIALISED Z / stat / d a_dst workspace of ``gat_aggregate(batch, layer, ...)``: hand it to ``rel_vectors(...,
     zero=ws)`` (which clears it in its own launch) and then to ``gat_aggregate(..., zbuf=ws)``."""
@@ -683,7 +765,7 @@ def aggregate_workspace(batch, layer: int, device) -> torch.Tensor:
 def gat_aggregate(batch, layer: int, H: torch.Tensor, U: torch.Tensor, V: torch.Tensor,
                   neg_slope: float = 0.2, temperature: float = 1.0, raw_weights: bool = False,
                   relu_input: bool = False, zbuf: torch.Tensor = None, logit_bias: torch.Tensor = None, dropout=None,
-                  heads: int = 1, sigmoid_gate: bool = False):
+                  heads: int = 1, sigmoid_gate: bool = False, edge_term: torch.Tensor = None):
     """Z[i, r] = sum_j softmax_j(leaky_relu(<H_src[j], u_r> + <H_dst[i], v_r>) / T) H_src[j] for every live relation
     of the layer.  H [n_src_rows,128]: layer input, type-major (``meta.src_base``; a destination node is row i of
     its own type's block); U, V [n_rels,128] by relation id.  Returns (Z [z_rows,128], stat [z_rows,2] =
@@ -709,8 +791,22 @@ def gat_aggregate(batch, layer: int, H: torch.Tensor, U: torch.Tensor, V: torch.
     (kgwas/conv.py:49,219-220): independent gates, no softmax, nothing normalised by the row's degree (KGW_F_SIGMOID_GATE; the rule:
     kgwgate_weight in include/kgwas_hip.h).  Differentiable; takes ``relu_input``, ``logit_bias`` and ``zbuf`` as the softmax does.
     stat is (0, 1) on visited rows and e_edge the leaky_relu logit, as with ``raw_weights``.  Not with ``heads`` != 1, ``dropout``,
-    ``raw_weights`` or the SNP-sharded mode."""
+    ``raw_weights`` or the SNP-sharded mode.
+    ``edge_term`` [n_edges]: ``edge_logit_term``'s output, added to the pre-activation logit of every edge (GATConv's ``edge_dim``);
+    differentiable (its gradient is the backward's d pre_e record, handed on in place).  The softmax, ``raw_weights``,
+    ``relu_input``, ``logit_bias`` and ``zbuf`` take it; not with ``sigmoid_gate``, ``heads`` != 1, ``dropout`` or the SNP-sharded
+    mode."""
     xchg = getattr(batch, 'exchange', None)
+    if edge_term is not None:
+        what = [n for n, v in (('sigmoid_gate', sigmoid_gate), (f'heads={heads}', heads != 1), ('dropout', dropout is not None),
+                               ('the SNP-sharded mode', xchg is not None)) if v]
+        if what:
+            raise NotImplementedError(f'edge_term together with {", ".join(what)} is not built')
+        if not _lib.has_edge_attr():
+            raise _lib.KgwasHipError('this libkgwas_hip.so predates the edge-attribute entry points')
+        stat, e_edge, Z = _GatAggregate.apply(H, U, V, batch, layer, float(neg_slope), 1.0 / float(temperature), raw_weights,
+                                              relu_input, zbuf, logit_bias, None, False, edge_term)
+        return Z, stat, e_edge
     if sigmoid_gate:
         if raw_weights:
             raise ValueError('sigmoid_gate and raw_weights both replace the softmax: one of them')

@@ -25,7 +25,7 @@ import torch
 from . import _lib
 from ._lib import (KGW_CHUNK, KGW_MAX_LAYERS, KGW_MAX_RELS, KGW_MAX_TYPES, KGW_TILE, KgwBatchBuf, KgwBatchMeta,
                    KgwGraph)
-from .graph import GraphSchema, HeteroGraph, build_csr
+from .graph import GraphSchema, HeteroGraph, build_csr, csr_edge_attr
 
 EdgeType = Tuple[str, str, str]
 
@@ -61,6 +61,13 @@ class DeviceGraph:
         ro = co = 0
         out_edges = [0] * sc.NT                        # edges leaving the nodes of each type (all relations)
         self.multi_dst_types = set()                    # destination types that have a row of more than KGW_CHUNK in-edges
+        # edge attributes (data[et].edge_attr, [E] or [E, D], aligned with data[et].edge_index): the rows of every attributed
+        # relation in the order of its CSR entries, one resident matrix (``g_eattr``, sorted and uploaded when first asked for: a
+        # model without gat_edge_dim never does); eattr_off[r] = first row of relation r, -1 = none; eattr_rels = the attributed ones
+        self.eattr_off, self.eattr_dim, self.eattr_rels = [-1] * sc.NR, 0, []
+        self._eattr = {}                                # {'rows': the resident matrix}, shared by the shallow copies of this graph
+        self._eattr_cached_csr = set()                  # relations whose CSR came from the ingest cache
+        ea_row = 0
         for r, et in enumerate(sc.edge_types):
             cached = data._extra.get('csr', {}).get(tuple(et)) if hasattr(data, '_extra') else None
             if cached is not None:                    # kgwas_amd/ingest.py: CSR straight from the on-disk cache
@@ -79,6 +86,19 @@ class DeviceGraph:
             if len(nch) and int(nch.max()) > 1:
                 self.multi_dst_types.add(sc.dst_type[r])
             rowptrs.append(rp.astype(np.int32)); cols.append(col)
+            if data[et].get('edge_attr') is not None:
+                a = data[et]['edge_attr']
+                width = 1 if a.ndim == 1 else int(a.shape[1])
+                if a.ndim > 2 or int(a.shape[0]) != len(col):
+                    raise ValueError(f'edge_attr of {et}: shape {tuple(a.shape)} does not match {len(col)} edges')
+                if self.eattr_dim and width != self.eattr_dim:
+                    raise ValueError(f'edge_attr of {et} has {width} columns, other relations {self.eattr_dim}: one width per graph')
+                self.eattr_dim = width
+                self.eattr_off[r] = ea_row
+                self.eattr_rels.append(r)
+                if cached is not None:
+                    self._eattr_cached_csr.add(r)
+                ea_row += len(col)
             rp_off.append(ro); col_off.append(co)
             ro += len(rp); co += len(col)
         self.seg_cap, self.edge_cap = int(seg_cap), int(edge_cap)
@@ -120,6 +140,30 @@ class DeviceGraph:
         # resident features / labels
         self.x = {t: data[t].x.to(self.device, torch.float32).contiguous() for t in sc.node_types if 'x' in data[t]}
         self.y = {t: data[t].y.to(self.device) for t in sc.node_types if 'y' in data[t]}
+
+    @property
+    def g_eattr(self) -> Optional[torch.Tensor]:
+        """[sum of E_r, D] float32: the attribute rows of the attributed relations, each in the order of its CSR entries (the stable
+        sort of ``build_csr``; with an ingest-cached CSR the recomputed permutation must reproduce the cached columns).  None for a
+        graph without attributes.  Sorted and uploaded on the first request."""
+        if 'rows' not in self._eattr:
+            if not self.eattr_rels:
+                return None
+            sc, rows = self.schema, []
+            for r in self.eattr_rels:
+                et = sc.edge_types[r]
+                col = None
+                if r in self._eattr_cached_csr:
+                    co = int(self.kg.col_off[r])
+                    col = self.g_col[co:co + int(self.data[et].edge_index.shape[1])].cpu().numpy()
+                rows.append(csr_edge_attr(self.data[et]['edge_attr'], self.data[et].edge_index, self.n_nodes[sc.src_type[r]],
+                                          self.n_nodes[sc.dst_type[r]], col))
+            self._eattr['rows'] = torch.from_numpy(np.concatenate(rows)).to(self.device)
+        return self._eattr['rows']
+
+    @g_eattr.setter
+    def g_eattr(self, rows):
+        self._eattr = {'rows': rows}                    # (this object alone: a copy that carries other attributes)
 
     def with_static_caps(self, caps: "BatchCaps") -> "DeviceGraph":
         """Same resident graph, but batches are laid out with fixed row-block capacities (``caps``) so that
@@ -336,6 +380,41 @@ class SampledBatch:
         if self._ei is None:
             self._ei = LazyEdgeIndexDict(self)
         return self._ei
+
+    @property
+    def edge_attr_dict(self):
+        """Edge attributes [E_r, D] of the attributed relations (``data[edge_type].edge_attr``), aligned with the columns of
+        ``edge_index_dict``: what a PyG batch carries as ``edge_attr_dict``.  Built on every access (the fused path never asks: its
+        kernels read the resident rows by CSR position).  Whole rows only: a segment that a finite fan-out drew keeps no record of
+        which entries of its row it holds."""
+        dg, m = self.dg, self.meta
+        sc = dg.schema
+        out = OrderedDict()
+        if getattr(dg, 'g_eattr', None) is None:
+            return out
+        seg_ptr = self.buf.seg_ptr
+        for r, et in enumerate(sc.edge_types):
+            if dg.eattr_off[r] < 0:
+                continue
+            d = int(sc.dst_type[r])
+            ro = int(dg.kg.rowptr_off[r])
+            rp = dg.g_rowptr[ro:ro + dg.n_nodes[d] + 1].long()
+            gid = self.n_id(sc.node_types[d]).long()
+            pos = []
+            for h in range(dg.n_hops):
+                a, b = int(m.seg_off[h][r]), int(m.seg_off[h][r + 1])
+                if b <= a:
+                    continue
+                sp = seg_ptr[a:b + 1].long()
+                deg = sp[1:] - sp[:-1]
+                g = gid[int(m.node_off[d][h]):int(m.node_off[d][h]) + (b - a)]
+                if not torch.equal(deg, rp[g + 1] - rp[g]):
+                    raise NotImplementedError('edge_attr_dict of a batch sampled with a finite fan-out: drawn segments carry no position')
+                first = rp[g] - (sp[:-1] - sp[0])                      # CSR position of a segment's first edge - its local offset
+                pos.append(torch.repeat_interleave(first, deg) + torch.arange(int(sp[-1] - sp[0]), device=dg.device))
+            p = torch.cat(pos) if pos else torch.zeros(0, dtype=torch.long, device=dg.device)
+            out[et] = dg.g_eattr[dg.eattr_off[r] + p]
+        return out
 
     def _build_coo(self):
         dg, m = self.dg, self.meta
