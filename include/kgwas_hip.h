@@ -304,6 +304,62 @@ int kgw_sample_batch_fanout(const KgwGraph* graph, const KgwBatchBuf* buf, const
                             int32_t seed_type, const int32_t* fanout /* [n_hops], host */, const uint64_t* sample_seed_dev,
                             kgw_stream_t stream);
 
+/* Per-epoch order of the training seeds: what PyG's NeighborLoader(shuffle=True) does on the host.  An EXTENSION: the reference
+ * passes no shuffle= (kgwas/kgwas.py:93-94) and visits its seeds in genome order every epoch.  The order of an epoch is a pure
+ * function of (word, n) -- no launch geometry, no sort, no atomics -- so every rank of a multi-GPU run computes the same order
+ * without talking to the others, and anyone can restate it: a 4-round Feistel network on 2 * hb bits, walked along its cycle
+ * until it is back inside [0, n):
+ *      base             = kgwfan_step(kgwfan_step(0, lo32(word)), hi32(word))                                 (kgwperm_base)
+ *      hb               : k = max(2, bit_length(n - 1));  k += k & 1;  hb = k / 2        (1 <= n <= 2^31)     (kgwperm_half_bits)
+ *      feistel(p)       : L = p >> hb, R = p & mask;  four times, r = 0 .. 3:
+ *                             F = kgwfan_mix32(kgwfan_step(base, r) ^ R) & mask;  (L, R) = (R, L ^ F)
+ *                         result (L << hb) | R                                                               (kgwperm_feistel)
+ *      index(base, n, i): p = i;  do p = feistel(p) while (p >= n);  result p                                 (kgwperm_index)
+ * feistel is a bijection of [0, 2^(2 hb)) whatever F is; following i along its cycle until the cycle re-enters [0, n) restricts
+ * it to a bijection of [0, n), and the walk ends because i itself lies on the cycle.  2^(2 hb) <= 4 n, so a walk takes 4
+ * applications or fewer on average.  The rule has no constants of its own.  The trainer sets word to order_word(seed, epoch)
+ * (kgwas_amd/sampler.py).
+ *
+ * Two orders over ids[0 .. n) with GLOBAL batch size B, nb = n / B full batches:
+ *      KGW_ORDER_SEEDS     position p holds ids[index(base, n, p)], every p < n (the n % B left-over seeds differ per epoch);
+ *      KGW_ORDER_BATCHES   the fixed, contiguous batches, visited in another order: position q * B + j (q < nb, j < B) holds
+ *                          ids[index(base, nb, q) * B + j]; positions from nb * B on keep ids[p].
+ * Rank ``rank`` of ``world`` takes positions [i * B + rank * B / world, i * B + (rank + 1) * B / world) of batch i, i < nb (the
+ * slices of the fixed order's multi-GPU runs).  kgw_epoch_order writes them batch after batch: nb * B / world entries, and for
+ * world == 1 the tail behind them, positions nb * B .. n - 1 (several ranks drop the partial batch).  One launch, one index per
+ * element, plain loads and stores; ids and out are device arrays.
+ * n < 1, n > 2^31, B < 1, B % world != 0, a mode other than the two, rank outside [0, world): KGW_E_RANGE, nothing launched.    */
+#define KGW_ORDER_SEEDS   1
+#define KGW_ORDER_BATCHES 2
+KGWFAN_INLINE uint32_t kgwperm_base(uint64_t word) {
+    return kgwfan_step(kgwfan_step(0u, (uint32_t)word), (uint32_t)(word >> 32));
+}
+KGWFAN_INLINE int32_t kgwperm_half_bits(int64_t n) {
+    int32_t k = 0;
+    for (uint64_t v = (uint64_t)(n - 1); v; v >>= 1) ++k;         /* bit_length(n - 1) */
+    if (k < 2) k = 2;
+    k += k & 1;
+    return k / 2;
+}
+KGWFAN_INLINE uint32_t kgwperm_feistel(uint32_t base, int32_t hb, uint32_t p) {
+    const uint32_t mask = (1u << hb) - 1u;
+    uint32_t L = p >> hb, R = p & mask;
+    for (uint32_t r = 0; r < 4u; ++r) {
+        const uint32_t F = kgwfan_mix32(kgwfan_step(base, r) ^ R) & mask;
+        const uint32_t t = L ^ F;
+        L = R; R = t;
+    }
+    return (L << hb) | R;
+}
+KGWFAN_INLINE uint32_t kgwperm_index(uint32_t base, int64_t n, uint32_t i) {       /* i < n <= 2^31 */
+    const int32_t hb = kgwperm_half_bits(n);
+    uint32_t p = i;
+    do p = kgwperm_feistel(base, hb, p); while ((int64_t)p >= n);
+    return p;
+}
+int kgw_epoch_order(const int64_t* ids, int64_t n, int64_t batch, int32_t mode, int32_t rank, int32_t world, uint64_t word,
+                    int64_t* out, kgw_stream_t stream);
+
 /* Attention dropout: alpha = F.dropout(alpha, p, training) after the softmax (kgwas/conv.py:224; the reference's HeteroGNN
  * never passes p, so like the finite fan-out this is an EXTENSION, off by default).  For LOCAL edge e of the batch (the index
  * of col_local / e_edge / adp) in layer l:

@@ -170,7 +170,7 @@ class KgwFoldArgs(C.Structure):
                 ('d_fc_weight', C.c_void_p * 4), ('d_fc_bias', C.c_void_p * 4)]
 
 
-EXPORTS = ['kgw_version', 'kgw_status_string', 'kgw_struct_sizes', 'kgw_sample_batch', 'kgw_sample_batch_parts', 'kgw_sample_batch_fanout', 'kgw_sampler_scan_ints', 'kgw_segments_copy',
+EXPORTS = ['kgw_version', 'kgw_status_string', 'kgw_struct_sizes', 'kgw_sample_batch', 'kgw_sample_batch_parts', 'kgw_sample_batch_fanout', 'kgw_epoch_order', 'kgw_sampler_scan_ints', 'kgw_segments_copy',
            'kgw_softmax_pack', 'kgw_softmax_merge', 'kgw_scatter_rows', 'kgw_linear_splitk', 'kgw_linear_splitk_workspace_floats', 'kgw_linear_splitk_ind', 'kgw_ind_colsum', 'kgw_linear_splitk_multi', 'kgw_ind_colsum_multi', 'kgw_fold_fwd', 'kgw_fold_bwd', 'kgw_relation_sums',
            'kgw_gat_aggregate_fwd', 'kgw_gat_aggregate_bwd_dst', 'kgw_gat_aggregate_bwd_src',
            'kgw_edge_term_fwd', 'kgw_edge_term_bwd', 'kgw_edge_term_workspace_floats', 'kgw_gat_aggregate_fwd_eterm',
@@ -219,6 +219,9 @@ def lib():
     if hasattr(L, 'kgw_sample_batch_fanout'):       # (absent from an older library named by KGW_LIB_PATH for an A/B run)
         L.kgw_sample_batch_fanout.argtypes = [C.POINTER(KgwGraph), C.POINTER(KgwBatchBuf), C.c_void_p, C.c_int32, C.c_int32,
                                               C.POINTER(C.c_int32), C.c_void_p, C.c_void_p]
+    if hasattr(L, 'kgw_epoch_order'):               # (absent from an older library named by KGW_LIB_PATH for an A/B run)
+        L.kgw_epoch_order.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_uint64, C.c_void_p,
+                                      C.c_void_p]
     L.kgw_sampler_scan_ints.argtypes = [C.c_int64, C.c_int64, C.c_int64]
     L.kgw_sampler_scan_ints.restype = C.c_int64
     L.kgw_segments_copy.argtypes = [C.POINTER(KgwSegCopy), C.c_int32, C.c_void_p]
@@ -371,6 +374,16 @@ def has_edge_attr() -> bool:
     """Does the loaded library have the edge-attribute entry points (kgw_edge_term_fwd, kgw_edge_term_bwd,
     kgw_gat_aggregate_fwd_eterm)?  An older library named by KGW_LIB_PATH for an A/B run lacks the symbols."""
     return hasattr(lib(), 'kgw_gat_aggregate_fwd_eterm')
+
+
+KGW_ORDER_SEEDS, KGW_ORDER_BATCHES = 1, 2     # kgw_epoch_order's modes (include/kgwas_hip.h)
+EPOCH_ORDER_BLOCK, EPOCH_ORDER_GRID = 256, 2048   # its launch: threads per block, most blocks (KGW_BLK, KGW_GRID of csrc/kgw_common.h)
+
+
+def has_epoch_order() -> bool:
+    """Does the loaded library have kgw_epoch_order (the per-epoch order of the training seeds)?  An older library named by
+    KGW_LIB_PATH for an A/B run lacks the symbol."""
+    return hasattr(lib(), 'kgw_epoch_order')
 
 
 def check(status: int, what: str):

@@ -1350,6 +1350,63 @@ extern "C" int kgw_segments_copy(const KgwSegCopy* plan, int32_t grid_blocks, kg
     return KGW_OK;
 }
 
+// ---- the epoch's order of the training seeds (kgwperm_index, include/kgwas_hip.h) -------------------------------------------------
+// One thread per entry of this rank's share of the order: entry o -> position p of the epoch -> the index kgwperm_index names ->
+// one 8-byte load of ids, one 8-byte store.  The cycle walk's trip count differs from lane to lane (mean <= 4 applications of
+// the four-round network, ~40 at worst): a plain divergent loop, no cross-lane traffic.  Launched once per epoch, ~0.5 M entries
+// at the benchmark's shape.
+namespace {
+struct OrderArgs {
+    const int64_t* ids;
+    int64_t* out;
+    int64_t n, batch, per, nb, total;     // per = batch / world; nb = n / batch; total = entries this rank writes
+    int32_t mode, rank;
+    uint32_t base;
+};
+
+__global__ void __launch_bounds__(KGW_BLK) k_epoch_order(OrderArgs A) {
+    const int64_t full = A.nb * A.per;                               // entries of the full batches; the tail follows (one rank only)
+    for (int64_t o = (int64_t)blockIdx.x * KGW_BLK + threadIdx.x; o < A.total; o += (int64_t)gridDim.x * KGW_BLK) {
+        int64_t p;                                                   // position of the epoch this entry holds
+        if (o < full) {
+            const int64_t q = o / A.per;
+            p = q * A.batch + A.rank * A.per + (o - q * A.per);
+        } else {
+            p = A.nb * A.batch + (o - full);
+        }
+        int64_t s;                                                   // index into ids
+        if (A.mode == KGW_ORDER_SEEDS) {
+            s = kgwperm_index(A.base, A.n, (uint32_t)p);
+        } else if (o < full) {
+            const int64_t q = p / A.batch;
+            s = (int64_t)kgwperm_index(A.base, A.nb, (uint32_t)q) * A.batch + (p - q * A.batch);
+        } else {
+            s = p;
+        }
+        A.out[o] = A.ids[s];
+    }
+}
+}  // namespace
+
+extern "C" int kgw_epoch_order(const int64_t* ids, int64_t n, int64_t batch, int32_t mode, int32_t rank, int32_t world,
+                               uint64_t word, int64_t* out, kgw_stream_t stream_) {
+    if (n < 1 || n > ((int64_t)1 << 31) || batch < 1 || world < 1 || batch % world != 0) return KGW_E_RANGE;
+    if ((mode != KGW_ORDER_SEEDS && mode != KGW_ORDER_BATCHES) || rank < 0 || rank >= world) return KGW_E_RANGE;
+    if (!ids || !out) return KGW_E_NULL;
+    OrderArgs A;
+    A.ids = ids; A.out = out;
+    A.n = n; A.batch = batch; A.per = batch / world; A.nb = n / batch;
+    A.total = A.nb * A.per + (world == 1 ? n - A.nb * batch : 0);
+    A.mode = mode; A.rank = rank;
+    A.base = kgwperm_base(word);
+    if (A.total == 0) return KGW_OK;
+    int64_t g = (A.total + KGW_BLK - 1) / KGW_BLK;
+    if (g > KGW_GRID) g = KGW_GRID;
+    k_epoch_order<<<(int)g, KGW_BLK, 0, (hipStream_t)stream_>>>(A);
+    KGW_LAUNCH_CHECK();
+    return KGW_OK;
+}
+
 // ---- x[n_id] feature slicing ---------------------------------------------------------------------
 namespace {
 constexpr int GATHER_MAX_JOBS = 8;

@@ -137,7 +137,9 @@ class BatchCache:
     sized by the trainer's static capacities -- into the batch's slot of a resident cache (kgw_segments_copy); from epoch 2 on one
     launch copies the slot back into the idle batch buffer where the sampler's ~25 launches ran.  Same bytes in the same
     buffers => the step's kernels produce the same bits as after live sampling (tests/test_gpu_graph.py).  19 GB for the
-    956 batches of the benchmark; a cache that would take more than ``max_fraction`` of the free HBM is not made."""
+    956 batches of the benchmark; a cache that would take more than ``max_fraction`` of the free HBM is not made.
+    epoch_order='batches' visits the same batches in another order every epoch: the slot of a step is then the batch of the fixed
+    order it trains on (GraphTrainStep._slot); epoch_order='seeds' and a finite fan-out have no batch to keep."""
 
     def __init__(self, dg, bufs, n_batches: int, max_fraction: float = 0.5):
         self.n_batches = int(n_batches)
@@ -231,14 +233,22 @@ class BatchCache:
 class GraphTrainStep:
     def __init__(self, run, input_nodes, batch_size: int, lr: float = 1e-4, weight_decay: float = 5e-4,
                  margin: float = 1.03, shard_gene_layer: bool = None, cache_batches: bool = False, num_neighbors=None,
-                 sample_seed: int = 0):
+                 sample_seed: int = 0, epoch_order: str = 'fixed', epochs: int = None, rank: int = 0, world: int = 1):
         """``num_neighbors`` (None = the reference's [-1] * L): PyG's list form of per-hop fan-outs.  With a finite fan-out the
         batches are redrawn every epoch from (``sample_seed``, epoch, batch index) -- ``set_epoch`` names the epoch, a step past
         the last batch moves on to the next one by itself -- the capacities of the static layout are bounds that hold for every
         draw (NeighborLoader.measure_caps), and no batch is kept for later epochs (BatchCache off).
         A model with ``gat_dropout > 0``: the step is captured in training mode (whatever mode the model is in; restored afterwards)
         and every ``step`` copies the 8-byte word of (``sample_seed``, epoch, batch index) into ``model.drop_word`` ahead of the
-        replay -- the kernels read it when they run.  The batches themselves stay the same from epoch to epoch (BatchCache on)."""
+        replay -- the kernels read it when they run.  The batches themselves stay the same from epoch to epoch (BatchCache on).
+        ``epoch_order`` ('fixed' | 'seeds' | 'batches', NeighborLoader): the order in which an epoch visits the seeds, a pure function
+        of (``sample_seed``, epoch) written on the device once per epoch (kgw_epoch_order); ``step(i)`` trains on batch i of the epoch
+        ``set_epoch`` named, and a step past the last batch moves on to the next epoch by itself.  'seeds': the batches of every
+        epoch are its own, so the static capacities are measured over exactly the batches of epochs 0 .. ``epochs`` - 1 (and batch 0
+        of epoch ``epochs``, sampled ahead and never trained on) -- an epoch outside that range is a ValueError -- and no batch is
+        kept (BatchCache off).  'batches': the fixed order's batches in another order; the cache stays on, its slot the SOURCE batch
+        of a step, while the fan-out and dropout words stay functions of the step's position i.  Several ranks that shuffle
+        (``rank`` of ``world``): ``input_nodes`` are the GLOBAL ids, ``batch_size`` this rank's share of the global batch."""
         self.run = run
         self.model = run.model
         self.batch_size = int(batch_size)
@@ -250,11 +260,16 @@ class GraphTrainStep:
         self.fanout = check_num_neighbors(num_neighbors) if num_neighbors is not None else None
         self.sample_seed, self.epoch = int(sample_seed), 0
         probe = NeighborLoader(run.data.data, self.fanout if self.fanout is not None else [-1] * L, (self.input_type, ids),
-                               batch_size=self.batch_size, drop_last=True, device=dev, prefetch=False, seed=self.sample_seed)
+                               batch_size=self.batch_size, drop_last=True, device=dev, prefetch=False, seed=self.sample_seed,
+                               epoch_order=epoch_order, rank=rank, world=world)
+        self.epoch_order, self._probe_loader = epoch_order, probe
+        self.redrawn = probe.redrawn                    # (a buffer holds batch i OF AN EPOCH)
+        # 'seeds': the epochs the capacities were measured for
+        self.epochs = max(1, int(epochs) if epochs is not None else 1) if epoch_order == 'seeds' else None
         self.n_batches = len(probe)
         if self.n_batches == 0:
             raise ValueError('no full batch in input_nodes')
-        self.caps = probe.measure_caps(margin)
+        self.caps = probe.measure_caps(margin, epochs=self.epochs or 1)
         self.dg = probe.dg.with_static_caps(self.caps)
         self.seed_type = probe.seed_type
         self.ids = probe.ids
@@ -265,6 +280,7 @@ class GraphTrainStep:
         # finite fan-out: the 64-bit sample seed the (captured) sampler reads, fed like ``seeds``; the words of an epoch's batches
         self.sample_word = torch.zeros(1, dtype=torch.int64, device=dev) if self.fanout is not None else None
         self._epoch_words = {}
+        self._orders, self._sources = {}, {}            # shuffled orders: {epoch: (order tensor, written-event, streams told)}, {epoch: source batches}
         # attention dropout: the words of an epoch's batches (like the fan-out's), copied one at a time into model.drop_word
         self.dropout = float(getattr(self.model, 'gat_dropout', 0.0)) > 0.0
         self._drop_words = {}
@@ -336,7 +352,8 @@ class GraphTrainStep:
         # ``cache_batches`` (KGWAS.train with more than one epoch; off for a bench line -- the headline samples live): the batches of
         # the first pass over the loader are kept and put back in later passes instead of being sampled again (BatchCache)
         self.cache = None
-        self._want_cache = bool(cache_batches) and os.environ.get('KGW_EPOCH_CACHE', '1') != '0' and self.fanout is None
+        self._want_cache = (bool(cache_batches) and os.environ.get('KGW_EPOCH_CACHE', '1') != '0' and self.fanout is None and
+                            epoch_order != 'seeds')
         # (parameter-only kernels on a parallel branch of the captured step: measured again in round 5 -- 1.397 ms against 1.081, and
         #  the branch's queue displaces the side sampler's, overlap ratio -0.14 -- HIP-graph branches are not a tool here; removed)
         if self.dropout:
@@ -498,8 +515,39 @@ class GraphTrainStep:
                     sample_word=self.sample_word)
 
     def set_epoch(self, epoch: int):
-        """Finite fan-out / attention dropout: the epoch the next ``step`` calls draw for."""
+        """Finite fan-out / attention dropout / a shuffled order: the epoch the next ``step`` calls draw for."""
+        self._check_epoch(int(epoch))
         self.epoch = int(epoch)
+
+    def _check_epoch(self, epoch: int):
+        if self.epochs is not None and not 0 <= epoch < self.epochs:
+            raise ValueError(f"epoch {epoch}: the static layout of this trainer holds the batches of epochs 0 .. {self.epochs - 1} "
+                             f"(epoch_order='seeds', epochs={self.epochs})")
+
+    def _order(self, epoch: int) -> torch.Tensor:
+        """The epoch's order tensor for a reader on the current stream: written there by kgw_epoch_order when first asked for,
+        the previous epoch's kept beside it (a prefetch may still read it)."""
+        ent = self._orders.get(epoch)
+        st = torch.cuda.current_stream()
+        if ent is None:
+            self._orders = {e: v for e, v in self._orders.items() if e >= epoch - 1}
+            t, ev = self._probe_loader.order_tensor(epoch), torch.cuda.Event()
+            ev.record(st)
+            ent = self._orders[epoch] = (t, ev, {st.cuda_stream})
+        elif st.cuda_stream not in ent[2]:
+            st.wait_event(ent[1])
+            ent[0].record_stream(st)
+            ent[2].add(st.cuda_stream)
+        return ent[0]
+
+    def _slot(self, i: int, epoch: int) -> int:
+        """The cache slot of batch i of ``epoch``: the batch of the fixed order it is."""
+        if self.epoch_order != 'batches':
+            return i
+        if epoch not in self._sources:
+            self._sources = {e: v for e, v in self._sources.items() if e >= epoch - 1}
+            self._sources[epoch] = [self._probe_loader.source_batch(epoch, k) for k in range(self.n_batches)]
+        return self._sources[epoch][i]
 
     def _feed_dropout(self, i: int, epoch: int):
         """The dropout word of batch i of ``epoch`` into ``model.drop_word``: one 8-byte device copy on the current stream."""
@@ -509,12 +557,13 @@ class GraphTrainStep:
 
     def _key(self, i: int, epoch: int) -> int:
         """What a buffer holds: batch i -- of epoch ``epoch`` when batches are redrawn every epoch."""
-        return i if self.fanout is None else epoch * self.n_batches + i
+        return i if not self.redrawn else epoch * self.n_batches + i
 
     def _feed(self, i: int, epoch: int):
         """Seeds (and sample seed) of batch i into the tensors the sampler reads, on the current stream."""
         b = self.batch_size
-        self.seeds.copy_(self.ids[i * b:(i + 1) * b])
+        src = self.ids if self.epoch_order == 'fixed' else self._order(epoch)
+        self.seeds.copy_(src[i * b:(i + 1) * b])
         if self.fanout is not None:
             if epoch not in self._epoch_words:
                 self._epoch_words = {e: w for e, w in self._epoch_words.items() if e >= epoch - 1}
@@ -526,13 +575,14 @@ class GraphTrainStep:
     def _sample_now(self, which: int, i: int):
         if self.cache is not None:
             torch.cuda.current_stream().wait_stream(self._side)    # (the cache's slot index is shared with the side stream's launches)
-        if self.cache is not None and self.cache.filled[i]:
-            self.cache.restore(which, i)
+        slot = self._slot(i, self.epoch) if self.cache is not None else i
+        if self.cache is not None and self.cache.filled[slot]:
+            self.cache.restore(which, slot)
         else:
             self._feed(i, self.epoch)
             self._sample(which)
             if self.cache is not None:
-                self.cache.save(which, i)
+                self.cache.save(which, slot)
         self._sampler.holds[which] = self._key(i, self.epoch)
 
     def _capture(self):
@@ -622,19 +672,21 @@ class GraphTrainStep:
     def _prefetch(self, which: int, i: int, epoch: int):
         """Batch i of ``epoch`` into bufs[which], on the current (the side) stream."""
         cache = self.cache if not self._skip_resample else None
-        if cache is not None and cache.filled[i]:
-            cache.restore(which, i)                             # (a later epoch: one copy launch instead of the sampler's ~25)
+        slot = self._slot(i, epoch) if cache is not None else i
+        if cache is not None and cache.filled[slot]:
+            cache.restore(which, slot)                          # (a later epoch: one copy launch instead of the sampler's ~25)
         else:
             self._feed(i, epoch)
             if not self._skip_resample:
                 self.sample_graphs[which].replay()
                 if cache is not None:
-                    cache.save(which, i)
+                    cache.save(which, slot)
 
     def step(self, i: int):
         """Train on batch ``i`` of the loader's fixed order (and pre-sample batch i+1); returns the (device,
         float64) loss tensor."""
         cur, sam = i % 2, self._sampler
+        self._check_epoch(self.epoch)
         if self._image_params:
             self._refresh_images()               # (a weight changed by anything but this trainer's own optimiser launch: re-pack)
         if sam.holds[cur] != self._key(i, self.epoch):       # first call / non-sequential access: sample it now
@@ -653,7 +705,7 @@ class GraphTrainStep:
             self._feed_dropout(i, self.epoch)
         self.graphs[cur].replay()
         sam.holds[cur] = -1
-        if (self.fanout is not None or self.dropout) and nxt == 0:
+        if (self.redrawn or self.dropout) and nxt == 0:
             self.epoch = nxt_epoch               # (a pass is over: the next one draws anew unless set_epoch says otherwise)
         if self.split_backward:
             from . import dist as kdist

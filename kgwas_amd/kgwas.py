@@ -120,16 +120,22 @@ class KGWAS:
         w[torch.from_numpy(ids)] = torch.from_numpy(np.asarray(self.data.ldsc_weight, dtype=np.float64))
         return w.to(self.device)
 
-    def make_loaders(self, batch_size, num_workers=0, num_neighbors=None):
+    def make_loaders(self, batch_size, num_workers=0, num_neighbors=None, epoch_order='fixed'):
         """``num_neighbors`` (extra, None = the reference's [-1] * L): fan-outs of the TRAINING loader only; validation, test
-        and inference always take full neighbourhoods, as the reference does."""
+        and inference always take full neighbourhoods, as the reference does.  ``epoch_order`` (extra, 'fixed' = the reference):
+        the per-epoch order of the TRAINING loader's seeds (NeighborLoader); the other loaders keep the order given."""
         kwargs = {'batch_size': batch_size, 'num_workers': num_workers, 'drop_last': True, 'device': self.device}
         eval_kwargs = {'batch_size': 512, 'num_workers': num_workers, 'drop_last': False, 'device': self.device}
         L = self.gnn_num_layers
         rank, world = kdist.rank_world()
         tr_type, tr_ids = self.data.train_input_nodes
-        tr_ids = kdist.shard_batches(np.asarray(tr_ids), batch_size, rank, world)
-        tr_kwargs = dict(kwargs, batch_size=batch_size // world)      # each rank: its slice of every batch
+        if epoch_order == 'fixed':
+            tr_ids = kdist.shard_batches(np.asarray(tr_ids), batch_size, rank, world)
+            tr_kwargs = dict(kwargs, batch_size=batch_size // world)      # each rank: its slice of every batch
+        else:                                                             # (a shuffled order: the loader slices the epoch's order)
+            if batch_size % world:
+                raise ValueError(f'batch_size {batch_size} must be divisible by world size {world}')
+            tr_kwargs = dict(kwargs, batch_size=batch_size // world, epoch_order=epoch_order, rank=rank, world=world)
         self.train_loader = NeighborLoader(self.data.data, num_neighbors=[-1] * L if num_neighbors is None else num_neighbors,
                                            sampler=None, input_nodes=(tr_type, tr_ids), seed=self.seed, **tr_kwargs)        # kgwas.py:99-101
         self.val_loader = NeighborLoader(self.data.data, num_neighbors=[-1] * L,
@@ -214,7 +220,7 @@ class KGWAS:
         self.shard_bytes_moved = st.xchg.bytes_moved
 
     def train(self, batch_size=512, num_workers=0, lr=1e-4, weight_decay=5e-4, epoch=10, save_best_model=True,
-              save_name=None, data_to_cuda=False, use_graph=True, parallelism='seed', num_neighbors=None):
+              save_name=None, data_to_cuda=False, use_graph=True, parallelism='seed', num_neighbors=None, shuffle=False):
         """Same signature and defaults as kgwas/kgwas.py:85-87.  ``use_graph`` (extra, default on): run the
         training step as one captured HIP graph (kgwas_amd/graph_step.py); off = eager launches, same math.
         ``parallelism`` (extra; matters under torch.distributed): 'seed' = every rank trains on its slice of each batch
@@ -222,8 +228,23 @@ class KGWAS:
         (kgwas_amd/shard.py, BASELINE.json north_star).
         ``num_neighbors`` (extra, default None = the reference's [-1] * L): PyG's list form [k_1, ..., k_L] for the TRAINING
         loader -- at most k_h in-edges per (node, relation) at hop h, redrawn every epoch from (the run's seed, epoch, batch
-        index); evaluation and inference keep full neighbourhoods.  Not available with parallelism='shard'."""
+        index); evaluation and inference keep full neighbourhoods.  Not available with parallelism='shard'.
+        ``shuffle`` (extra, default False = the reference, which visits its training SNPs in genome order every epoch,
+        kgwas/kgwas.py:93-94): True = every epoch visits the training seeds in an order of its own (what PyG's shuffle=True means;
+        NeighborLoader(epoch_order='seeds')), 'batches' = the fixed order's genome-contiguous batches, visited in another order
+        every epoch.  The order is a pure function of (the run's seed, epoch), the same on every rank.  An argument of the run,
+        not of the model: nothing enters config.pkl.  Validation, test and inference keep their order.  Not available with
+        parallelism='shard'."""
         total_epoch = epoch
+        if isinstance(shuffle, (bool, np.bool_)):
+            epoch_order = 'seeds' if shuffle else 'fixed'
+        elif isinstance(shuffle, str) and shuffle == 'batches':
+            epoch_order = 'batches'
+        else:
+            raise ValueError(f"shuffle {shuffle!r}: False, True or 'batches'")
+        if epoch_order != 'fixed' and parallelism == 'shard':
+            raise NotImplementedError("shuffle is not available with parallelism='shard': the sharded trainer walks the fixed "
+                                      "order's batches")
         if num_neighbors is not None:
             from .sampler import check_num_neighbors
             if not isinstance(num_neighbors, dict) and len(num_neighbors) != self.gnn_num_layers:
@@ -244,7 +265,7 @@ class KGWAS:
         if parallelism != 'seed':
             raise ValueError(f"parallelism {parallelism!r}: 'seed' or 'shard'")
         print_sys('Creating data loader...')
-        self.make_loaders(batch_size, num_workers, num_neighbors)
+        self.make_loaders(batch_size, num_workers, num_neighbors, epoch_order)
         rank, world = kdist.rank_world()
         if world > 1:
             kdist.broadcast_params(self.model)
@@ -253,9 +274,10 @@ class KGWAS:
             from .graph_step import GraphTrainStep
             # (multi-GPU: a 512-seed batch split over the ranks = strong scaling; from 4 ranks on the batch-independent first gene
             #  Linear is split by gene rows instead of repeated on every rank -- ops.GeneLayerShard)
+            shuffled = {} if epoch_order == 'fixed' else {'epoch_order': epoch_order, 'epochs': total_epoch, 'rank': rank, 'world': world}
             graph_step = GraphTrainStep(self, (self.train_loader.input_type, self.train_loader.ids.cpu().numpy()),
                                         self.train_loader.batch_size, lr=lr, weight_decay=weight_decay,
-                                        shard_gene_layer=None,
+                                        shard_gene_layer=None, **shuffled,
                                         # (the loader's batch order is fixed, kgwas.py:93-101: the batches sampled in epoch 1 are
                                         #  kept in HBM and put back in later epochs -- graph_step.BatchCache)
                                         cache_batches=total_epoch > 1, num_neighbors=num_neighbors, sample_seed=self.seed)
@@ -269,7 +291,7 @@ class KGWAS:
         print_sys('Start Training...')
         for ep in range(total_epoch):
             self.model.train()
-            if num_neighbors is not None:                            # (a finite fan-out draws anew every epoch)
+            if num_neighbors is not None or epoch_order != 'fixed':  # (a finite fan-out draws anew every epoch, a shuffle orders anew)
                 (graph_step if graph_step is not None else self.train_loader).set_epoch(ep)
             elif dropout and graph_step is not None:                 # (so do the dropout masks, on the same batches)
                 graph_step.set_epoch(ep)

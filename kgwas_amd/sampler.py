@@ -11,7 +11,8 @@ What differs from PyG by design (MI355X-first):
   * a batch carries the per-layer block structure the fused kernels consume (chunk lists,
     src-major transpose) and exposes COO ``edge_index_dict`` / gathered ``x_dict`` lazily, only for
     callers that ask for them;
-  * no shuffle (the reference passes none, kgwas.py:93-94), ``num_workers`` is accepted and ignored.
+  * the seeds are visited in the order given (the reference passes no shuffle=, kgwas.py:93-94) unless ``epoch_order`` asks for
+    a per-epoch order, written on the device (kgw_epoch_order); ``num_workers`` is accepted and ignored.
 """
 from __future__ import annotations
 
@@ -638,6 +639,73 @@ def dropout_words(seed: int, epoch: int, n_batches: int, device) -> torch.Tensor
     return torch.from_numpy(w.copy()).to(device)
 
 
+_ORDER_TAG = 0x73687566666C6521         # the bytes of 'shuffle!'
+EPOCH_ORDERS = {'seeds': _lib.KGW_ORDER_SEEDS, 'batches': _lib.KGW_ORDER_BATCHES}      # ('fixed': no call)
+
+
+def order_word(seed: int, epoch: int) -> int:
+    """The 64-bit word of the order in which epoch ``epoch`` of a run made with ``seed`` visits its training seeds: the
+    splitmix64 rounds of ``dropout_word`` behind a tag of its own, so that an epoch's order is tied neither to its fan-out draws
+    nor to its dropout masks.  (The kernel's rule takes it from there: kgwperm_index in include/kgwas_hip.h.)"""
+    z = _splitmix64(_ORDER_TAG)
+    z = _splitmix64(z ^ (int(seed) & _M64))
+    return _splitmix64(z ^ (int(epoch) & _M64))
+
+
+def _mix32(h: int) -> int:
+    h ^= h >> 16; h = (h * 0x85EBCA6B) & 0xFFFFFFFF
+    h ^= h >> 13; h = (h * 0xC2B2AE35) & 0xFFFFFFFF
+    return h ^ (h >> 16)
+
+
+def _fan_step(h: int, x: int) -> int:
+    return _mix32(((h ^ (x & 0xFFFFFFFF)) + 0x9E3779B9) & 0xFFFFFFFF)
+
+
+def epoch_order_index(word: int, n: int, i: int) -> int:
+    """kgwperm_index(kgwperm_base(word), n, i) of include/kgwas_hip.h in python ints: the index that position ``i`` of an order
+    over ``n`` elements holds.  For small n -- the source batch of a step when whole batches are shuffled; the orders themselves
+    are written on the device (kgw_epoch_order)."""
+    n, i, word = int(n), int(i), int(word) & _M64
+    if not 0 <= i < n <= 1 << 31:
+        raise ValueError(f'epoch_order_index: 0 <= i < n <= 2^31, got i = {i}, n = {n}')
+    base = _fan_step(_fan_step(0, word & 0xFFFFFFFF), word >> 32)
+    k = max(2, (n - 1).bit_length())
+    hb = (k + (k & 1)) // 2
+    mask = (1 << hb) - 1
+    keys = [_fan_step(base, r) for r in range(4)]
+    p = i
+    while True:
+        L, R = p >> hb, p & mask
+        for key in keys:
+            L, R = R, L ^ (_mix32(key ^ R) & mask)
+        p = (L << hb) | R
+        if p < n:
+            return p
+
+
+def epoch_order_len(n: int, batch: int, world: int = 1) -> int:
+    """Entries of kgw_epoch_order's output for one rank: its slice of every full batch, and for a single rank the partial one."""
+    nb = n // batch
+    return nb * (batch // world) + (n - nb * batch if world == 1 else 0)
+
+
+def epoch_order(ids: torch.Tensor, batch: int, mode: str, word: int, rank: int = 0, world: int = 1,
+                out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """This rank's positions of the epoch's order over the int64 device tensor ``ids`` (kgw_epoch_order, on the current stream):
+    ``mode`` 'seeds' or 'batches', ``batch`` the GLOBAL batch size, ``word`` = order_word(seed, epoch)."""
+    if not _lib.has_epoch_order():
+        raise _lib.KgwasHipError('the loaded libkgwas_hip.so has no kgw_epoch_order: rebuild it')
+    assert ids.dtype == torch.int64 and ids.is_cuda and ids.is_contiguous()
+    n = int(ids.numel())
+    if out is None:
+        out = torch.empty(epoch_order_len(n, batch, world) if n >= 1 and batch >= 1 and world >= 1 else 0, dtype=torch.int64,
+                          device=ids.device)
+    _lib.check(_lib.lib().kgw_epoch_order(_ptr(ids), n, int(batch), EPOCH_ORDERS[mode], int(rank), int(world),
+                                          int(word) & _M64, _ptr(out), _lib.stream_ptr()), 'kgw_epoch_order')
+    return out
+
+
 def dropout_params(p: float):
     """(thresh, scale) of the kernels' rule for drop probability ``p``: floor(p * 2^32) from the double, float32(1 / (1 - p))."""
     p = float(p)
@@ -677,21 +745,39 @@ def sample_full_graph(data: HeteroGraph, num_layers: int, device) -> SampledBatc
 class NeighborLoader:
     def __init__(self, data: HeteroGraph, num_neighbors: Sequence[int], input_nodes, batch_size: int = 512,
                  drop_last: bool = False, num_workers: int = 0, shuffle: bool = False, sampler=None,
-                 device=None, prefetch: bool = True, seed: int = 0, replace: bool = False, **kwargs):
+                 device=None, prefetch: bool = True, seed: int = 0, replace: bool = False, epoch_order: str = 'fixed',
+                 rank: int = 0, world: int = 1, **kwargs):
         """``num_neighbors``: [-1] * L as the reference (kgwas/kgwas.py:99-113), or PyG's list form [k_1, ..., k_L] (each -1 or
         >= 1; k_h in-edges per (node, relation) at hop h, uniformly without replacement).  A finite fan-out is redrawn every
         epoch from (``seed``, epoch, batch index): ``set_epoch(e)`` names the epoch of the next pass, else every pass after the
-        first advances it by one."""
+        first advances it by one.
+        ``epoch_order``: 'fixed' (the reference: the seeds in the order given, every epoch), 'seeds' (what PyG's shuffle=True
+        means: every epoch visits the seeds in an order of its own) or 'batches' (the fixed order's batches, visited in another
+        order every epoch).  The order is a pure function of (``seed``, epoch) -- kgwperm_index, include/kgwas_hip.h -- written
+        on the device once per pass (kgw_epoch_order); ``seed`` and ``set_epoch`` drive it as they drive the fan-out's draw.
+        ``rank`` / ``world`` (several ranks, each its slice of every batch): ``input_nodes`` are the GLOBAL ids and ``batch_size``
+        is this rank's share of the global batch, world * batch_size; the partial last batch is dropped (``drop_last``)."""
         self.fanout = check_num_neighbors(num_neighbors)
         if replace:
             raise NotImplementedError('sampling with replacement is not supported')
         if shuffle:
-            raise NotImplementedError('the reference never shuffles (kgwas/kgwas.py:93-94)')
+            raise NotImplementedError("shuffle=True is not taken (the reference never shuffles, kgwas/kgwas.py:93-94): ask for a "
+                                      "per-epoch order with epoch_order='seeds' or epoch_order='batches'")
+        if epoch_order != 'fixed' and epoch_order not in EPOCH_ORDERS:
+            raise ValueError(f"epoch_order {epoch_order!r}: 'fixed', 'seeds' or 'batches'")
+        rank, world = int(rank), int(world)
+        if world < 1 or not 0 <= rank < world:
+            raise ValueError(f'rank {rank} of {world}')
+        if world > 1 and epoch_order == 'fixed':
+            raise ValueError('the fixed order takes the slice of this rank as input_nodes (dist.shard_batches), not rank / world')
+        if world > 1 and not drop_last:
+            raise ValueError('several ranks share full batches only: drop_last=True')
         self.data = data
         self.num_layers = len(num_neighbors)
         self.input_type, ids = input_nodes
         ids = np.asarray(ids.cpu() if torch.is_tensor(ids) else ids, dtype=np.int64).reshape(-1)
         self.batch_size = int(batch_size)
+        self.epoch_order, self.rank, self.world = epoch_order, rank, world
         self.drop_last = drop_last
         self.device = torch.device(device if device is not None else 'cuda')
         self.dg = DeviceGraph.get(data, self.num_layers, self.device)
@@ -699,6 +785,9 @@ class NeighborLoader:
         if ids.size and (ids.min() < 0 or ids.max() >= self.dg.n_nodes[self.seed_type]):
             raise ValueError('input_nodes out of range')
         self.ids = torch.from_numpy(ids).to(self.device)
+        # seeds this rank visits in a pass (a shuffled order: its share of the global ids)
+        self.n_seeds = len(ids) if epoch_order == 'fixed' else \
+            (epoch_order_len(len(ids), self.batch_size * world, world) if len(ids) else 0)
         self.prefetch = prefetch
         self._bufs = None
         self._stream = None
@@ -706,15 +795,36 @@ class NeighborLoader:
         self.epoch = 0
         self._epoch_set = True                       # (the next pass runs at self.epoch; later passes advance it themselves)
         self._words = None
+        self._orders = {}                            # {epoch: its order tensor}: the running pass's and the one before
+
+    @property
+    def redrawn(self) -> bool:
+        """Do the batches of a pass depend on its epoch?"""
+        return self.fanout is not None or self.epoch_order != 'fixed'
 
     def set_epoch(self, epoch: int):
-        """Epoch of the next pass over the loader (a finite fan-out draws from (seed, epoch, batch index))."""
+        """Epoch of the next pass over the loader (a finite fan-out draws from (seed, epoch, batch index), a shuffled order is
+        that of (seed, epoch))."""
         self.epoch = int(epoch)
         self._epoch_set = True
 
     def __len__(self):
-        n = self.ids.numel()
+        n = self.n_seeds
         return n // self.batch_size if self.drop_last else (n + self.batch_size - 1) // self.batch_size
+
+    def order_tensor(self, epoch: int) -> Optional[torch.Tensor]:
+        """int64 device tensor: the seeds of this rank in the order epoch ``epoch`` visits them, written on the CURRENT stream
+        (None for the fixed order: ``self.ids`` is it)."""
+        if self.epoch_order == 'fixed':
+            return None
+        return epoch_order(self.ids, self.batch_size * self.world, self.epoch_order, order_word(self.seed, epoch), self.rank,
+                           self.world)
+
+    def source_batch(self, epoch: int, i: int) -> int:
+        """Which batch of the fixed order is batch ``i`` of epoch ``epoch``?  (epoch_order='batches'; the partial last batch stays.)"""
+        assert self.epoch_order == 'batches'
+        nb = int(self.ids.numel()) // (self.batch_size * self.world)
+        return epoch_order_index(order_word(self.seed, epoch), nb, i) if i < nb else i
 
     def _ensure(self):
         if self._bufs is None:
@@ -726,8 +836,8 @@ class NeighborLoader:
                 for b in self._bufs:
                     b.record_stream(self._stream)
 
-    def _launch(self, i: int, buf: BatchBuffers):
-        seeds = self.ids[i * self.batch_size:(i + 1) * self.batch_size]
+    def _launch(self, i: int, buf: BatchBuffers, order: Optional[torch.Tensor] = None):
+        seeds = (self.ids if order is None else order)[i * self.batch_size:(i + 1) * self.batch_size]
         word = self._words[i:i + 1] if self.fanout is not None else None      # (resident: the kernels read it where it is)
         if self._stream is not None:
             if buf.released is not None:
@@ -737,9 +847,10 @@ class NeighborLoader:
             sample_into(self.dg, buf, seeds, self.seed_type, fanout=self.fanout, sample_word=word)
         return int(seeds.numel())
 
-    def measure_caps(self, margin: float = 1.03, round_to: int = 64) -> BatchCaps:
+    def measure_caps(self, margin: float = 1.03, round_to: int = 64, epochs: int = 1) -> BatchCaps:
         """Dry pass over every batch of this loader (the batch order is fixed, kgwas.py:93-94): the largest
-        node / edge / chunk counts, plus a safety margin, become the capacities of a static layout.
+        node / edge / chunk counts, plus a safety margin, become the capacities of a static layout (``margin=1.0, round_to=1``:
+        the largest counts themselves).
 
         A loader with a finite fan-out redraws its batches every epoch, so what one pass saw bounds nothing.  Its capacities are
         bounds that hold for EVERY draw: the dry pass is made over the FULL neighbourhoods of the same seeds (whatever a draw
@@ -747,29 +858,45 @@ class NeighborLoader:
         and chunk count of a draw is at most the full one), and each is then lowered to the analytic bound where that is
         smaller -- new nodes of a type at hop h+1 <= sum over the relations leaving the type of (rows of the relation's
         destination type new at hop h) x k_h, edges of hop h <= the same sum over all relations, chunks likewise with
-        ceil(k_h / KGW_CHUNK) per segment, never more nodes than the type has."""
+        ceil(k_h / KGW_CHUNK) per segment, never more nodes than the type has.
+
+        epoch_order='seeds': every epoch has batches of its own, but which ones is a pure function of (seed, epoch), so the batches
+        of a run are known before it starts: the dry pass runs over every batch of epochs 0 .. ``epochs`` - 1 and batch 0 of epoch
+        ``epochs`` (which a captured trainer samples ahead and never trains on), and the capacities hold for exactly those.
+        epoch_order='batches' visits the fixed order's batches: one pass, any epoch's, sees them all.  A finite fan-out composes as
+        before: the same passes over the full neighbourhoods, then the analytic bounds.  The loader's own epoch is left alone."""
+        epochs = int(epochs)
+        if epochs < 1:
+            raise ValueError(f'measure_caps: epochs = {epochs}')
         if self.fanout is not None:
             full = NeighborLoader(self.data, [-1] * self.num_layers, (self.input_type, self.ids), batch_size=self.batch_size,
-                                  drop_last=self.drop_last, device=self.device, prefetch=False)
-            return self._fanout_caps(full.measure_caps(margin, round_to), round_to)
+                                  drop_last=self.drop_last, device=self.device, prefetch=False, seed=self.seed,
+                                  epoch_order=self.epoch_order, rank=self.rank, world=self.world)
+            return self._fanout_caps(full.measure_caps(margin, round_to, epochs), round_to)
         dg = self.dg
         sc, L = dg.schema, dg.num_layers
         node_off = np.zeros((sc.NT, L + 2), dtype=np.int64)
         edges = np.zeros(L, dtype=np.int64)
         chunks = np.zeros(L, dtype=np.int64)
-        for b in self:
-            m = b.meta
-            for t in range(sc.NT):
-                for k in range(L + 2):
-                    node_off[t, k] = max(node_off[t, k], int(m.node_off[t][min(k, dg.n_hops + 1)]))
-            for l in range(L):
-                edges[l] = max(edges[l], int(m.n_edges[l]))
-                chunks[l] = max(chunks[l], int(m.n_chunks[l]))
+        if self.epoch_order == 'seeds':
+            passes = [(e, None) for e in range(epochs)] + [(epochs, 1)]
+        else:
+            passes = [(0, None)]
+        for epoch, first in passes:
+            for b in self._pass(epoch, first):
+                m = b.meta
+                for t in range(sc.NT):
+                    for k in range(L + 2):
+                        node_off[t, k] = max(node_off[t, k], int(m.node_off[t][min(k, dg.n_hops + 1)]))
+                for l in range(L):
+                    edges[l] = max(edges[l], int(m.n_edges[l]))
+                    chunks[l] = max(chunks[l], int(m.n_chunks[l]))
+        plain = margin == 1.0 and round_to == 1             # (no margin, no rounding: the counts as they were seen)
 
         def up(v, hi=None, exact=False):
             if exact:
                 return int(v)
-            w = int(-(-int(v * margin + 1) // round_to) * round_to)
+            w = int(v) if plain else int(-(-int(v * margin + 1) // round_to) * round_to)
             return min(w, hi) if hi is not None else w
         seed_t = self.seed_type
         for t in range(sc.NT):
@@ -817,26 +944,41 @@ class NeighborLoader:
         return BatchCaps(node_off, edges, chunks)
 
     def __iter__(self):
-        self._ensure()
-        nb = len(self)
-        if nb == 0:
+        if len(self) == 0:
             return
-        if self.fanout is not None:
+        if self.redrawn:
             if not self._epoch_set:
                 self.epoch += 1
             self._epoch_set = False
-            self._words = fanout_words(self.seed, self.epoch, nb, self.device)
+        yield from self._pass(self.epoch)
+
+    def _pass(self, epoch: int, n_first: Optional[int] = None):
+        """The batches of epoch ``epoch`` (the first ``n_first`` of them)."""
+        self._ensure()
+        nb = len(self) if n_first is None else min(len(self), n_first)
+        if nb == 0:
+            return
+        if self._stream is not None and self.redrawn:
+            self._stream.wait_stream(torch.cuda.current_stream())      # (words and ids are uploaded on the consumer's stream)
+        if self.fanout is not None:
+            self._words = fanout_words(self.seed, epoch, len(self), self.device)
             if self._stream is not None:
-                self._stream.wait_stream(torch.cuda.current_stream())      # (the words are uploaded on the consumer's stream)
                 self._words.record_stream(self._stream)
+        order = None
+        if self.epoch_order != 'fixed':
+            # the order is written on the stream whose sampler reads it; the previous pass's tensor stays alive beside it (a
+            # prefetch of a pass that was left early may still read it)
+            self._orders = {e: t for e, t in self._orders.items() if e == epoch - 1}
+            with torch.cuda.stream(self._stream if self._stream is not None else torch.cuda.current_stream()):
+                order = self._orders[epoch] = self.order_tensor(epoch)
         nbuf = len(self._bufs)
         pending = {}
         if self.prefetch:
-            pending[0] = self._launch(0, self._bufs[0])
+            pending[0] = self._launch(0, self._bufs[0], order)
         for i in range(nb):
             buf = self._bufs[i % nbuf]
             if not self.prefetch:
-                pending[i] = self._launch(i, buf)
+                pending[i] = self._launch(i, buf, order)
             elif i + 1 < nb:
                 nxt = self._bufs[(i + 1) % nbuf]
                 # the consumer finished enqueuing work on batch i-1 (it asked for batch i): its buffer may
@@ -844,5 +986,5 @@ class NeighborLoader:
                 ev = torch.cuda.Event()
                 ev.record(torch.cuda.current_stream())
                 nxt.released = ev
-                pending[i + 1] = self._launch(i + 1, nxt)
+                pending[i + 1] = self._launch(i + 1, nxt, order)
             yield finish_sample(self.dg, buf, self.input_type, pending.pop(i))
