@@ -383,6 +383,42 @@ KGWFAN_INLINE int kgwdrop_keep(uint32_t base, uint32_t local_edge, uint32_t thre
     return kgwfan_mix32(base ^ local_edge) >= thresh;
 }
 
+/* Hidden-state dropout: x = F.dropout(x, p, training) on the OUTPUT of message-passing layer l, 1 <= l <= L - 1 (after its ReLU,
+ * kgwas/model.py:75; never on the feature MLPs' output, never on the last layer).  The reference's HeteroGNN has no such line:
+ * like the attention dropout an EXTENSION, off by default.  For stored column c (0 .. 127) of the node with LOCAL index row within
+ * node type t of the batch (the index into the type's n_id; NOT the row of the type-major layer input, whose bases differ between
+ * a batch's own layout and the static one of a captured step):
+ *      base(word, l, t) = kgwfan_step(kgwfan_step(kgwdrop_base(word, l), KGW_HDROP_TAG), t)                 (kgwhdrop_base)
+ *      keep(row, c)     = kgwfan_mix32(base ^ (row * 128 + c)) >= thresh,   thresh = floor(p * 2^32)          (kgwhdrop_keep)
+ *      y'(row, c)       = keep ? y * scale : 0.0f,                          scale = (float)(1 / (1 - p))
+ * -- a pure function of (word, layer, node type, local row, column): no launch geometry and no capacity of a layout enters, and
+ * the tag keeps the masks apart from the attention-dropout masks of the same (word, layer).  A dropped element is exactly 0.0f
+ * whatever bits it held (a select, not a product: NaN and Inf do not survive a drop); thresh = 0, scale = 1 gives the input bits
+ * back.  The backward of y' = m' y is dy = m' dy' with the same mask, recomputed: kgw_hidden_dropout is called on dY with the
+ * values of the forward call, and no mask is stored.  word is READ FROM DEVICE MEMORY when the kernel runs, as above.
+ *
+ * One launch for up to 8 jobs (the destination types of one layer): job j drops rows [0, rows) of 128 floats, row i at
+ * src + i * lds, into dst + i * ldd.  dst == src (and ldd == lds) drops in place; any other overlap is undefined.  One float4 per
+ * lane, 32 lanes per row, grid-stride over the rows of all jobs; no atomics, no LDS.  Refused before any launch: jobs or word_dev
+ * NULL, src or dst of a job with rows > 0 NULL: KGW_E_NULL;  n_jobs outside [1, 8], layer < 1, a scale that is not finite or < 1,
+ * rows < 0 or > 2^25 (row * 128 + c must fit 32 bits), lds or ldd < 128 with rows > 1: KGW_E_RANGE;  a src or dst that is not
+ * 16-byte aligned, lds % 4 or ldd % 4 != 0: KGW_E_UNSUPPORTED.  Jobs without rows are skipped; no rows at all: KGW_OK, no launch. */
+#define KGW_HDROP_TAG 1751413360u     /* the bytes of 'hdrp', big-endian */
+KGWFAN_INLINE uint32_t kgwhdrop_base(uint64_t word, int32_t layer, int32_t type) {
+    return kgwfan_step(kgwfan_step(kgwdrop_base(word, layer), KGW_HDROP_TAG), (uint32_t)type);
+}
+KGWFAN_INLINE int kgwhdrop_keep(uint32_t base, uint32_t row, uint32_t col, uint32_t thresh) {
+    return kgwfan_mix32(base ^ (row * 128u + col)) >= thresh;
+}
+typedef struct KgwHDropJob {
+    const float* src; int64_t lds;    /* rows of 128 floats, leading dimension in floats                                          */
+    float* dst; int64_t ldd;
+    int32_t rows;                     /* local rows 0 .. rows - 1 of the type                                                      */
+    int32_t type;                     /* node type id of the schema                                                                */
+} KgwHDropJob;
+int kgw_hidden_dropout(int32_t n_jobs, const KgwHDropJob* jobs, int32_t layer, const uint64_t* word_dev, uint32_t thresh,
+                       float scale, kgw_stream_t stream);
+
 /* Sigmoid-gated attention (KGW_F_SIGMOID_GATE): alpha = sigmoid(leaky_relu(a_j + a_i) / T) instead of the softmax over the row
  * (kgwas/conv.py:49,219-220, the reference GATConv's sigmoid_gat; its HeteroGNN never passes it, so like the dropout this is an
  * EXTENSION, off by default).  The gates are independent per edge and are not normalised by the row's degree.  With

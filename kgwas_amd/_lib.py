@@ -159,6 +159,10 @@ class KgwRelvecJob(C.Structure):
                 ('dw_src_t', C.c_void_p), ('dw_dst_t', C.c_void_p), ('datt_src', C.c_void_p), ('datt_dst', C.c_void_p)]
 
 
+class KgwHDropJob(C.Structure):
+    _fields_ = [('src', C.c_void_p), ('lds', C.c_int64), ('dst', C.c_void_p), ('ldd', C.c_int64), ('rows', C.c_int32), ('type', C.c_int32)]
+
+
 class KgwFoldArgs(C.Structure):
     _fields_ = [('n', C.c_int32), ('n_rels', C.c_int32), ('n_mlp', C.c_int32), ('duv_pieces', C.c_int32),
                 ('rel_ids_host', C.c_void_p), ('src_mlp_host', C.c_void_p), ('dst_mlp_host', C.c_void_p),
@@ -177,7 +181,7 @@ EXPORTS = ['kgw_version', 'kgw_status_string', 'kgw_struct_sizes', 'kgw_sample_b
            'kgw_gather_rows', 'kgw_gather_rows_multi', 'kgw_scatter_relu_rows', 'kgw_scatter_relu_rows_workspace_floats', 'kgw_edge_alpha', 'kgw_debug_reduce', 'kgw_debug_reduce8', 'kgw_tn_gemm', 'kgw_tn_gemm_ex', 'kgw_tn_gemm_multi', 'kgw_tn_gemm_workspace_floats', 'kgw_tn_gemm_partial', 'kgw_tn_gemm_multi_partial', 'kgw_tn_split', 'kgw_tn_direct_rows', 'kgw_param_tail', 'kgw_tn_reduce_launch', 'kgw_tn_gemm_partial_ride', 'kgw_transform_bwd_ex', 'kgw_mlp2_bwd_first_partial', 'kgw_mlp2_bwd_first_packed', 'kgw_adam_fused', 'kgw_gemm3_partial', 'kgw_gemm3_flip', 'kgw_transform_bwd', 'kgw_grad_finish',
            'kgw_linear', 'kgw_mlp2_fwd', 'kgw_mlp2w_fwd', 'kgw_mlp2_bwd_first', 'kgw_mlp2_bwd_first_workspace_floats', 'kgw_gemm3', 'kgw_gemm3_riders', 'kgw_gemm3_rider_blocks', 'kgw_gemm3_pack', 'kgw_gemm3_packed_bytes', 'kgw_gemm3_workspace_floats', 'kgw_adam', 'kgw_adam_notick', 'kgw_relvec_fwd', 'kgw_relvec_bwd', 'kgw_relvec_bwd_acc', 'kgw_relvec_fwd_multi', 'kgw_relvec_bwd_multi', 'kgw_wmse_fwd', 'kgw_wmse_bwd', 'kgw_readout_wmse_fwd', 'kgw_readout_wmse_bwd', 'kgw_readout_wmse_train', 'kgw_readout_wmse_train_parts', 'kgw_readout_train_fold', 'kgw_readout_mt_pred', 'kgw_readout_mt_pred_bwd', 'kgw_readout_wmse_mt_fwd', 'kgw_readout_wmse_mt_bwd',
            'kgw_readout_wmse_mt_train', 'kgw_readout_wmse_mtw_fwd', 'kgw_readout_wmse_mtw_bwd', 'kgw_readout_wmse_mtw_train',
-           'kgw_accumulate_stats', 'kgw_accumulate_stats_tick']
+           'kgw_accumulate_stats', 'kgw_accumulate_stats_tick', 'kgw_hidden_dropout']
 
 _lib = None
 
@@ -340,6 +344,8 @@ def lib():
         L.kgw_readout_wmse_mtw_fwd.argtypes = L.kgw_readout_wmse_mt_fwd.argtypes
         L.kgw_readout_wmse_mtw_bwd.argtypes = L.kgw_readout_wmse_mt_bwd.argtypes
         L.kgw_readout_wmse_mtw_train.argtypes = L.kgw_readout_wmse_mt_train.argtypes
+    if hasattr(L, 'kgw_hidden_dropout'):            # (absent from an older library named by KGW_LIB_PATH for an A/B run)
+        L.kgw_hidden_dropout.argtypes = [C.c_int32, C.POINTER(KgwHDropJob), C.c_int32, C.c_void_p, C.c_uint32, C.c_float, C.c_void_p]
     L.kgw_accumulate_stats.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
     L.kgw_accumulate_stats_tick.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     _lib = L
@@ -374,6 +380,12 @@ def has_edge_attr() -> bool:
     """Does the loaded library have the edge-attribute entry points (kgw_edge_term_fwd, kgw_edge_term_bwd,
     kgw_gat_aggregate_fwd_eterm)?  An older library named by KGW_LIB_PATH for an A/B run lacks the symbols."""
     return hasattr(lib(), 'kgw_gat_aggregate_fwd_eterm')
+
+
+def has_hidden_dropout() -> bool:
+    """Does the loaded library have kgw_hidden_dropout (hidden-state dropout between the layers)?  An older library named by
+    KGW_LIB_PATH for an A/B run lacks the symbol."""
+    return hasattr(lib(), 'kgw_hidden_dropout')
 
 
 KGW_ORDER_SEEDS, KGW_ORDER_BATCHES = 1, 2     # kgw_epoch_order's modes (include/kgwas_hip.h)

@@ -241,6 +241,8 @@ class GraphTrainStep:
         A model with ``gat_dropout > 0``: the step is captured in training mode (whatever mode the model is in; restored afterwards)
         and every ``step`` copies the 8-byte word of (``sample_seed``, epoch, batch index) into ``model.drop_word`` ahead of the
         replay -- the kernels read it when they run.  The batches themselves stay the same from epoch to epoch (BatchCache on).
+        A model with ``gnn_dropout > 0`` (``self.hidden_dropout``; ``self.dropout`` keeps meaning ATTENTION dropout, which alone
+        takes the unfolded route) is fed the same way: training-mode capture, the word copy ahead of every replay, ``set_epoch``.
         ``epoch_order`` ('fixed' | 'seeds' | 'batches', NeighborLoader): the order in which an epoch visits the seeds, a pure function
         of (``sample_seed``, epoch) written on the device once per epoch (kgw_epoch_order); ``step(i)`` trains on batch i of the epoch
         ``set_epoch`` named, and a step past the last batch moves on to the next epoch by itself.  'seeds': the batches of every
@@ -283,6 +285,9 @@ class GraphTrainStep:
         self._orders, self._sources = {}, {}            # shuffled orders: {epoch: (order tensor, written-event, streams told)}, {epoch: source batches}
         # attention dropout: the words of an epoch's batches (like the fan-out's), copied one at a time into model.drop_word
         self.dropout = float(getattr(self.model, 'gat_dropout', 0.0)) > 0.0
+        # hidden-state dropout reads the same word; it keeps the FC_output fold and the fused optimiser launch
+        self.hidden_dropout = float(getattr(self.model, 'gnn_dropout', 0.0)) > 0.0
+        self._drops = self.dropout or self.hidden_dropout
         self._drop_words = {}
         self.ld_w = run._ld_weight_vector()             # ([N] or, per-trait weights, [N, T]: resident, read in place by the graph)
         self.world = 1
@@ -356,9 +361,9 @@ class GraphTrainStep:
                             epoch_order != 'seeds')
         # (parameter-only kernels on a parallel branch of the captured step: measured again in round 5 -- 1.397 ms against 1.081, and
         #  the branch's queue displaces the side sampler's, overlap ratio -0.14 -- HIP-graph branches are not a tool here; removed)
-        if self.dropout:
+        if self._drops:
             was_training = self.model.training
-            self.model.train()                     # (the captured step is a TRAINING step: its aggregates take the dropout kernels)
+            self.model.train()                     # (the captured step is a TRAINING step: its layers take the dropout kernels)
             try:
                 self._capture()
             finally:
@@ -515,7 +520,7 @@ class GraphTrainStep:
                     sample_word=self.sample_word)
 
     def set_epoch(self, epoch: int):
-        """Finite fan-out / attention dropout / a shuffled order: the epoch the next ``step`` calls draw for."""
+        """Finite fan-out / attention or hidden-state dropout / a shuffled order: the epoch the next ``step`` calls draw for."""
         self._check_epoch(int(epoch))
         self.epoch = int(epoch)
 
@@ -701,11 +706,11 @@ class GraphTrainStep:
         #  0.9794 / 0.9806 ms)
         sam.prefetch(1 - cur, self._key(nxt, nxt_epoch), lambda: self._prefetch(1 - cur, nxt, nxt_epoch))
         sam.wait(cur)
-        if self.dropout:
+        if self._drops:
             self._feed_dropout(i, self.epoch)
         self.graphs[cur].replay()
         sam.holds[cur] = -1
-        if (self.redrawn or self.dropout) and nxt == 0:
+        if (self.redrawn or self._drops) and nxt == 0:
             self.epoch = nxt_epoch               # (a pass is over: the next one draws anew unless set_epoch says otherwise)
         if self.split_backward:
             from . import dist as kdist
@@ -847,8 +852,8 @@ class GraphEvalStep:
 
     def _forward(self, cur: int):
         batch = SampledBatch(self.dg, self.bufs[cur], self.meta, self.input_type, self.batch_size, static=True)
-        # (evaluation never drops attention weights, whatever mode the caller left the model in)
-        drops = self.model.training and getattr(self.model, 'gat_dropout', 0.0) > 0
+        # (evaluation never drops attention weights or hidden state, whatever mode the caller left the model in)
+        drops = self.model.training and (getattr(self.model, 'gat_dropout', 0.0) > 0 or getattr(self.model, 'gnn_dropout', 0.0) > 0)
         if drops:
             self.model.eval()
         try:

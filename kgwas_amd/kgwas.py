@@ -50,7 +50,7 @@ class KGWAS:
 
     def initialize_model(self, gnn_num_layers=2, gnn_hidden_dim=128, gnn_backbone='GAT', gnn_aggr='sum',
                          gat_num_head=1, no_relu=False, out_channels=1, gat_dropout=0.0, gat_sigmoid=False, gat_temperature=1.0,
-                         gat_edge_dim=None):
+                         gat_edge_dim=None, gnn_dropout=0.0):
         """``out_channels`` (extra, default 1 = the reference, kgwas.py:52): T > 1 reads ONE shared trunk out into T label columns
         (``data['SNP'].y`` [N, T], KGWAS_Data.from_synthetic(n_traits=T)) -- a shared-trunk multi-task model, not T independent
         models.  It enters ``config`` only when it is not 1, so the config.pkl of a single-trait run is what it always was.
@@ -64,7 +64,10 @@ class KGWAS:
         ``gat_edge_dim`` = D in 1..8 (extra, default None = the reference's model, launch for launch and bit for bit): GATConv's
         ``edge_dim`` (conv.py:46,207-215) for the relations whose ``data[edge_type].edge_attr`` is set (KGWAS_Data.set_edge_attr /
         from_synthetic(edge_dim=D)); it enters ``config`` only when it is set.  GAT only; not with gat_num_head > 1, gat_dropout > 0
-        or gat_sigmoid; training takes whole neighbourhoods (no ``num_neighbors``) and parallelism='seed'."""
+        or gat_sigmoid; training takes whole neighbourhoods (no ``num_neighbors``) and parallelism='seed'.
+        ``gnn_dropout`` (extra, default 0 = the reference): dropout p on the hidden state between the message-passing layers while
+        training (HeteroGNN; needs gnn_num_layers >= 2); every backbone and switch takes it, parallelism='shard' does not.  It
+        enters ``config`` only when it is not 0."""
         self.config = {'gnn_num_layers': gnn_num_layers, 'gnn_hidden_dim': gnn_hidden_dim,
                        'gnn_backbone': gnn_backbone, 'gnn_aggr': gnn_aggr, 'gat_num_head': gat_num_head}
         out_channels = int(out_channels)
@@ -82,12 +85,15 @@ class KGWAS:
             self.config['gat_temperature'] = gat_temperature
         if gat_edge_dim is not None:
             self.config['gat_edge_dim'] = int(gat_edge_dim)
+        gnn_dropout = float(gnn_dropout)
+        if gnn_dropout != 0.0:
+            self.config['gnn_dropout'] = gnn_dropout
         self.gnn_num_layers = gnn_num_layers
         self.model = HeteroGNN(self.data.data, gnn_hidden_dim, out_channels, gnn_num_layers, gnn_backbone, gnn_aggr,
                                self.data.snp_init_dim_size, self.data.gene_init_dim_size,
                                self.data.go_init_dim_size, gat_num_head, no_relu=no_relu, gat_dropout=gat_dropout,
                                gat_split_heads=True, gat_sigmoid=gat_sigmoid, gat_temperature=gat_temperature,
-                               gat_edge_dim=gat_edge_dim).to(self.device)
+                               gat_edge_dim=gat_edge_dim, gnn_dropout=gnn_dropout).to(self.device)
 
     def load_pretrained(self, path):
         import pandas as pd
@@ -170,6 +176,9 @@ class KGWAS:
         if getattr(self.model, 'gat_dropout', 0.0) > 0:
             raise NotImplementedError("gat_dropout > 0 is not available with parallelism='shard': it would drop inside partial "
                                       "softmax states; use parallelism='seed'")
+        if getattr(self.model, 'gnn_dropout', 0.0) > 0:
+            raise NotImplementedError("gnn_dropout > 0 is not available with parallelism='shard': the sharded step does not run "
+                                      "the hidden-state dropout launches; use parallelism='seed'")
         if getattr(self.model, 'gat_sigmoid', False) or getattr(self.model, 'temperature', 1.0) != 1.0:
             raise NotImplementedError("gat_sigmoid / gat_temperature are not available with parallelism='shard': the exchange of "
                                       "partial softmax states is built for the softmax at T = 1; use parallelism='seed'")
@@ -287,7 +296,7 @@ class KGWAS:
         ld_w = self._ld_weight_vector()
         min_val = -1000
         self.best_model = deepcopy(self.model).to(self.device)
-        dropout = getattr(self.model, 'gat_dropout', 0.0) > 0
+        dropout = getattr(self.model, 'gat_dropout', 0.0) > 0 or getattr(self.model, 'gnn_dropout', 0.0) > 0
         print_sys('Start Training...')
         for ep in range(total_epoch):
             self.model.train()

@@ -292,11 +292,19 @@ class HeteroGNN(nn.Module):
     the attention logit of its edges before the LeakyReLU, in every layer (state-dict keys ``convs.<l>.convs.<key>.lin_edge.weight``
     / ``.att_edge``).  The other relations are what they were.  The softmax still sums to one: the model keeps the FC_output fold
     and the fused optimiser launch.  GAT only; not with gat_num_head > 1, gat_dropout > 0 or gat_sigmoid; ``None`` (the default) is
-    the model as ever, launch for launch."""
+    the model as ever, launch for launch.
+    ``gnn_dropout`` = p (an extension, keyword only: the reference's HeteroGNN has no dropout on its hidden state): in training mode
+    the output of every message-passing layer but the last -- after its ReLU, for ``gnn_aggr='mean'`` after the 1 / R scale -- goes
+    through F.dropout(x, p): every element is dropped with probability p and the kept ones are scaled by 1 / (1 - p), by one
+    element-wise launch per layer and pass (ops.hidden_dropout); which elements is a pure function of (``drop_word``, layer, node
+    type, local row, column) -- kgwhdrop_keep in include/kgwas_hip.h.  Never on the feature MLPs' output, so the FC_output fold, the
+    parameter riders and the fused optimiser launch stay; every backbone, aggregation and attention switch takes it.  Needs
+    ``num_layers >= 2`` (there is no site otherwise).  Evaluation, the attention queries and the export never drop; 0 (the default)
+    runs exactly the launches the model ran without it."""
 
     def __init__(self, pyg_data, hidden_channels, out_channels, num_layers, gnn_backbone, gnn_aggr,
                  snp_init_dim_size, gene_init_dim_size, go_init_dim_size, gat_num_head, no_relu=False, gat_dropout=0.0,
-                 gat_split_heads=False, *, gat_sigmoid=False, gat_temperature=1.0, gat_edge_dim=None):
+                 gat_split_heads=False, *, gat_sigmoid=False, gat_temperature=1.0, gat_edge_dim=None, gnn_dropout=0.0):
         super().__init__()
         if gnn_backbone not in ('GAT', 'SAGE'):
             raise NotImplementedError(f"backbone {gnn_backbone!r}: 'GAT' (the reference default, kgwas.py:52) and 'SAGE' "
@@ -310,8 +318,16 @@ class HeteroGNN(nn.Module):
             raise ValueError("gat_dropout needs gnn_backbone='GAT': SAGE has no attention weights to drop (its aggregate merely "
                              "reuses the kernels)")
         self.gat_dropout = gat_dropout
-        # the 64-bit word of the step's masks, resident on the device: the kernels read it when they run, so a captured step
-        # replays with whatever the trainer copied here (set_dropout_word / GraphTrainStep).  Not part of the state_dict.
+        gnn_dropout = float(gnn_dropout)
+        if not 0.0 <= gnn_dropout < 1.0:
+            raise ValueError(f'gnn_dropout {gnn_dropout}: 0 <= p < 1')
+        if gnn_dropout != 0.0 and int(num_layers) < 2:
+            raise ValueError(f'gnn_dropout > 0 with num_layers = {num_layers}: the hidden state is dropped BETWEEN message-passing '
+                             'layers, and one layer has no such site')
+        self.gnn_dropout = gnn_dropout
+        # the 64-bit word of the step's masks (attention and hidden-state dropout alike: the rules keep them apart), resident on
+        # the device: the kernels read it when they run, so a captured step replays with whatever the trainer copied here
+        # (set_dropout_word / GraphTrainStep).  Not part of the state_dict.
         self.register_buffer('drop_word', torch.tensor([_signed64(dropout_word(0, 0, 0))], dtype=torch.int64), persistent=False)
         if gnn_aggr not in ('sum', 'mean', 'min', 'max'):
             raise NotImplementedError(f"gnn_aggr {gnn_aggr!r}: 'sum' (the reference default, fused), 'mean', 'min' and 'max' are "
@@ -577,7 +593,7 @@ class HeteroGNN(nn.Module):
             return o[0]
         return getattr(torch, self.aggr)(o, dim=0).values
 
-    def _sage_layers(self, batch: SampledBatch, h: Dict[str, torch.Tensor], hbuf=None):
+    def _sage_layers(self, batch: SampledBatch, h: Dict[str, torch.Tensor], hbuf=None, hdrop=None):
         """SAGE backbone (kgwas/model.py:38,74-75): out_d = relu(sum_r [lin_l^r(mean_{j->i} h_s[j]) + lin_r^r(h_d[i])]).
         The neighbour mean IS the attention aggregate with all logits equal: the same kernels run with zero attention
         vectors (alpha = 1/deg; rows without in-edges stay zero like PyG's mean), forward and backward; the root
@@ -633,7 +649,7 @@ class HeteroGNN(nn.Module):
                 if self.aggr == 'mean':
                     y = y * (1.0 / R)
                 h_next[name] = torch.relu(y)
-            h = h_next
+            h = self._drop_hidden(l, h_next, hdrop)
         return h, []
 
     def _all_layer_params(self, batch: SampledBatch, folded: bool):
@@ -722,7 +738,7 @@ class HeteroGNN(nn.Module):
         V = v.new_zeros(self.heads, self.schema.NR, self.hidden).index_copy(1, P.rel_ids_t, v)
         return U, V
 
-    def _head_layers(self, batch: SampledBatch, h: Dict[str, torch.Tensor], hbuf=None, last_premasked=False):
+    def _head_layers(self, batch: SampledBatch, h: Dict[str, torch.Tensor], hbuf=None, last_premasked=False, hdrop=None):
         """The layers with gat_num_head = H > 1: per relation exactly GATConv((-1,-1), cl / H, heads=H, concat=True), re-associated
         as the single-head route is -- the aggregate gathers the layer input once per edge for all heads (ops.gat_aggregate(heads=H):
         Z[h] = sum_j alpha^h_ij x_j, full width per head), and column c of the output takes head(c)'s aggregate:
@@ -752,11 +768,15 @@ class HeteroGNN(nn.Module):
             # (from layer 2 on, H is the previous layer's ReLU output and its backward is folded into this node's)
             Z, _, _ = ops.gat_aggregate(batch, l, H, U, V, self.negative_slope, self.temperature, relu_input=(l > 1), heads=NH)
             hbuf, nxt = self._layer_input(batch, l + 1) if l < self.num_layers else (None, {})
-            outs = ops.layer_transform_heads(P, Z, blocks, self.head_mask, [nxt.get(sc.node_types[t]) for t in tys],
+            drops = hdrop is not None and l < self.num_layers
+            # (a layer whose output is dropped leaves the next layer's blocks to the dropout launch: see _fused_layers)
+            outs = ops.layer_transform_heads(P, Z, blocks, self.head_mask, None if drops else [nxt.get(sc.node_types[t]) for t in tys],
                                              premasked=(l < self.num_layers) or last_premasked)
             if self.aggr == 'mean':
-                hbuf = None
+                hbuf = None if not drops else hbuf
                 outs = [o * (1.0 / (hi - lo)) for o, (lo, hi, _, _) in zip(outs, blocks)]
+            if drops:
+                outs = ops.hidden_dropout(outs, tys, l, hdrop[0], hdrop[1], [nxt.get(sc.node_types[t]) for t in tys])
             h = {sc.node_types[t]: o for t, o in zip(tys, outs)}
         return h, []
 
@@ -780,20 +800,34 @@ class HeteroGNN(nn.Module):
         nodes.  Evaluation and the attention queries never drop and keep the fold."""
         return (self.gat_dropout, self.drop_word) if (self.training and self.gat_dropout > 0.0) else None
 
+    def _hidden_dropout(self):
+        """``hdrop=`` of the training forward's layers: (p, word) in training mode with gnn_dropout > 0, else None.  Unlike the
+        attention dropout it leaves the softmax rows alone (they still sum to 1), so the FC_output fold stays."""
+        return (self.gnn_dropout, self.drop_word) if (self.training and self.gnn_dropout > 0.0) else None
+
+    def _drop_hidden(self, l: int, h: Dict[str, torch.Tensor], hdrop):
+        """Hidden-state dropout on the per-type outputs ``h`` of layer l (the routes whose outputs are framework tensors: SAGE, the
+        relation min / max): one launch over all types, nothing for the last layer or with ``hdrop`` None."""
+        if hdrop is None or l >= self.num_layers or not h:
+            return h
+        names = list(h)
+        outs = ops.hidden_dropout([h[n] for n in names], [self.schema.type_id[n] for n in names], l, hdrop[0], hdrop[1])
+        return dict(zip(names, outs))
+
     def _fused_layers(self, batch: SampledBatch, h: Dict[str, torch.Tensor], want_attention=False, hbuf=None,
-                      last_premasked=False, folded=False, prep=None, dropout=None):
+                      last_premasked=False, folded=False, prep=None, dropout=None, hdrop=None):
         """``folded``: h holds the feature MLPs' hidden state h2 (``_embed_all(fold=True)``), not their output: layer 1 runs
         with FC_output folded into its relation parameters (ops.fold_fc_output_hip).  ``prep``: per layer, what
-        ``_layer_params`` returns, computed ahead by the caller.  ``dropout``: see ``_dropout`` (only ``forward`` and
-        ``forward_loss`` pass it: the attention queries never drop)."""
+        ``_layer_params`` returns, computed ahead by the caller.  ``dropout``: see ``_dropout``, ``hdrop``: see ``_hidden_dropout``
+        (only ``forward`` and ``forward_loss`` pass them: the attention queries never drop)."""
         if self.backbone == 'SAGE':
             if want_attention:
                 raise NotImplementedError('attention weights exist for the GAT backbone only (kgwas/model.py:65-72)')
-            return self._sage_layers(batch, h, hbuf)
+            return self._sage_layers(batch, h, hbuf, hdrop)
         if self.heads > 1:
             if want_attention:
                 raise NotImplementedError('gat_num_head > 1: the attention queries are single-head (kgw_edge_alpha)')
-            return self._head_layers(batch, h, hbuf, last_premasked)
+            return self._head_layers(batch, h, hbuf, last_premasked, hdrop)
         sc = self.schema
         m = batch.meta
         C = self.hidden
@@ -839,18 +873,24 @@ class HeteroGNN(nn.Module):
                         ops.LIBRARY_GEMM.note('gat min/max per-relation outputs', R, rows, C)
                         o = torch.baddbmm(P.bias[lo:hi].unsqueeze(1), zr, Wv[lo:hi])
                     outs.append(torch.relu(self._combine_relations(o)))
-                h = {sc.node_types[t]: o for t, o in zip(tys, outs)}
+                h = self._drop_hidden(l, {sc.node_types[t]: o for t, o in zip(tys, outs)}, hdrop)
                 continue
             # per-relation linear maps + bias + relation sum + ReLU: one GEMM per destination type, one autograd node
             hbuf, nxt = self._layer_input(batch, l + 1) if l < self.num_layers else (None, {})
-            outs = ops.layer_transform(P, Z, blocks, [nxt.get(sc.node_types[t]) for t in tys],
+            # hidden-state dropout on this layer's output: the transform keeps its own (undropped) rows -- it saves them -- and the
+            # dropout launch writes the dropped state into the next layer's blocks, so no join_blocks copy is added.  The next
+            # aggregate folds dH *= (H > 0) with H the DROPPED state (kept and positive); the dropout's backward supplies the scale.
+            drops = hdrop is not None and l < self.num_layers
+            outs = ops.layer_transform(P, Z, blocks, None if drops else [nxt.get(sc.node_types[t]) for t in tys],
                                        premasked=(l < self.num_layers) or last_premasked, bias_sum=bsum,
                                        weight=Wp if Wp is not None else Wv, gamma=gam, stat=stat if gam is not None else None)
             if self.aggr == 'mean':
                 # mean over the relations of a destination type = the sum scaled by 1/R; relu(s/R) = relu(s)/R, and the
                 # positive scale commutes with the folded ReLU masks
-                hbuf = None
+                hbuf = None if not drops else hbuf
                 outs = [o * (1.0 / (hi - lo)) for o, (lo, hi, _, _) in zip(outs, blocks)]
+            if drops:
+                outs = ops.hidden_dropout(outs, tys, l, hdrop[0], hdrop[1], [nxt.get(sc.node_types[t]) for t in tys])
             h_next = {sc.node_types[t]: o for t, o in zip(tys, outs)}
             h = h_next
         return h, attn
@@ -873,7 +913,7 @@ class HeteroGNN(nn.Module):
         drop = self._dropout()
         fold = self.fold_fc and drop is None                    # (see _dropout: a step that drops runs layer 1 unfolded)
         h = self._embed_all(batch, x_dict, blocks, fold=fold)
-        h, attn = self._fused_layers(batch, h, hbuf=hbuf, folded=fold, dropout=drop)
+        h, attn = self._fused_layers(batch, h, hbuf=hbuf, folded=fold, dropout=drop, hdrop=self._hidden_dropout())
         snp = h['SNP']
         out = self._readout(snp[:batch_size])
         if return_h:                                            # model.py:78-79
@@ -934,7 +974,8 @@ class HeteroGNN(nn.Module):
         self.last_riders_taken = riders.taken if riders is not None else 0
         if mlp_out is not None:
             mlp_out.extend(h.values())
-        h, _ = self._fused_layers(batch, h, hbuf=hbuf, last_premasked=gat, folded=fold, prep=prep, dropout=drop)
+        h, _ = self._fused_layers(batch, h, hbuf=hbuf, last_premasked=gat, folded=fold, prep=prep, dropout=drop,
+                                  hdrop=self._hidden_dropout())
         return ops.readout_weighted_mse(h['SNP'], self.lin.weight, self.lin.bias, n_id, y_all, w_all, batch_size,
                                         relu=not self.no_relu, h_is_relu=gat, unit_grad=unit_grad)
 

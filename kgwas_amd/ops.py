@@ -2458,6 +2458,74 @@ def layer_transform_heads(pack, Z, blocks, head_mask, out_blocks=None, premasked
     return _LayerTransform.apply(Wm, bias_v, Zv, vblocks, bsum, out_blocks, premasked, None, None)
 
 
+def _hdrop_launch(pairs, types, layer, thresh, scale, word):
+    """kgw_hidden_dropout over (src, dst) row matrices of ``types``: one launch."""
+    jobs = (_lib.KgwHDropJob * len(pairs))()
+    for j, (x, y), t in zip(jobs, pairs, types):
+        j.src, j.lds, j.dst, j.ldd, j.rows, j.type = _p(x), x.stride(0), _p(y), y.stride(0), x.shape[0], int(t)
+    _lib.check(_lib.lib().kgw_hidden_dropout(len(pairs), jobs, int(layer), _p(word), thresh, scale, _lib.stream_ptr()),
+               'kgw_hidden_dropout')
+
+
+def _hdrop_rows(x):
+    """``x`` as the kernel reads it: fp32 rows of 128, 16-byte aligned, row stride a multiple of 4 floats (a copy only if not)."""
+    ok = x.dtype == torch.float32 and x.stride(1) == 1 and x.stride(0) % 4 == 0 and x.data_ptr() % 16 == 0 and \
+        (x.stride(0) >= KGW_C or x.shape[0] <= 1)
+    return x if ok else x.float().contiguous()
+
+
+class _HiddenDropout(torch.autograd.Function):
+    """y'_t = m'_t * y_t for the per-type outputs of one layer, m' from kgwhdrop_keep (include/kgwas_hip.h): one launch forward,
+    one backward (dy = m' * dy', the mask recomputed from the same word tensor -- whoever changes the word between a forward and
+    its backward gets another mask, as with the attention dropout)."""
+
+    @staticmethod
+    def forward(ctx, types, layer, thresh, scale, word, out_blocks, *outs):
+        ctx.set_materialize_grads(False)
+        pairs = []
+        for k, x in enumerate(outs):
+            x = _hdrop_rows(x)
+            ob = out_blocks[k] if out_blocks is not None else None
+            # (never the input's own rows: the node that produced them may have saved them -- _LayerTransform does)
+            y = ob.view() if ob is not None and ob.n == x.shape[0] and ob.buf.data_ptr() % 16 == 0 else torch.empty_like(x, memory_format=torch.contiguous_format)
+            assert y.data_ptr() != x.data_ptr() or x.shape[0] == 0
+            pairs.append((x, y))
+        _hdrop_launch(pairs, types, layer, thresh, scale, word)
+        ctx.args = (types, layer, thresh, scale)
+        ctx.word = word
+        return tuple(y for _, y in pairs)
+
+    @staticmethod
+    def backward(ctx, *dys):
+        types, layer, thresh, scale = ctx.args
+        live = [(k, _hdrop_rows(d)) for k, d in enumerate(dys) if d is not None]
+        dxs = [None] * len(dys)
+        if live:
+            pairs = [(d, torch.empty_like(d, memory_format=torch.contiguous_format)) for _, d in live]
+            _hdrop_launch(pairs, [types[k] for k, _ in live], layer, thresh, scale, ctx.word)
+            for (k, _), (_, dx) in zip(live, pairs):
+                dxs[k] = dx
+        return (None,) * 6 + tuple(dxs)
+
+
+def hidden_dropout(outs, types, layer: int, p: float, word: torch.Tensor, out_blocks=None):
+    """F.dropout on the hidden state between two message-passing layers: ``outs`` = the per-type outputs [rows_t, 128] of layer
+    ``layer`` (row i = local node i of its type), ``types`` = their node type ids.  Element (i, c) of type t is kept iff
+    kgwhdrop_keep(kgwhdrop_base(word, layer, t), i, c, floor(p * 2^32)) and then scaled by float32(1 / (1 - p)), else exactly 0
+    (include/kgwas_hip.h).  ``word``: int64 device tensor of one element, READ WHEN THE KERNEL RUNS (a captured step replays with
+    whatever it then holds).  ``out_blocks``: optional RowBlock per output to write the dropped rows into (the next layer's input);
+    the inputs themselves are never overwritten.  Returns the dropped outputs, in order."""
+    outs = list(outs)
+    if not outs:
+        return []
+    assert len(outs) == len(types) <= 8 and all(o.dim() == 2 and o.shape[1] == KGW_C for o in outs)
+    assert word.dtype == torch.int64 and word.numel() == 1 and word.is_cuda and word.is_contiguous()
+    if not _lib.has_hidden_dropout():
+        raise _lib.KgwasHipError('this libkgwas_hip.so predates hidden-state dropout (kgw_hidden_dropout)')
+    thresh, scale = dropout_params(p)
+    return list(_HiddenDropout.apply(tuple(int(t) for t in types), int(layer), thresh, scale, word, out_blocks, *outs))
+
+
 class _FoldFC(torch.autograd.Function):
     """fold_fc_output_hip's autograd node (kgw_fold_fwd / kgw_fold_bwd): two launches instead of ~40 framework ops."""
 
