@@ -419,6 +419,72 @@ typedef struct KgwHDropJob {
 int kgw_hidden_dropout(int32_t n_jobs, const KgwHDropJob* jobs, int32_t layer, const uint64_t* word_dev, uint32_t thresh,
                        float scale, kgw_stream_t stream);
 
+/* Layer normalisation between the message-passing layers: x = relu(LayerNorm(y)) on the PRE-ACTIVATION output y of layer l,
+ * 1 <= l <= L - 1, per node and per node type (torch.nn.LayerNorm(hidden, eps = 1e-5) / PyG's LayerNorm(mode='node') duplicated
+ * per node type; the sites of the hidden-state dropout, which then follows the ReLU).  The reference's HeteroGNN has no norm: an
+ * EXTENSION, off by default -- but unlike the dropouts it has learned parameters and is live in evaluation.  For one row y of
+ * 128 stored columns of a model Cl = c_logical wide (columns Cl .. 127 are the zero padding of a narrower model):
+ *      mean = (1 / Cl) sum_{c < Cl} y_c        var = (1 / Cl) sum_{c < Cl} (y_c - mean)^2      (passes over registers: the
+ *      rstd = 1 / sqrt(var + eps)              xh_c = (y_c - mean) * rstd                       differences are formed BEFORE they
+ *      out_c = max(0, xh_c * w_c + b_c)  for c < Cl,      out_c = 0.0f exactly for Cl <= c < 128    are squared, no E[y^2] - mean^2)
+ * (kgwlnorm_out; the row sums go over the 32 lanes of a row by a butterfly, xor 16, 8, 4, 2, 1).  In float32 the mean is refined
+ * once -- m0 = sum(y) / Cl, mean = m0 + sum(y - m0) / Cl, y_c - mean taken as (y_c - m0) - sum(y - m0) / Cl -- because at a row
+ * mean of 1e4 a single float32 quotient is good to 5e-4 only, which a unit spread would see in every xh; the backward centres the
+ * row again the same way around the stored mean.  Sums and means are correctly rounded divisions by Cl, so a constant row of
+ * exactly summable values has mean = the value, var = 0, rstd = 1 / sqrt(eps) and out = max(0, b) bit for bit.  Backward, with
+ * g the upstream gradient ALREADY masked by (out > 0) -- the consumer did it (out == NULL) or the kernel does it from the saved out:
+ *      gh_c = g_c w_c       dy_c = rstd (gh_c - mean_c(gh) - xh_c mean_c(gh xh))     (means over c < Cl;  dy_c = 0.0f for c >= Cl)
+ *      dw_c = sum_rows g_rc xh_rc           db_c = sum_rows g_rc                     (kgwlnorm_dy; 0.0f for c >= Cl)
+ *
+ * kgw_layer_norm_relu_fwd: one launch for up to 8 jobs (the destination types of one layer), the row mapping of
+ * kgw_hidden_dropout (one float4 per lane, 32 lanes per row, grid-stride over the rows of all jobs, no LDS, no atomics).  Job j
+ * reads rows [0, rows) at src + i * lds, writes out to dst + i * ldd and stat[2 i], stat[2 i + 1] = (mean, rstd); weight / bias
+ * point at the 128 floats of the job's node type.  src is only read (whoever produced it may have saved it): dst == src is refused.
+ * kgw_layer_norm_bwd: job j reads g, the saved y, stat, weight and (out != NULL) the saved out, and writes dy.  The column sums
+ * are left as PER-BLOCK partial sums: job j owns the blocks [b0_j, b0_j + nb_j) of the grid, nb_j = ceil(rows_j / P) with P = 64
+ * doubled until the grid has at most 2048 blocks -- a function of the row counts alone, so the layout and with it the bits are the
+ * same on every run and every device.  A block walks its job's rows with stride 8 nb_j (8 row slots), every slot adds its rows in
+ * ascending order, the 8 slots are added through LDS in slot order, and the block writes partial[block][2][128] = (dw, db).
+ * kgw_layer_norm_partial_floats: the floats ``partial`` must hold for these jobs.  (One job per block rather than a
+ * [block][job] table: the same fixed order, an eighth of the partial sums.)
+ * kgw_layer_norm_fold: the SAME jobs; block t of n_types adds the partial sums of the job whose ``type`` is t in ascending block
+ * order into dweight[t][128], dbias[t][128]; a type without a job, or whose job has no rows, gets zero rows.  No floating-point
+ * atomics anywhere.
+ * Refused before any launch: a NULL jobs / partial / dweight / dbias, a NULL pointer of a job with rows > 0 (``out`` may be
+ * NULL): KGW_E_NULL;  n_jobs outside [1, 8], c_logical outside [1, 128], an eps that is not finite or < 0, rows < 0 or > 2^25, a
+ * leading dimension < 128 with rows > 1, partial_floats too small, n_types outside [1, 8], a type outside [0, 8) / [0, n_types),
+ * two jobs of one type (bwd, fold): KGW_E_RANGE;  a row pointer or weight / bias not 16-byte aligned, stat not 8-byte aligned, a
+ * leading dimension % 4 != 0, dst == src: KGW_E_UNSUPPORTED.  Jobs without rows are skipped; no rows at all: no fwd / bwd launch. */
+#define KGW_LNORM_EPS 1e-5f
+KGWFAN_INLINE float kgwlnorm_out(float xh, float w, float b) { const float v = xh * w + b; return v > 0.0f ? v : 0.0f; }
+KGWFAN_INLINE float kgwlnorm_dy(float gh, float xh, float rstd, float mean_gh, float mean_ghxh) {
+    return rstd * (gh - mean_gh - xh * mean_ghxh);
+}
+typedef struct KgwLNormJob {
+    const float* src; int64_t lds;    /* y: rows of 128 floats, leading dimension in floats                                        */
+    float* dst; int64_t ldd;          /* out                                                                                       */
+    int32_t rows;
+    int32_t type;                     /* node type id of the schema (names the job; weight / bias already point at its row)        */
+    const float* weight; const float* bias;       /* [128] each, columns c_logical .. 127 ignored                                 */
+    float* stat;                      /* [rows][2]: (mean, rstd)                                                                   */
+} KgwLNormJob;
+typedef struct KgwLNormBwdJob {
+    const float* g; int64_t ldg;      /* upstream gradient                                                                         */
+    const float* y; int64_t ldy;      /* the forward's src                                                                         */
+    const float* out; int64_t ldo;    /* the forward's dst, to mask g by (out > 0); NULL: g arrives masked                         */
+    float* dy; int64_t lddy;
+    int32_t rows;
+    int32_t type;                     /* node type id: the row of dweight / dbias the fold writes                                  */
+    const float* weight;              /* [128]                                                                                     */
+    const float* stat;                /* [rows][2] of the forward                                                                  */
+} KgwLNormBwdJob;
+int kgw_layer_norm_relu_fwd(int32_t n_jobs, const KgwLNormJob* jobs, int32_t c_logical, float eps, kgw_stream_t stream);
+int64_t kgw_layer_norm_partial_floats(int32_t n_jobs, const KgwLNormBwdJob* jobs);      /* (< 0: a status)                        */
+int kgw_layer_norm_bwd(int32_t n_jobs, const KgwLNormBwdJob* jobs, int32_t c_logical, float* partial, int64_t partial_floats,
+                       kgw_stream_t stream);
+int kgw_layer_norm_fold(int32_t n_jobs, const KgwLNormBwdJob* jobs, const float* partial, int64_t partial_floats, int32_t n_types,
+                        float* dweight, float* dbias, kgw_stream_t stream);
+
 /* Sigmoid-gated attention (KGW_F_SIGMOID_GATE): alpha = sigmoid(leaky_relu(a_j + a_i) / T) instead of the softmax over the row
  * (kgwas/conv.py:49,219-220, the reference GATConv's sigmoid_gat; its HeteroGNN never passes it, so like the dropout this is an
  * EXTENSION, off by default).  The gates are independent per edge and are not normalised by the row's degree.  With

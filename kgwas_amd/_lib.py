@@ -163,6 +163,17 @@ class KgwHDropJob(C.Structure):
     _fields_ = [('src', C.c_void_p), ('lds', C.c_int64), ('dst', C.c_void_p), ('ldd', C.c_int64), ('rows', C.c_int32), ('type', C.c_int32)]
 
 
+class KgwLNormJob(C.Structure):
+    _fields_ = [('src', C.c_void_p), ('lds', C.c_int64), ('dst', C.c_void_p), ('ldd', C.c_int64), ('rows', C.c_int32), ('type', C.c_int32),
+                ('weight', C.c_void_p), ('bias', C.c_void_p), ('stat', C.c_void_p)]
+
+
+class KgwLNormBwdJob(C.Structure):
+    _fields_ = [('g', C.c_void_p), ('ldg', C.c_int64), ('y', C.c_void_p), ('ldy', C.c_int64), ('out', C.c_void_p), ('ldo', C.c_int64),
+                ('dy', C.c_void_p), ('lddy', C.c_int64), ('rows', C.c_int32), ('type', C.c_int32), ('weight', C.c_void_p),
+                ('stat', C.c_void_p)]
+
+
 class KgwFoldArgs(C.Structure):
     _fields_ = [('n', C.c_int32), ('n_rels', C.c_int32), ('n_mlp', C.c_int32), ('duv_pieces', C.c_int32),
                 ('rel_ids_host', C.c_void_p), ('src_mlp_host', C.c_void_p), ('dst_mlp_host', C.c_void_p),
@@ -181,7 +192,8 @@ EXPORTS = ['kgw_version', 'kgw_status_string', 'kgw_struct_sizes', 'kgw_sample_b
            'kgw_gather_rows', 'kgw_gather_rows_multi', 'kgw_scatter_relu_rows', 'kgw_scatter_relu_rows_workspace_floats', 'kgw_edge_alpha', 'kgw_debug_reduce', 'kgw_debug_reduce8', 'kgw_tn_gemm', 'kgw_tn_gemm_ex', 'kgw_tn_gemm_multi', 'kgw_tn_gemm_workspace_floats', 'kgw_tn_gemm_partial', 'kgw_tn_gemm_multi_partial', 'kgw_tn_split', 'kgw_tn_direct_rows', 'kgw_param_tail', 'kgw_tn_reduce_launch', 'kgw_tn_gemm_partial_ride', 'kgw_transform_bwd_ex', 'kgw_mlp2_bwd_first_partial', 'kgw_mlp2_bwd_first_packed', 'kgw_adam_fused', 'kgw_gemm3_partial', 'kgw_gemm3_flip', 'kgw_transform_bwd', 'kgw_grad_finish',
            'kgw_linear', 'kgw_mlp2_fwd', 'kgw_mlp2w_fwd', 'kgw_mlp2_bwd_first', 'kgw_mlp2_bwd_first_workspace_floats', 'kgw_gemm3', 'kgw_gemm3_riders', 'kgw_gemm3_rider_blocks', 'kgw_gemm3_pack', 'kgw_gemm3_packed_bytes', 'kgw_gemm3_workspace_floats', 'kgw_adam', 'kgw_adam_notick', 'kgw_relvec_fwd', 'kgw_relvec_bwd', 'kgw_relvec_bwd_acc', 'kgw_relvec_fwd_multi', 'kgw_relvec_bwd_multi', 'kgw_wmse_fwd', 'kgw_wmse_bwd', 'kgw_readout_wmse_fwd', 'kgw_readout_wmse_bwd', 'kgw_readout_wmse_train', 'kgw_readout_wmse_train_parts', 'kgw_readout_train_fold', 'kgw_readout_mt_pred', 'kgw_readout_mt_pred_bwd', 'kgw_readout_wmse_mt_fwd', 'kgw_readout_wmse_mt_bwd',
            'kgw_readout_wmse_mt_train', 'kgw_readout_wmse_mtw_fwd', 'kgw_readout_wmse_mtw_bwd', 'kgw_readout_wmse_mtw_train',
-           'kgw_accumulate_stats', 'kgw_accumulate_stats_tick', 'kgw_hidden_dropout']
+           'kgw_accumulate_stats', 'kgw_accumulate_stats_tick', 'kgw_hidden_dropout',
+           'kgw_layer_norm_relu_fwd', 'kgw_layer_norm_partial_floats', 'kgw_layer_norm_bwd', 'kgw_layer_norm_fold']
 
 _lib = None
 
@@ -346,6 +358,13 @@ def lib():
         L.kgw_readout_wmse_mtw_train.argtypes = L.kgw_readout_wmse_mt_train.argtypes
     if hasattr(L, 'kgw_hidden_dropout'):            # (absent from an older library named by KGW_LIB_PATH for an A/B run)
         L.kgw_hidden_dropout.argtypes = [C.c_int32, C.POINTER(KgwHDropJob), C.c_int32, C.c_void_p, C.c_uint32, C.c_float, C.c_void_p]
+    if hasattr(L, 'kgw_layer_norm_relu_fwd'):       # (absent likewise)
+        L.kgw_layer_norm_relu_fwd.argtypes = [C.c_int32, C.POINTER(KgwLNormJob), C.c_int32, C.c_float, C.c_void_p]
+        L.kgw_layer_norm_partial_floats.argtypes = [C.c_int32, C.POINTER(KgwLNormBwdJob)]
+        L.kgw_layer_norm_partial_floats.restype = C.c_int64
+        L.kgw_layer_norm_bwd.argtypes = [C.c_int32, C.POINTER(KgwLNormBwdJob), C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]
+        L.kgw_layer_norm_fold.argtypes = [C.c_int32, C.POINTER(KgwLNormBwdJob), C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p,
+                                          C.c_void_p]
     L.kgw_accumulate_stats.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
     L.kgw_accumulate_stats_tick.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     _lib = L
@@ -386,6 +405,12 @@ def has_hidden_dropout() -> bool:
     """Does the loaded library have kgw_hidden_dropout (hidden-state dropout between the layers)?  An older library named by
     KGW_LIB_PATH for an A/B run lacks the symbol."""
     return hasattr(lib(), 'kgw_hidden_dropout')
+
+
+def has_layer_norm() -> bool:
+    """Does the loaded library have the layer-normalisation kernels (kgw_layer_norm_relu_fwd / _bwd / _fold)?  An older library
+    named by KGW_LIB_PATH for an A/B run lacks the symbols."""
+    return hasattr(lib(), 'kgw_layer_norm_relu_fwd')
 
 
 KGW_ORDER_SEEDS, KGW_ORDER_BATCHES = 1, 2     # kgw_epoch_order's modes (include/kgwas_hip.h)

@@ -11,6 +11,7 @@
 //   kgw_readout_order.h     the fixed summation orders of the read-out fold, shared by kgw_dense_loss.h and kgw_dense_transform.h
 //   kgw_dense_relvec.h      attention vectors u_r / v_r (conv.py:138-151) and the parameter-only end of the backward pass
 //   kgw_dense_hdrop.h       hidden-state dropout between the layers (an extension: HeteroGNN(gnn_dropout=p)), forward and backward
+//   kgw_dense_lnorm.h       layer normalisation + ReLU between the layers (an extension: HeteroGNN(gnn_norm='layer')), forward, backward, fold
 //
 // Mapping of the tall TN product (gfx950): v_mfma_f32_32x32x2_f32.  The MFMA operand layout IS the memory layout:
 // lane l supplies A[row k = l>>5][column i = l&31] -- a wave-instruction reads two contiguous 128-float rows.
@@ -31,3 +32,4 @@
 #include "kgw_dense_loss.h"
 #include "kgw_dense_relvec.h"
 #include "kgw_dense_hdrop.h"
+#include "kgw_dense_lnorm.h"

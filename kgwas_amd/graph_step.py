@@ -243,6 +243,9 @@ class GraphTrainStep:
         replay -- the kernels read it when they run.  The batches themselves stay the same from epoch to epoch (BatchCache on).
         A model with ``gnn_dropout > 0`` (``self.hidden_dropout``; ``self.dropout`` keeps meaning ATTENTION dropout, which alone
         takes the unfolded route) is fed the same way: training-mode capture, the word copy ahead of every replay, ``set_epoch``.
+        A model with ``gnn_norm`` (``self.layer_norm``) needs nothing from the trainer: its three launches per site are captured with
+        the rest, their row statistics and partial column sums are allocations of the capture (static for the captured capacities),
+        and its parameters take their place in the optimiser's tables -- 2 (L - 1) more tensors, the fused launch while they fit.
         ``epoch_order`` ('fixed' | 'seeds' | 'batches', NeighborLoader): the order in which an epoch visits the seeds, a pure function
         of (``sample_seed``, epoch) written on the device once per epoch (kgw_epoch_order); ``step(i)`` trains on batch i of the epoch
         ``set_epoch`` named, and a step past the last batch moves on to the next epoch by itself.  'seeds': the batches of every
@@ -288,6 +291,7 @@ class GraphTrainStep:
         # hidden-state dropout reads the same word; it keeps the FC_output fold and the fused optimiser launch
         self.hidden_dropout = float(getattr(self.model, 'gnn_dropout', 0.0)) > 0.0
         self._drops = self.dropout or self.hidden_dropout
+        self.layer_norm = getattr(self.model, 'gnn_norm', None) is not None
         self._drop_words = {}
         self.ld_w = run._ld_weight_vector()             # ([N] or, per-trait weights, [N, T]: resident, read in place by the graph)
         self.world = 1

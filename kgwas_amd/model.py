@@ -300,11 +300,26 @@ class HeteroGNN(nn.Module):
     type, local row, column) -- kgwhdrop_keep in include/kgwas_hip.h.  Never on the feature MLPs' output, so the FC_output fold, the
     parameter riders and the fused optimiser launch stay; every backbone, aggregation and attention switch takes it.  Needs
     ``num_layers >= 2`` (there is no site otherwise).  Evaluation, the attention queries and the export never drop; 0 (the default)
-    runs exactly the launches the model ran without it."""
+    runs exactly the launches the model ran without it.
+    ``gnn_norm`` = 'layer' (an extension, keyword only: PyG's BasicGNN runs conv -> norm -> act -> dropout, the reference's HeteroGNN
+    has no norm): the pre-activation output y of every message-passing layer but the last -- the relation sum, or the relation
+    mean (the 1 / R goes in BEFORE the norm) / min / max -- becomes relu(LN_{l,t}(y)), LN = torch.nn.LayerNorm(hidden, eps=1e-5)
+    per node, one per site and per node type that is the destination of some relation (PyG's LayerNorm(mode='node') as to_hetero
+    would duplicate it); ``gnn_dropout`` then reads the norm's output.  One forward launch per site, a backward and a fold launch
+    (ops.layer_norm_relu, kgwlnorm_* in include/kgwas_hip.h).  Learned, and live in evaluation, the attention queries and the
+    export alike (the export, which applies no ReLU between the layers, applies the norm without one).  The parameters of a site
+    are ONE packed pair ``norm_weight[l - 1]`` / ``norm_bias[l - 1]`` [n_node_types, 128]: row t for node type t, the columns past
+    the model's width and the rows of types that receive no relation zero and kept zero; under the reference's names
+    ``norms.<l - 1>.<node type>.weight`` / ``.bias`` (the index of the ``convs.<l - 1>`` they follow) at the model's own width.  A
+    type that has no rows in a batch's layer gets ZERO gradient rows, where one torch module per type would leave ``grad`` None:
+    with weight decay such a row still decays.  The FC_output fold, the parameter riders and the fused optimiser launch stay (the
+    norm sits after the layer-1 transform).  Needs ``num_layers >= 2``; ``None`` (the default) is the model as ever, launch for
+    launch and bit for bit."""
 
     def __init__(self, pyg_data, hidden_channels, out_channels, num_layers, gnn_backbone, gnn_aggr,
                  snp_init_dim_size, gene_init_dim_size, go_init_dim_size, gat_num_head, no_relu=False, gat_dropout=0.0,
-                 gat_split_heads=False, *, gat_sigmoid=False, gat_temperature=1.0, gat_edge_dim=None, gnn_dropout=0.0):
+                 gat_split_heads=False, *, gat_sigmoid=False, gat_temperature=1.0, gat_edge_dim=None, gnn_dropout=0.0,
+                 gnn_norm=None):
         super().__init__()
         if gnn_backbone not in ('GAT', 'SAGE'):
             raise NotImplementedError(f"backbone {gnn_backbone!r}: 'GAT' (the reference default, kgwas.py:52) and 'SAGE' "
@@ -325,6 +340,12 @@ class HeteroGNN(nn.Module):
             raise ValueError(f'gnn_dropout > 0 with num_layers = {num_layers}: the hidden state is dropped BETWEEN message-passing '
                              'layers, and one layer has no such site')
         self.gnn_dropout = gnn_dropout
+        if gnn_norm not in (None, 'layer'):
+            raise ValueError(f"gnn_norm {gnn_norm!r}: None (the reference's model) or 'layer'")
+        if gnn_norm is not None and int(num_layers) < 2:
+            raise ValueError(f'gnn_norm with num_layers = {num_layers}: the hidden state is normalised BETWEEN message-passing '
+                             'layers, and one layer has no such site')
+        self.gnn_norm = gnn_norm
         # the 64-bit word of the step's masks (attention and hidden-state dropout alike: the rules keep them apart), resident on
         # the device: the kernels read it when they run, so a captured step replays with whatever the trainer copied here
         # (set_dropout_word / GraphTrainStep).  Not part of the state_dict.
@@ -480,6 +501,15 @@ class HeteroGNN(nn.Module):
                 self._fold_tab = (np.asarray(order, dtype=np.int32), np.asarray(sm, dtype=np.int32), np.asarray(dm, dtype=np.int32))
                 self.register_buffer('_fold_src_m', torch.tensor(sm, dtype=torch.long), persistent=False)
                 self.register_buffer('_fold_dst_m', torch.tensor(dm, dtype=torch.long), persistent=False)
+        # layer normalisation: one packed (weight, bias) pair per site l = 1 .. L - 1, row t = node type t; none without gnn_norm, so
+        # the default model's parameters are what they were
+        self.norm_types = [t for t in range(sc.NT) if sc.rels_by_dst[t]] if gnn_norm is not None else []
+        self.norm_weight, self.norm_bias = nn.ParameterList(), nn.ParameterList()
+        for _ in range(num_layers - 1 if gnn_norm is not None else 0):
+            w = torch.zeros(sc.NT, hidden_channels)
+            w[self.norm_types, :cl] = 1.0
+            self.norm_weight.append(nn.Parameter(w))
+            self.norm_bias.append(nn.Parameter(torch.zeros(sc.NT, hidden_channels)))
         # dead packs never receive gradients; keep them out of autograd entirely
         for p in self.dead_packs.parameters():
             p.requires_grad_(False)
@@ -637,7 +667,7 @@ class HeteroGNN(nn.Module):
                         ops.LIBRARY_GEMM.note('sage min/max per-relation outputs', R, rows, C)
                         o = torch.baddbmm(P.bias[lo:hi].unsqueeze(1), zr, P.w_l_t[lo:hi]) + \
                             torch.matmul(h[name][:rows].unsqueeze(0), P.w_r_t[lo:hi])
-                    h_next[name] = torch.relu(self._combine_relations(o))
+                    h_next[name] = self._combine_relations(o)
                     continue
                 x = Z[z0:z0 + rows * R].view(rows, R * C)
                 y = ops.linear_act(x, P.w_l_t[lo:hi].reshape(R * C, C), P.bias[lo:hi].sum(0), relu=False)
@@ -648,8 +678,8 @@ class HeteroGNN(nn.Module):
                     y = y + h[name][:rows] @ P.w_r_t[lo:hi].sum(0)        # root term: sum_r lin_r^r(h_d[i])
                 if self.aggr == 'mean':
                     y = y * (1.0 / R)
-                h_next[name] = torch.relu(y)
-            h = self._drop_hidden(l, h_next, hdrop)
+                h_next[name] = y
+            h = self._drop_hidden(l, self._activate(l, h_next), hdrop)
         return h, []
 
     def _all_layer_params(self, batch: SampledBatch, folded: bool):
@@ -769,12 +799,18 @@ class HeteroGNN(nn.Module):
             Z, _, _ = ops.gat_aggregate(batch, l, H, U, V, self.negative_slope, self.temperature, relu_input=(l > 1), heads=NH)
             hbuf, nxt = self._layer_input(batch, l + 1) if l < self.num_layers else (None, {})
             drops = hdrop is not None and l < self.num_layers
-            # (a layer whose output is dropped leaves the next layer's blocks to the dropout launch: see _fused_layers)
-            outs = ops.layer_transform_heads(P, Z, blocks, self.head_mask, None if drops else [nxt.get(sc.node_types[t]) for t in tys],
-                                             premasked=(l < self.num_layers) or last_premasked)
+            site = self._norm_site(l)
+            # (a layer whose output is normalised or dropped leaves the next layer's blocks to the LAST of those launches: see
+            #  _fused_layers)
+            later = drops or site is not None
+            outs = ops.layer_transform_heads(P, Z, blocks, self.head_mask, None if later else [nxt.get(sc.node_types[t]) for t in tys],
+                                             premasked=(l < self.num_layers) or last_premasked, relu=site is None)
             if self.aggr == 'mean':
-                hbuf = None if not drops else hbuf
+                hbuf = None if not later else hbuf
                 outs = [o * (1.0 / (hi - lo)) for o, (lo, hi, _, _) in zip(outs, blocks)]
+            if site is not None:
+                outs = ops.layer_norm_relu(outs, tys, site[0], site[1], self.hidden_logical,
+                                           None if drops else [nxt.get(sc.node_types[t]) for t in tys], premasked=True)
             if drops:
                 outs = ops.hidden_dropout(outs, tys, l, hdrop[0], hdrop[1], [nxt.get(sc.node_types[t]) for t in tys])
             h = {sc.node_types[t]: o for t, o in zip(tys, outs)}
@@ -812,6 +848,27 @@ class HeteroGNN(nn.Module):
             return h
         names = list(h)
         outs = ops.hidden_dropout([h[n] for n in names], [self.schema.type_id[n] for n in names], l, hdrop[0], hdrop[1])
+        return dict(zip(names, outs))
+
+    def _norm_site(self, l: int):
+        """(weight, bias) [n_node_types, 128] of the normalisation after layer l, or None: a model without ``gnn_norm``, or the
+        last layer.  In every mode: the norm is part of the function the model computes, not of its training."""
+        return (self.norm_weight[l - 1], self.norm_bias[l - 1]) if self.gnn_norm is not None and l < self.num_layers else None
+
+    def _activate(self, l: int, pre: Dict[str, torch.Tensor], relu: bool = True):
+        """The activation of layer l on per-type PRE-ACTIVATIONS that are framework tensors (SAGE, the relation min / max, the
+        all-relations routes): the ReLU of model.py:75, or at a norm site relu(LN(y)) for all types in one launch, whose backward
+        masks by the saved output.  ``relu=False`` (the export: utils.py:460 applies no ReLU) leaves the plain state, or LN(y) =
+        relu(LN(y)) - relu(-LN(y)) exactly: the kernel twice, the second time with the negated parameters."""
+        site = self._norm_site(l)
+        if site is None or not pre:
+            return {n: torch.relu(y) for n, y in pre.items()} if relu else pre
+        names = list(pre)
+        ys, tys = [pre[n] for n in names], [self.schema.type_id[n] for n in names]
+        outs = ops.layer_norm_relu(ys, tys, site[0], site[1], self.hidden_logical)
+        if not relu:
+            neg = ops.layer_norm_relu(ys, tys, -site[0].detach(), -site[1].detach(), self.hidden_logical)
+            outs = [a - b for a, b in zip(outs, neg)]
         return dict(zip(names, outs))
 
     def _fused_layers(self, batch: SampledBatch, h: Dict[str, torch.Tensor], want_attention=False, hbuf=None,
@@ -872,8 +929,8 @@ class HeteroGNN(nn.Module):
                     else:
                         ops.LIBRARY_GEMM.note('gat min/max per-relation outputs', R, rows, C)
                         o = torch.baddbmm(P.bias[lo:hi].unsqueeze(1), zr, Wv[lo:hi])
-                    outs.append(torch.relu(self._combine_relations(o)))
-                h = self._drop_hidden(l, {sc.node_types[t]: o for t, o in zip(tys, outs)}, hdrop)
+                    outs.append(self._combine_relations(o))
+                h = self._drop_hidden(l, self._activate(l, {sc.node_types[t]: o for t, o in zip(tys, outs)}), hdrop)
                 continue
             # per-relation linear maps + bias + relation sum + ReLU: one GEMM per destination type, one autograd node
             hbuf, nxt = self._layer_input(batch, l + 1) if l < self.num_layers else (None, {})
@@ -881,14 +938,23 @@ class HeteroGNN(nn.Module):
             # dropout launch writes the dropped state into the next layer's blocks, so no join_blocks copy is added.  The next
             # aggregate folds dH *= (H > 0) with H the DROPPED state (kept and positive); the dropout's backward supplies the scale.
             drops = hdrop is not None and l < self.num_layers
-            outs = ops.layer_transform(P, Z, blocks, None if drops else [nxt.get(sc.node_types[t]) for t in tys],
+            # layer normalisation of this layer's output: the transform then stops at the pre-activation (its backward has no ReLU
+            # left: premasked), the norm's launch applies LN and the ReLU and writes the next layer's blocks (or, with dropout
+            # behind it, a temporary).  The next aggregate folds dH *= (H > 0) with H the norm's output: premasked for the norm too.
+            site = self._norm_site(l)
+            later = drops or site is not None
+            outs = ops.layer_transform(P, Z, blocks, None if later else [nxt.get(sc.node_types[t]) for t in tys],
                                        premasked=(l < self.num_layers) or last_premasked, bias_sum=bsum,
-                                       weight=Wp if Wp is not None else Wv, gamma=gam, stat=stat if gam is not None else None)
+                                       weight=Wp if Wp is not None else Wv, gamma=gam, stat=stat if gam is not None else None,
+                                       relu=site is None)
             if self.aggr == 'mean':
                 # mean over the relations of a destination type = the sum scaled by 1/R; relu(s/R) = relu(s)/R, and the
-                # positive scale commutes with the folded ReLU masks
-                hbuf = None if not drops else hbuf
+                # positive scale commutes with the folded ReLU masks.  At a norm site the scale goes in BEFORE the norm: LN(y / R)
+                hbuf = None if not later else hbuf
                 outs = [o * (1.0 / (hi - lo)) for o, (lo, hi, _, _) in zip(outs, blocks)]
+            if site is not None:
+                outs = ops.layer_norm_relu(outs, tys, site[0], site[1], self.hidden_logical,
+                                           None if drops else [nxt.get(sc.node_types[t]) for t in tys], premasked=True)
             if drops:
                 outs = ops.hidden_dropout(outs, tys, l, hdrop[0], hdrop[1], [nxt.get(sc.node_types[t]) for t in tys])
             h_next = {sc.node_types[t]: o for t, o in zip(tys, outs)}
@@ -1024,9 +1090,9 @@ class HeteroGNN(nn.Module):
                     pack = self.live_packs[l - 1] if which == 'live' else self.dead_packs[l - 1]
                     ws.append(pack.w_src_t[i])
                     bs = bs + pack.bias[i]
-                y = ops.linear(x, torch.cat(ws, 0), bs, w_kn=True)
-                h_next[name] = y if raw else torch.relu(y)                   # model.py:75 / no ReLU at utils.py:460
-            h = h_next
+                h_next[name] = ops.linear(x, torch.cat(ws, 0), bs, w_kn=True)
+            h = self._activate(l, h_next, relu=not raw)                      # model.py:75 / no ReLU at utils.py:460
+
         return h, per_layer
 
     @torch.no_grad()
@@ -1153,6 +1219,17 @@ class HeteroGNN(nn.Module):
                         t = t[:cl]
                 yield f'{prefix}.{n}', t
 
+    def _norm_items(self, grad: bool = False, keep_vars: bool = False):
+        """(``norms.<l>.<node type>.weight`` | ``.bias``, the type's row of the site's packed tensor at the model's own width) for the
+        norm after ``convs.<l>`` -- nothing for a model without ``gnn_norm``.  ``grad``: rows of the packed gradient; a type without
+        rows in the batch has a ZERO row there (ops.layer_norm_relu), not None."""
+        cl = self.hidden_logical
+        for l, (w, b) in enumerate(zip(self.norm_weight, self.norm_bias)):
+            for t in self.norm_types:
+                for f, p in (('weight', w), ('bias', b)):
+                    v = p.grad if grad else (p if keep_vars else p.detach())
+                    yield f'norms.{l}.{self.node_types[t]}.{f}', None if v is None else v[t, :cl]
+
     def named_reference_tensors(self, grad: bool = False) -> "OrderedDict[str, Optional[torch.Tensor]]":
         """Parameters (or their gradients) under the reference's names.  Lazy lin_dst of same-type relations
         is omitted; structurally dead relations have gradient None."""
@@ -1163,6 +1240,8 @@ class HeteroGNN(nn.Module):
             out[k] = v
         for k, t in self._dense_items(grad):
             out[k] = t
+        for k, t in self._norm_items(grad):
+            out[k] = t
         return out
 
     def state_dict(self, *args, destination=None, prefix='', keep_vars=False):
@@ -1171,6 +1250,8 @@ class HeteroGNN(nn.Module):
             out[prefix + k] = torch.nn.parameter.UninitializedParameter() if isinstance(v, str) else v.clone()
         for k, t in self._dense_items(keep_vars=keep_vars):
             out[prefix + k] = t
+        for k, t in self._norm_items(keep_vars=keep_vars):
+            out[prefix + k] = t.clone()
         return out
 
     def load_state_dict(self, state_dict, strict=True, **kw):
@@ -1195,16 +1276,16 @@ class HeteroGNN(nn.Module):
         missing = [k for k, (l, r, f) in want.items() if k not in seen and
                    not (f == 'lin_dst.weight' and self.edge_types[r][0] == self.edge_types[r][2])]
         unexpected = []
-        known = ('snp_feat_mlp.', 'go_feat_mlp.', 'gene_feat_mlp.', 'lin.')
+        known = ('snp_feat_mlp.', 'go_feat_mlp.', 'gene_feat_mlp.', 'lin.', 'norms.')
         with torch.no_grad():
-            for k, dst in self._dense_items():              # (views of the padded storage at the model's own width)
+            for k, dst in list(self._dense_items()) + list(self._norm_items()):     # (views of the padded storage at the model's own width)
                 if k in rest:
                     if tuple(rest[k].shape) != tuple(dst.shape):
                         raise RuntimeError(f'load_state_dict: {k} has shape {tuple(rest[k].shape)}, the model expects {tuple(dst.shape)}')
                     dst.copy_(rest[k])
                 else:
                     missing.append(k)
-        have = {k for k, _ in self._dense_items()}
+        have = {k for k, _ in self._dense_items()} | {k for k, _ in self._norm_items()}
         unexpected += [k for k in rest if k.startswith(known) and k not in have]
         unexpected += [k for k in rest if not k.startswith(known)]
         if strict and (missing or unexpected):

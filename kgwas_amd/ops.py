@@ -2193,7 +2193,7 @@ def rel_vectors(pack, blocks=None, zero=None, pass_weights=False):
 _MULTI_TRANSFORM = os.environ.get('KGW_MULTI_TRANSFORM', '1') != '0'     # (A/B: one launch per destination type as before)
 
 
-def _transform_multi_forward(w_src_t, Z, blocks, bsum, out_blocks, gamma, stat, C):
+def _transform_multi_forward(w_src_t, Z, blocks, bsum, out_blocks, gamma, stat, C, relu=True):
     """All forward transforms of a layer through ONE kgw_linear_splitk_multi launch, or None when the layer does not qualify
     (a single destination type, a single relation into one, an unaligned operand, too many rows for the few-rows kernel)."""
     live = [(k, b) for k, b in enumerate(blocks) if b[3] > 0]
@@ -2214,7 +2214,7 @@ def _transform_multi_forward(w_src_t, Z, blocks, bsum, out_blocks, gamma, stat, 
         if x.data_ptr() % 16 or y.data_ptr() % 16 or y.stride(0) % 4 or (gamma is not None and gamma[lo:hi].data_ptr() % 16):
             return None
         j.X, j.ldx, j.W, j.ldw, j.bias = x.data_ptr(), x.stride(0), W.data_ptr(), W.stride(0), bsum[k].data_ptr()
-        j.Y, j.ldy, j.rows, j.K, j.N, j.relu, j.w_is_kn = y.data_ptr(), y.stride(0), rows, R * C, C, 1, 1
+        j.Y, j.ldy, j.rows, j.K, j.N, j.relu, j.w_is_kn = y.data_ptr(), y.stride(0), rows, R * C, C, int(relu), 1
         if gamma is not None:
             j.seg_stat, j.gamma = stat.data_ptr() + 8 * z0, gamma[lo:hi].data_ptr()
         outs.append(y)
@@ -2299,15 +2299,18 @@ class _LayerTransform(torch.autograd.Function):
     """h_d = relu([Z[:, r0] | Z[:, r1] | ...] @ [W_r0^T ; W_r1^T ; ...] + sum_r bias_r) for every destination
     type of a layer (lin_src of kgwas/conv.py:138/142 + bias :190 + HeteroConv sum model.py:74 + ReLU :75).
     ``Z`` is the aggregate's type-major output; ``blocks`` = [(lo, hi, z0, rows)]: relations [lo, hi) of the packed
-    arrays feed the destination type whose block starts at Z row z0 and has ``rows`` destination rows."""
+    arrays feed the destination type whose block starts at Z row z0 and has ``rows`` destination rows.  ``relu=False`` (a layer
+    whose output is normalised before its ReLU: ops.layer_norm_relu) returns the pre-activation on every route -- the multi launch,
+    kgw_linear_splitk_ind and kgw_linear all carry the flag -- and the backward then needs ``premasked=True``: no ReLU is left in it."""
 
     @staticmethod
-    def forward(ctx, w_src_t, bias, Z, blocks, bsum, out_blocks, premasked=False, gamma=None, stat=None):
+    def forward(ctx, w_src_t, bias, Z, blocks, bsum, out_blocks, premasked=False, gamma=None, stat=None, relu=True):
+        assert relu or premasked
         C = bias.shape[1]
         outs, ys = [], []
         # every destination type's transform of the layer in ONE launch (kgw_linear_splitk_multi) when there are several and
         # all are of the fused-forward kind: K = R * 128 > 128 rows-few problems that each leave most of the chip idle
-        multi = _transform_multi_forward(w_src_t, Z, blocks, bsum, out_blocks, gamma, stat, C)
+        multi = _transform_multi_forward(w_src_t, Z, blocks, bsum, out_blocks, gamma, stat, C, relu)
         if multi is not None:
             ctx.save_for_backward(w_src_t, Z, gamma, stat, *multi)
             ctx.blocks = blocks
@@ -2328,13 +2331,15 @@ class _LayerTransform(torch.autograd.Function):
                 ws = torch.empty(nws, device=Z.device)
                 W = w_src_t[lo:hi].view(R * C, C)
                 _lib.check(L.kgw_linear_splitk_ind(_p(x), x.stride(0), _p(W), W.stride(0), _p(bsum[k]), _p(y), y.stride(0), rows,
-                                                   R * C, 1, stat.data_ptr() + 8 * z0, _p(gamma[lo:hi]), _p(ws), nws, None,
+                                                   R * C, int(relu), stat.data_ptr() + 8 * z0, _p(gamma[lo:hi]), _p(ws), nws, None,
                                                    _lib.stream_ptr()), 'kgw_linear_splitk_ind')
             else:
-                y = linear(x, w_src_t[lo:hi].view(R * C, C), bsum[k], relu=False if gamma is not None else True, w_kn=True, out=out)
+                y = linear(x, w_src_t[lo:hi].view(R * C, C), bsum[k], relu=relu and gamma is None, w_kn=True, out=out)
                 if gamma is not None and rows:      # (single relation into the type: no K split; rare, framework ops)
                     ind = (stat[z0:z0 + rows * R, 1] > 0).to(y.dtype).view(rows, R)
-                    y = torch.relu_(y.add_((ind.unsqueeze(2) * gamma[lo:hi].unsqueeze(0)).sum(1)))
+                    y = y.add_((ind.unsqueeze(2) * gamma[lo:hi].unsqueeze(0)).sum(1))
+                    if relu:
+                        y = torch.relu_(y)
             outs.append(y)
             ys.append(y)
         ctx.save_for_backward(w_src_t, Z, gamma, stat, *ys)
@@ -2374,7 +2379,7 @@ class _LayerTransform(torch.autograd.Function):
         # everything that is a function of dz alone -- weight / bias gradients, dZ twins, d gamma sums, of every destination type -- as
         # blocks of ONE launch (+ the split-K products' second) where the kernels' shape conditions hold (kgw_transform_bwd)
         if _MERGED_TRANSFORM_BWD and _transform_bwd_merged(live_blocks, dW, db, dZ if need_dz else None, w_src_t, gamma, stat, dgamma, C):
-            return dW, db, dZ, None, None, None, None, dgamma, None
+            return dW, db, dZ, None, None, None, None, dgamma, None, None
         # dWt = x^T dz lands transposed in place (the pack keeps [in, out]); db = colsum(dz) for each relation: the
         # destination types' products in ONE launch pair when the grouped kernel takes them
         if not _tn_gemm_group([(dz, x, dW[lo:hi].view(R * C, C), db[lo:hi]) for lo, hi, z0, rows, R, x, dz in live_blocks]):
@@ -2406,14 +2411,15 @@ class _LayerTransform(torch.autograd.Function):
             if gamma is not None:
                 _lib.check(_lib.lib().kgw_ind_colsum(stat.data_ptr() + 8 * z0, _p(dz), dz.stride(0), rows, R, _p(dgamma[lo:hi]),
                                                      _lib.stream_ptr()), 'kgw_ind_colsum')
-        return dW, db, dZ, None, None, None, None, dgamma, None
+        return dW, db, dZ, None, None, None, None, dgamma, None, None
 
 
-def layer_transform(pack, Z, blocks, out_blocks=None, premasked=False, bias_sum=None, weight=None, gamma=None, stat=None):
+def layer_transform(pack, Z, blocks, out_blocks=None, premasked=False, bias_sum=None, weight=None, gamma=None, stat=None, relu=True):
     """``blocks`` = [(lo, hi, z0, rows)] (see _LayerTransform); ``out_blocks``: optional RowBlock per block to write
     the outputs into; ``premasked``: whoever consumes the outputs folds this node's ReLU backward into its own
     backward kernel (gat_aggregate(relu_input=True) / readout_weighted_mse(h_is_relu=True)), so no stand-alone
-    threshold launch runs here; ``bias_sum``: per-block summed bias from rel_vectors(pack, blocks)."""
+    threshold launch runs here; ``bias_sum``: per-block summed bias from rel_vectors(pack, blocks); ``relu=False``: the
+    pre-activation (a norm site: see _LayerTransform; needs ``premasked=True``)."""
     if bias_sum is None:
         key = _block_key(blocks)
         sel = pack._sel_cache.get(key)
@@ -2424,10 +2430,10 @@ def layer_transform(pack, Z, blocks, out_blocks=None, premasked=False, bias_sum=
             pack._sel_cache[key] = sel
         bias_sum = (sel.unsqueeze(2) * pack.bias.detach().unsqueeze(0)).sum(1)        # [blocks, n, 1] * [1, n, C]: no GEMM for a sum
     return _LayerTransform.apply(pack.w_src_t if weight is None else weight, pack.bias, Z, blocks, bias_sum, out_blocks, premasked,
-                                 gamma, stat)
+                                 gamma, stat, relu)
 
 
-def layer_transform_heads(pack, Z, blocks, head_mask, out_blocks=None, premasked=False):
+def layer_transform_heads(pack, Z, blocks, head_mask, out_blocks=None, premasked=False, relu=True):
     """The layer transform behind ``gat_aggregate(heads=NH)``: Z [NH, z_rows, C] holds one full-width aggregate per head and
     column c of the output takes head(c)'s:  h_d = relu(sum_r sum_h Z[h][:, r] @ (W_r^T * mask_h) + sum_r bias_r)  per destination
     type, ``head_mask`` [NH, C] being the heads' column masks.  It is ``layer_transform`` over NH x R stacked "relations" per
@@ -2455,7 +2461,7 @@ def layer_transform_heads(pack, Z, blocks, head_mask, out_blocks=None, premasked
         z0v += rows * NH * R
         lov += NH * R
     Zv = torch.cat(pieces, 0) if len(pieces) != 1 else pieces[0].contiguous()
-    return _LayerTransform.apply(Wm, bias_v, Zv, vblocks, bsum, out_blocks, premasked, None, None)
+    return _LayerTransform.apply(Wm, bias_v, Zv, vblocks, bsum, out_blocks, premasked, None, None, relu)
 
 
 def _hdrop_launch(pairs, types, layer, thresh, scale, word):
@@ -2524,6 +2530,93 @@ def hidden_dropout(outs, types, layer: int, p: float, word: torch.Tensor, out_bl
         raise _lib.KgwasHipError('this libkgwas_hip.so predates hidden-state dropout (kgw_hidden_dropout)')
     thresh, scale = dropout_params(p)
     return list(_HiddenDropout.apply(tuple(int(t) for t in types), int(layer), thresh, scale, word, out_blocks, *outs))
+
+
+LNORM_EPS = 1e-5            # KGW_LNORM_EPS (include/kgwas_hip.h): torch.nn.LayerNorm's default
+
+
+class _LayerNormReLU(torch.autograd.Function):
+    """out_t = relu(LayerNorm(y_t) * w_t + b_t) for the per-type pre-activations of one layer (kgwlnorm_* in include/kgwas_hip.h):
+    one launch forward; backward one launch for every dy and the per-block partial column sums, and one that folds them into
+    d weight / d bias [n_types, 128] in a fixed order (a launch of its own: the partial sums fit no KgwGradSrc kind).  Saves y (the
+    producer's own tensor, never written), (mean, rstd) per row and -- unless the consumer masks the gradient itself -- out."""
+
+    @staticmethod
+    def forward(ctx, types, c_logical, out_blocks, premasked, weight, bias, *ys):
+        ctx.set_materialize_grads(False)
+        L = _lib.lib()
+        xs = [_hdrop_rows(y) for y in ys]
+        stat = torch.empty(max(sum(x.shape[0] for x in xs), 1), 2, device=weight.device)
+        jobs = (_lib.KgwLNormJob * len(xs))()
+        outs, r0 = [], 0
+        for k, (j, x, t) in enumerate(zip(jobs, xs, types)):
+            ob = out_blocks[k] if out_blocks is not None else None
+            o = ob.view() if ob is not None and ob.n == x.shape[0] and ob.buf.data_ptr() % 16 == 0 else torch.empty_like(x, memory_format=torch.contiguous_format)
+            j.src, j.lds, j.dst, j.ldd, j.rows, j.type = _p(x), x.stride(0), _p(o), o.stride(0), x.shape[0], t
+            j.weight, j.bias, j.stat = _p(weight[t]), _p(bias[t]), _p(stat[r0:])
+            r0 += x.shape[0]
+            outs.append(o)
+        _lib.check(L.kgw_layer_norm_relu_fwd(len(xs), jobs, c_logical, LNORM_EPS, _lib.stream_ptr()), 'kgw_layer_norm_relu_fwd')
+        ctx.args = (types, c_logical, premasked)
+        ctx.save_for_backward(weight, stat, *xs, *([] if premasked else outs))
+        return tuple(outs)
+
+    @staticmethod
+    def backward(ctx, *gs):
+        types, c_logical, premasked = ctx.args
+        weight, stat = ctx.saved_tensors[:2]
+        n = len(types)
+        xs = ctx.saved_tensors[2:2 + n]
+        outs = ctx.saved_tensors[2 + n:] if not premasked else [None] * n
+        live = [k for k, g in enumerate(gs) if g is not None]
+        dys = [None] * n
+        if not live:
+            return (None,) * 6 + tuple(dys)
+        L = _lib.lib()
+        starts = [0]
+        for x in xs:
+            starts.append(starts[-1] + x.shape[0])
+        jobs = (_lib.KgwLNormBwdJob * len(live))()
+        keep = []
+        for j, k in zip(jobs, live):
+            g, x, o = _hdrop_rows(gs[k]), xs[k], outs[k]
+            dy = torch.empty_like(x, memory_format=torch.contiguous_format)
+            keep.append(g)
+            dys[k] = dy
+            j.g, j.ldg, j.y, j.ldy, j.dy, j.lddy = _p(g), g.stride(0), _p(x), x.stride(0), _p(dy), dy.stride(0)
+            j.out, j.ldo = (_p(o), o.stride(0)) if o is not None else (None, 0)
+            j.rows, j.type, j.weight, j.stat = x.shape[0], types[k], _p(weight[types[k]]), _p(stat[starts[k]:])
+        nf = int(L.kgw_layer_norm_partial_floats(len(live), jobs))
+        _lib.check(min(nf, 0), 'kgw_layer_norm_partial_floats')
+        partial = torch.empty(max(nf, 1), device=weight.device)
+        dw, db = torch.empty_like(weight), torch.empty_like(weight)
+        _lib.check(L.kgw_layer_norm_bwd(len(live), jobs, c_logical, _p(partial), nf, _lib.stream_ptr()), 'kgw_layer_norm_bwd')
+        _lib.check(L.kgw_layer_norm_fold(len(live), jobs, _p(partial), nf, weight.shape[0], _p(dw), _p(db), _lib.stream_ptr()),
+                   'kgw_layer_norm_fold')
+        return (None,) * 4 + (dw, db) + tuple(dys)
+
+
+def layer_norm_relu(outs, types, weight: torch.Tensor, bias: torch.Tensor, c_logical: int, out_blocks=None, premasked=False):
+    """relu(torch.nn.LayerNorm(c_logical, eps=1e-5)) per node on the hidden state between two message-passing layers: ``outs`` = the
+    per-type PRE-ACTIVATION outputs [rows_t, 128] of a layer, ``types`` = their (distinct) node type ids, ``weight`` / ``bias`` =
+    the site's packed parameters [n_types <= 8, 128], row t for node type t.  The statistics run over the first ``c_logical``
+    columns; the others come out exactly 0 (include/kgwas_hip.h).  ``out_blocks``: optional RowBlock per output to write into (the
+    next layer's input); the inputs themselves are never overwritten.  ``premasked``: whoever consumes the outputs multiplies
+    their gradient by (out > 0) itself (gat_aggregate(relu_input=True)); otherwise the backward kernel does, from the saved out.
+    One autograd node over all types: d weight / d bias come back whole -- a type whose output received no gradient, or that is
+    not in ``types``, has ZERO rows there (not ``None``).  Returns the outputs, in order."""
+    outs = list(outs)
+    if not outs:
+        return []
+    types = tuple(int(t) for t in types)
+    assert len(outs) == len(types) == len(set(types)) <= 8 and all(o.dim() == 2 and o.shape[1] == KGW_C for o in outs)
+    assert weight.shape == bias.shape and weight.dim() == 2 and weight.shape[1] == KGW_C and max(types) < weight.shape[0] <= 8
+    assert weight.is_contiguous() and bias.is_contiguous() and weight.dtype == bias.dtype == torch.float32
+    if not 1 <= int(c_logical) <= KGW_C:
+        raise ValueError(f'c_logical {c_logical}: 1 to {KGW_C} columns')
+    if not _lib.has_layer_norm():
+        raise _lib.KgwasHipError('this libkgwas_hip.so predates layer normalisation (kgw_layer_norm_relu_fwd)')
+    return list(_LayerNormReLU.apply(types, int(c_logical), out_blocks, bool(premasked), weight, bias, *outs))
 
 
 class _FoldFC(torch.autograd.Function):
