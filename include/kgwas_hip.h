@@ -485,6 +485,60 @@ int kgw_layer_norm_bwd(int32_t n_jobs, const KgwLNormBwdJob* jobs, int32_t c_log
 int kgw_layer_norm_fold(int32_t n_jobs, const KgwLNormBwdJob* jobs, const float* partial, int64_t partial_floats, int32_t n_types,
                         float* dweight, float* dbias, kgw_stream_t stream);
 
+/* Root weight: a learned self term per layer and node type, y_i += W_root[l][t] x_i with x_i node i's OWN layer-l input (PyG's
+ * SAGEConv.lin_r / RGCNConv.root / GATConv(residual=True); the reference builds GATConv(add_self_loops=False) for every relation
+ * and a SNP has no SNP-SNP relation, so its own state never enters its own update: an EXTENSION, off by default, learned and live in
+ * every mode).  For one destination row of 128 stored columns, W [128][128] in nn.Linear layout [out][in], bias-free:
+ *      dst_n = act(y_n + sum_k x_k W[n][k])                 act = max(0, .) iff relu          (kgwroot_out)
+ * with y the relation combine's pre-activation (the transform run with relu = 0).  Backward, g the upstream gradient:
+ *      gm_n = out ? (out_n > 0 ? g_n : 0) : g_n             (out == NULL: g arrives masked, or no ReLU was applied)
+ *      dx_k = sum_n gm_n W[n][k]                            times (x_k > 0) iff x_premasked    (kgwroot_mask)
+ *      d y  = gm                                            (written to ``gm`` when the kernel had to mask: the transform behind it is
+ *                                                            premasked and takes gm as its dY)
+ *      dW[n][k] = sum_rows gm_n x_k                         by kgw_tn_gemm_multi, not here.
+ * x_premasked: x is a ReLU output (possibly dropped) whose producer runs premasked -- the consumer of that state multiplies the
+ * gradient by (x > 0) itself, as kgw_gat_aggregate_bwd does with KGW_F_RELU_INPUT for the same rows -- so the kernel does too.
+ * Columns of a narrower model: with the pad columns of x, y and the pad rows / columns of W zero, the pad columns of dst and dx
+ * are exactly 0.0f.
+ *
+ * kgw_root_linear_fwd / kgw_root_linear_bwd: one launch for up to 8 jobs (the destination types of one layer).  fp32 arithmetic on
+ * the fp32 MFMA pipe (v_mfma_f32_32x32x2_f32, as kgw_linear).  A job owns a range of the grid's blocks -- ceil(tiles / P) of them,
+ * 32-row tiles, P = 2 doubled until the grid has at most 2048 blocks; a block stages its job's 128 x 128 weights in LDS once, every
+ * wavefront keeps its half (64 output columns) in registers and walks the job's row tiles.  Every output element is one
+ * wavefront's sum in ascending k: no atomics, no partial sums, the bits do not depend on the grid.
+ * Refused before any launch: a NULL jobs, a NULL x / y / dst / W (fwd) or g / dx / W, or x with x_premasked (bwd) of a job with
+ * rows > 0 (``out`` and ``gm`` may be NULL; gm == NULL with out != NULL: the masked gradient is not written): KGW_E_NULL;  n_jobs
+ * outside [1, 8], rows < 0 or > 2^25, a leading dimension < 128 with rows > 1, a type outside [0, 8) or given twice: KGW_E_RANGE;
+ * a pointer not 16-byte aligned, a leading dimension % 4 != 0, an output that is one of the call's inputs or its other output
+ * (dst == y, dst == x;  dx or gm == g, out or -- with x_premasked -- x;  gm == dx): KGW_E_UNSUPPORTED.  Beyond these equalities
+ * the caller owes the kernels outputs that overlap NO input and no other output, of this job or another of the launch: a tile's two
+ * column halves read whole rows of x / g / out while the other half stores, and partial overlaps are not looked for.  Jobs without
+ * rows are skipped; no rows at all: KGW_OK without a launch. */
+KGWFAN_INLINE float kgwroot_out(float y, float xw, int relu) { const float v = y + xw; return (relu && !(v > 0.0f)) ? 0.0f : v; }
+KGWFAN_INLINE float kgwroot_mask(float g, float by) { return by > 0.0f ? g : 0.0f; }
+typedef struct KgwRootJob {
+    const float* x; int64_t ldx;      /* the destination rows' own layer input: rows of 128 floats                                 */
+    const float* y; int64_t ldy;      /* the pre-activation of the relation combine                                                */
+    float* dst; int64_t ldd;
+    int32_t rows;
+    int32_t type;                     /* node type id (names the job; W already points at its slice)                               */
+    const float* W;                   /* [128][128], [out][in]                                                                     */
+} KgwRootJob;
+typedef struct KgwRootBwdJob {
+    const float* g; int64_t ldg;      /* upstream gradient                                                                         */
+    const float* out; int64_t ldo;    /* the forward's dst, to mask g by (out > 0); NULL: g is used as it is                       */
+    const float* x; int64_t ldx;      /* the forward's x: read only with x_premasked                                               */
+    float* gm; int64_t ldgm;          /* the masked gradient (written only when out != NULL), or NULL                              */
+    float* dx; int64_t lddx;
+    int32_t rows;
+    int32_t type;
+    const float* W;
+    int32_t x_premasked;              /* dx *= (x > 0)                                                                             */
+    int32_t reserved;
+} KgwRootBwdJob;
+int kgw_root_linear_fwd(int32_t n_jobs, const KgwRootJob* jobs, int32_t relu, kgw_stream_t stream);
+int kgw_root_linear_bwd(int32_t n_jobs, const KgwRootBwdJob* jobs, kgw_stream_t stream);
+
 /* Sigmoid-gated attention (KGW_F_SIGMOID_GATE): alpha = sigmoid(leaky_relu(a_j + a_i) / T) instead of the softmax over the row
  * (kgwas/conv.py:49,219-220, the reference GATConv's sigmoid_gat; its HeteroGNN never passes it, so like the dropout this is an
  * EXTENSION, off by default).  The gates are independent per edge and are not normalised by the row's degree.  With

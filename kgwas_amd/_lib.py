@@ -174,6 +174,17 @@ class KgwLNormBwdJob(C.Structure):
                 ('stat', C.c_void_p)]
 
 
+class KgwRootJob(C.Structure):
+    _fields_ = [('x', C.c_void_p), ('ldx', C.c_int64), ('y', C.c_void_p), ('ldy', C.c_int64), ('dst', C.c_void_p), ('ldd', C.c_int64),
+                ('rows', C.c_int32), ('type', C.c_int32), ('W', C.c_void_p)]
+
+
+class KgwRootBwdJob(C.Structure):
+    _fields_ = [('g', C.c_void_p), ('ldg', C.c_int64), ('out', C.c_void_p), ('ldo', C.c_int64), ('x', C.c_void_p), ('ldx', C.c_int64),
+                ('gm', C.c_void_p), ('ldgm', C.c_int64), ('dx', C.c_void_p), ('lddx', C.c_int64), ('rows', C.c_int32),
+                ('type', C.c_int32), ('W', C.c_void_p), ('x_premasked', C.c_int32), ('reserved', C.c_int32)]
+
+
 class KgwFoldArgs(C.Structure):
     _fields_ = [('n', C.c_int32), ('n_rels', C.c_int32), ('n_mlp', C.c_int32), ('duv_pieces', C.c_int32),
                 ('rel_ids_host', C.c_void_p), ('src_mlp_host', C.c_void_p), ('dst_mlp_host', C.c_void_p),
@@ -193,7 +204,8 @@ EXPORTS = ['kgw_version', 'kgw_status_string', 'kgw_struct_sizes', 'kgw_sample_b
            'kgw_linear', 'kgw_mlp2_fwd', 'kgw_mlp2w_fwd', 'kgw_mlp2_bwd_first', 'kgw_mlp2_bwd_first_workspace_floats', 'kgw_gemm3', 'kgw_gemm3_riders', 'kgw_gemm3_rider_blocks', 'kgw_gemm3_pack', 'kgw_gemm3_packed_bytes', 'kgw_gemm3_workspace_floats', 'kgw_adam', 'kgw_adam_notick', 'kgw_relvec_fwd', 'kgw_relvec_bwd', 'kgw_relvec_bwd_acc', 'kgw_relvec_fwd_multi', 'kgw_relvec_bwd_multi', 'kgw_wmse_fwd', 'kgw_wmse_bwd', 'kgw_readout_wmse_fwd', 'kgw_readout_wmse_bwd', 'kgw_readout_wmse_train', 'kgw_readout_wmse_train_parts', 'kgw_readout_train_fold', 'kgw_readout_mt_pred', 'kgw_readout_mt_pred_bwd', 'kgw_readout_wmse_mt_fwd', 'kgw_readout_wmse_mt_bwd',
            'kgw_readout_wmse_mt_train', 'kgw_readout_wmse_mtw_fwd', 'kgw_readout_wmse_mtw_bwd', 'kgw_readout_wmse_mtw_train',
            'kgw_accumulate_stats', 'kgw_accumulate_stats_tick', 'kgw_hidden_dropout',
-           'kgw_layer_norm_relu_fwd', 'kgw_layer_norm_partial_floats', 'kgw_layer_norm_bwd', 'kgw_layer_norm_fold']
+           'kgw_layer_norm_relu_fwd', 'kgw_layer_norm_partial_floats', 'kgw_layer_norm_bwd', 'kgw_layer_norm_fold',
+           'kgw_root_linear_fwd', 'kgw_root_linear_bwd']
 
 _lib = None
 
@@ -365,6 +377,9 @@ def lib():
         L.kgw_layer_norm_bwd.argtypes = [C.c_int32, C.POINTER(KgwLNormBwdJob), C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]
         L.kgw_layer_norm_fold.argtypes = [C.c_int32, C.POINTER(KgwLNormBwdJob), C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p,
                                           C.c_void_p]
+    if hasattr(L, 'kgw_root_linear_fwd'):           # (absent likewise)
+        L.kgw_root_linear_fwd.argtypes = [C.c_int32, C.POINTER(KgwRootJob), C.c_int32, C.c_void_p]
+        L.kgw_root_linear_bwd.argtypes = [C.c_int32, C.POINTER(KgwRootBwdJob), C.c_void_p]
     L.kgw_accumulate_stats.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
     L.kgw_accumulate_stats_tick.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     _lib = L
@@ -411,6 +426,12 @@ def has_layer_norm() -> bool:
     """Does the loaded library have the layer-normalisation kernels (kgw_layer_norm_relu_fwd / _bwd / _fold)?  An older library
     named by KGW_LIB_PATH for an A/B run lacks the symbols."""
     return hasattr(lib(), 'kgw_layer_norm_relu_fwd')
+
+
+def has_root_weight() -> bool:
+    """Does the loaded library have the root-weight kernels (kgw_root_linear_fwd / _bwd)?  An older library named by KGW_LIB_PATH
+    for an A/B run lacks the symbols."""
+    return hasattr(lib(), 'kgw_root_linear_fwd')
 
 
 KGW_ORDER_SEEDS, KGW_ORDER_BATCHES = 1, 2     # kgw_epoch_order's modes (include/kgwas_hip.h)

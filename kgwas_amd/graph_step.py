@@ -246,6 +246,10 @@ class GraphTrainStep:
         A model with ``gnn_norm`` (``self.layer_norm``) needs nothing from the trainer: its three launches per site are captured with
         the rest, their row statistics and partial column sums are allocations of the capture (static for the captured capacities),
         and its parameters take their place in the optimiser's tables -- 2 (L - 1) more tensors, the fused launch while they fit.
+        A model with ``gnn_root_weight`` (``self.root_weight``) likewise: its forward and backward launch per layer and the
+        weight-gradient products (which finish their own sums: ops._root_weight_grad) are captured with the rest, their temporaries
+        are allocations of the capture, and the L packed tensors join the optimiser's tables -- the fused launch while they fit,
+        else the fallback below decides.  Its layer 1 runs unfolded (``model.fold_fc`` is False).
         ``epoch_order`` ('fixed' | 'seeds' | 'batches', NeighborLoader): the order in which an epoch visits the seeds, a pure function
         of (``sample_seed``, epoch) written on the device once per epoch (kgw_epoch_order); ``step(i)`` trains on batch i of the epoch
         ``set_epoch`` named, and a step past the last batch moves on to the next epoch by itself.  'seeds': the batches of every
@@ -292,6 +296,7 @@ class GraphTrainStep:
         self.hidden_dropout = float(getattr(self.model, 'gnn_dropout', 0.0)) > 0.0
         self._drops = self.dropout or self.hidden_dropout
         self.layer_norm = getattr(self.model, 'gnn_norm', None) is not None
+        self.root_weight = bool(getattr(self.model, 'gnn_root_weight', False))
         self._drop_words = {}
         self.ld_w = run._ld_weight_vector()             # ([N] or, per-trait weights, [N, T]: resident, read in place by the graph)
         self.world = 1

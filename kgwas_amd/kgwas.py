@@ -50,7 +50,7 @@ class KGWAS:
 
     def initialize_model(self, gnn_num_layers=2, gnn_hidden_dim=128, gnn_backbone='GAT', gnn_aggr='sum',
                          gat_num_head=1, no_relu=False, out_channels=1, gat_dropout=0.0, gat_sigmoid=False, gat_temperature=1.0,
-                         gat_edge_dim=None, gnn_dropout=0.0, gnn_norm=None):
+                         gat_edge_dim=None, gnn_dropout=0.0, gnn_norm=None, gnn_root_weight=False):
         """``out_channels`` (extra, default 1 = the reference, kgwas.py:52): T > 1 reads ONE shared trunk out into T label columns
         (``data['SNP'].y`` [N, T], KGWAS_Data.from_synthetic(n_traits=T)) -- a shared-trunk multi-task model, not T independent
         models.  It enters ``config`` only when it is not 1, so the config.pkl of a single-trait run is what it always was.
@@ -71,7 +71,14 @@ class KGWAS:
         ``gnn_norm`` = 'layer' (extra, default None = the reference's model, launch for launch and bit for bit): a learned LayerNorm
         per node type on the output of every message-passing layer but the last, before its ReLU (HeteroGNN; needs
         gnn_num_layers >= 2), in training, evaluation and the attention queries alike; every backbone and switch takes it,
-        parallelism='shard' does not.  It enters ``config`` only when it is set."""
+        parallelism='shard' does not.  It enters ``config`` only when it is set.
+        ``gnn_root_weight`` = True (extra, default False = the reference's model, launch for launch and bit for bit): a learned
+        bias-free Linear per layer and node type on every destination node's OWN layer input, added to the relation sum / mean /
+        min / max before the norm and the ReLU (HeteroGNN) -- the self term the reference's GATConv(add_self_loops=False) relations
+        leave out -- in training, evaluation and the attention queries alike; GAT with every switch takes it, gnn_backbone='SAGE'
+        (whose lin_r already is one) and parallelism='shard' do not.  It enters ``config`` only when it is True."""
+        if gnn_root_weight and gnn_backbone == 'SAGE':
+            raise ValueError("gnn_root_weight needs gnn_backbone='GAT': SAGE's lin_r already is a root weight per relation")
         if gnn_norm not in (None, 'layer'):
             raise ValueError(f"gnn_norm {gnn_norm!r}: None or 'layer'")
         if gnn_norm is not None and int(gnn_num_layers) < 2:
@@ -98,12 +105,15 @@ class KGWAS:
             self.config['gnn_dropout'] = gnn_dropout
         if gnn_norm is not None:
             self.config['gnn_norm'] = gnn_norm
+        if gnn_root_weight:
+            self.config['gnn_root_weight'] = True
         self.gnn_num_layers = gnn_num_layers
         self.model = HeteroGNN(self.data.data, gnn_hidden_dim, out_channels, gnn_num_layers, gnn_backbone, gnn_aggr,
                                self.data.snp_init_dim_size, self.data.gene_init_dim_size,
                                self.data.go_init_dim_size, gat_num_head, no_relu=no_relu, gat_dropout=gat_dropout,
                                gat_split_heads=True, gat_sigmoid=gat_sigmoid, gat_temperature=gat_temperature,
-                               gat_edge_dim=gat_edge_dim, gnn_dropout=gnn_dropout, gnn_norm=gnn_norm).to(self.device)
+                               gat_edge_dim=gat_edge_dim, gnn_dropout=gnn_dropout, gnn_norm=gnn_norm,
+                               gnn_root_weight=bool(gnn_root_weight)).to(self.device)
 
     def load_pretrained(self, path):
         import pandas as pd
@@ -192,6 +202,9 @@ class KGWAS:
         if getattr(self.model, 'gnn_norm', None) is not None:
             raise NotImplementedError("gnn_norm is not available with parallelism='shard': the sharded step does not run the "
                                       "layer-normalisation launches; use parallelism='seed'")
+        if getattr(self.model, 'gnn_root_weight', False):
+            raise NotImplementedError("gnn_root_weight is not available with parallelism='shard': the sharded step does not run the "
+                                      "root-weight launches; use parallelism='seed'")
         if getattr(self.model, 'gat_sigmoid', False) or getattr(self.model, 'temperature', 1.0) != 1.0:
             raise NotImplementedError("gat_sigmoid / gat_temperature are not available with parallelism='shard': the exchange of "
                                       "partial softmax states is built for the softmax at T = 1; use parallelism='seed'")

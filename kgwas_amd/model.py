@@ -314,12 +314,30 @@ class HeteroGNN(nn.Module):
     type that has no rows in a batch's layer gets ZERO gradient rows, where one torch module per type would leave ``grad`` None:
     with weight decay such a row still decays.  The FC_output fold, the parameter riders and the fused optimiser launch stay (the
     norm sits after the layer-1 transform).  Needs ``num_layers >= 2``; ``None`` (the default) is the model as ever, launch for
-    launch and bit for bit."""
+    launch and bit for bit.
+    ``gnn_root_weight`` = True (an extension, keyword only: PyG's SAGEConv.lin_r, RGCNConv.root, GATConv(residual=True); the
+    reference builds GATConv(add_self_loops=False) for every relation and a SNP has no SNP-SNP relation, so a node's own state
+    never enters its own update): for every layer l = 1 .. L and every node type t that is the destination of a relation the
+    pre-activation of destination node i becomes  y_i = combine_r(conv_r(...)_i) + W_root[l][t] x_i  with x_i the node's OWN layer-l
+    input -- at layer 1 its feature MLP's output, later the state the previous layer left (after its norm, ReLU and, in training,
+    hidden dropout: what the relations of layer l read for that node as a source).  The 1 / R of 'mean' scales the relation part
+    only, 'min' / 'max' add the root term after the reduction; everything after y (norm, ReLU, dropout, read-out) is as it was.  One
+    forward and one backward launch per layer (ops.root_linear, kgwroot_* in include/kgwas_hip.h) plus the weight-gradient products;
+    learned and live in evaluation, the attention queries and the export.  The destination rows of a type are the leading
+    ``lay_rows[l - 1][t]`` rows of that type's layer input (the sampler's layout: seeds, then hop 1, ...; the SAGE root term and the
+    read-out rely on the same).  Parameters: ONE packed tensor per layer ``root_weight[l - 1]`` [n_node_types, 128, 128], slice t
+    a bias-free nn.Linear [out, in] for node type t (glorot, as lin_src), the padding and the slices of types that receive no
+    relation zero and kept zero; drawn AFTER every other parameter, so the other parameters are those of a default model at the
+    same seed; under the names ``roots.<l - 1>.<node type>.weight`` at the model's own width.  A type without rows in a batch's
+    layer gets a ZERO gradient slice (the ``gnn_norm`` convention).  Layer 1 runs UNFOLDED (``fold_fc`` False, as a gated model's):
+    FC_output would get gradient from the fold and from the root product, which the one-source-per-tensor records of the fused
+    optimiser launch do not take.  GAT only (SAGE's lin_r IS a root weight per relation: ValueError); ``False`` (the default) is
+    the model as ever, launch for launch and bit for bit."""
 
     def __init__(self, pyg_data, hidden_channels, out_channels, num_layers, gnn_backbone, gnn_aggr,
                  snp_init_dim_size, gene_init_dim_size, go_init_dim_size, gat_num_head, no_relu=False, gat_dropout=0.0,
                  gat_split_heads=False, *, gat_sigmoid=False, gat_temperature=1.0, gat_edge_dim=None, gnn_dropout=0.0,
-                 gnn_norm=None):
+                 gnn_norm=None, gnn_root_weight=False):
         super().__init__()
         if gnn_backbone not in ('GAT', 'SAGE'):
             raise NotImplementedError(f"backbone {gnn_backbone!r}: 'GAT' (the reference default, kgwas.py:52) and 'SAGE' "
@@ -346,6 +364,9 @@ class HeteroGNN(nn.Module):
             raise ValueError(f'gnn_norm with num_layers = {num_layers}: the hidden state is normalised BETWEEN message-passing '
                              'layers, and one layer has no such site')
         self.gnn_norm = gnn_norm
+        self.gnn_root_weight = bool(gnn_root_weight)
+        if self.gnn_root_weight and gnn_backbone == 'SAGE':
+            raise ValueError("gnn_root_weight needs gnn_backbone='GAT': SAGE's lin_r already is a root weight per relation")
         # the 64-bit word of the step's masks (attention and hidden-state dropout alike: the rules keep them apart), resident on
         # the device: the kernels read it when they run, so a captured step replays with whatever the trainer copied here
         # (set_dropout_word / GraphTrainStep).  Not part of the state_dict.
@@ -513,6 +534,20 @@ class HeteroGNN(nn.Module):
         # dead packs never receive gradients; keep them out of autograd entirely
         for p in self.dead_packs.parameters():
             p.requires_grad_(False)
+        # root weight: one packed tensor per layer, slice t = node type t's bias-free Linear [out, in]; none without gnn_root_weight,
+        # and drawn LAST, so the default model's parameters -- and a root model's other parameters -- are what they were
+        self.root_types = [t for t in range(sc.NT) if sc.rels_by_dst[t]] if self.gnn_root_weight else []
+        self.root_weight = nn.ParameterList()
+        if self.gnn_root_weight:
+            # FC_output would get gradient from the fold AND from the root product of layer 1's destination rows; the fused
+            # optimiser's records hold one source per tensor: layer 1 runs unfolded (OPEN)
+            self.fold_fc = False
+            a_w = math.sqrt(6.0 / (cl + cl))                  # glorot on [C_out, C_in]: RelationPack's rule for lin_src
+            for _ in range(num_layers):
+                w = torch.zeros(sc.NT, hidden_channels, hidden_channels)
+                for t in self.root_types:
+                    _uniform_(w[t, :cl, :cl], a_w)
+                self.root_weight.append(nn.Parameter(w))
 
     # ------------------------------------------------------------------------------------------
     def _mlp_for(self, t: str) -> SimpleMLP:
@@ -800,14 +835,20 @@ class HeteroGNN(nn.Module):
             hbuf, nxt = self._layer_input(batch, l + 1) if l < self.num_layers else (None, {})
             drops = hdrop is not None and l < self.num_layers
             site = self._norm_site(l)
-            # (a layer whose output is normalised or dropped leaves the next layer's blocks to the LAST of those launches: see
-            #  _fused_layers)
-            later = drops or site is not None
+            root = self._root_site(l)
+            # (a layer whose output gets a root term, is normalised or dropped leaves the next layer's blocks to the LAST of those
+            #  launches: see _fused_layers)
+            later = drops or site is not None or root is not None
             outs = ops.layer_transform_heads(P, Z, blocks, self.head_mask, None if later else [nxt.get(sc.node_types[t]) for t in tys],
-                                             premasked=(l < self.num_layers) or last_premasked, relu=site is None)
+                                             premasked=(l < self.num_layers) or last_premasked or root is not None,
+                                             relu=site is None and root is None)
             if self.aggr == 'mean':
                 hbuf = None if not later else hbuf
                 outs = [o * (1.0 / (hi - lo)) for o, (lo, hi, _, _) in zip(outs, blocks)]
+            if root is not None:        # (the root Linear is full width, as PyG's ``res`` is H * C wide)
+                outs = ops.root_linear(outs, tys, self._root_inputs(h, tys, [b[3] for b in blocks]), root,
+                                       None if (drops or site is not None) else [nxt.get(sc.node_types[t]) for t in tys],
+                                       premasked=(l < self.num_layers) or last_premasked, relu=site is None, x_premasked=l > 1)
             if site is not None:
                 outs = ops.layer_norm_relu(outs, tys, site[0], site[1], self.hidden_logical,
                                            None if drops else [nxt.get(sc.node_types[t]) for t in tys], premasked=True)
@@ -854,6 +895,33 @@ class HeteroGNN(nn.Module):
         """(weight, bias) [n_node_types, 128] of the normalisation after layer l, or None: a model without ``gnn_norm``, or the
         last layer.  In every mode: the norm is part of the function the model computes, not of its training."""
         return (self.norm_weight[l - 1], self.norm_bias[l - 1]) if self.gnn_norm is not None and l < self.num_layers else None
+
+    def _root_site(self, l: int):
+        """The packed root weights [n_node_types, 128, 128] of layer l, or None for a model without ``gnn_root_weight``.  In every
+        mode: the root term is part of the function the model computes."""
+        return self.root_weight[l - 1] if self.gnn_root_weight else None
+
+    def _root_inputs(self, h: Dict[str, torch.Tensor], tys, rows):
+        """The destination rows' own layer input: the leading ``rows`` rows of each type's state (the sampler's layout)."""
+        xs = []
+        for t, n in zip(tys, rows):
+            name = self.schema.node_types[t]
+            if name not in h or h[name].shape[0] < n:
+                raise RuntimeError(f'root weight: node type {name!r} has {n} destination rows but no layer input of its own for them')
+            xs.append(h[name] if h[name].shape[0] == n else h[name][:n])
+        return xs
+
+    def _add_root(self, l: int, h: Dict[str, torch.Tensor], pre: Dict[str, torch.Tensor]):
+        """``pre`` + W_root x on per-type PRE-ACTIVATIONS that are framework tensors (the relation min / max, the all-relations
+        routes), ahead of ``_activate``: one launch, no ReLU in it, and x an ordinary autograd tensor (not premasked)."""
+        root = self._root_site(l)
+        if root is None or not pre:
+            return pre
+        names = list(pre)
+        tys = [self.schema.type_id[n] for n in names]
+        ys = [pre[n] for n in names]
+        outs = ops.root_linear(ys, tys, self._root_inputs(h, tys, [y.shape[0] for y in ys]), root, relu=False)
+        return dict(zip(names, outs))
 
     def _activate(self, l: int, pre: Dict[str, torch.Tensor], relu: bool = True):
         """The activation of layer l on per-type PRE-ACTIVATIONS that are framework tensors (SAGE, the relation min / max, the
@@ -930,7 +998,8 @@ class HeteroGNN(nn.Module):
                         ops.LIBRARY_GEMM.note('gat min/max per-relation outputs', R, rows, C)
                         o = torch.baddbmm(P.bias[lo:hi].unsqueeze(1), zr, Wv[lo:hi])
                     outs.append(self._combine_relations(o))
-                h = self._drop_hidden(l, self._activate(l, {sc.node_types[t]: o for t, o in zip(tys, outs)}), hdrop)
+                pre = self._add_root(l, h, {sc.node_types[t]: o for t, o in zip(tys, outs)})
+                h = self._drop_hidden(l, self._activate(l, pre), hdrop)
                 continue
             # per-relation linear maps + bias + relation sum + ReLU: one GEMM per destination type, one autograd node
             hbuf, nxt = self._layer_input(batch, l + 1) if l < self.num_layers else (None, {})
@@ -942,16 +1011,24 @@ class HeteroGNN(nn.Module):
             # left: premasked), the norm's launch applies LN and the ReLU and writes the next layer's blocks (or, with dropout
             # behind it, a temporary).  The next aggregate folds dH *= (H > 0) with H the norm's output: premasked for the norm too.
             site = self._norm_site(l)
-            later = drops or site is not None
+            # root weight: the transform stops at the pre-activation as at a norm site; the root launch adds W_root x of the
+            # destination rows' own layer input and applies the ReLU (or leaves it to the norm), writing the next layer's blocks when
+            # it is the site's last launch.  From layer 2 on x is a ReLU output whose producer runs premasked: x_premasked.
+            root = self._root_site(l)
+            later = drops or site is not None or root is not None
             outs = ops.layer_transform(P, Z, blocks, None if later else [nxt.get(sc.node_types[t]) for t in tys],
-                                       premasked=(l < self.num_layers) or last_premasked, bias_sum=bsum,
+                                       premasked=(l < self.num_layers) or last_premasked or root is not None, bias_sum=bsum,
                                        weight=Wp if Wp is not None else Wv, gamma=gam, stat=stat if gam is not None else None,
-                                       relu=site is None)
+                                       relu=site is None and root is None)
             if self.aggr == 'mean':
                 # mean over the relations of a destination type = the sum scaled by 1/R; relu(s/R) = relu(s)/R, and the
                 # positive scale commutes with the folded ReLU masks.  At a norm site the scale goes in BEFORE the norm: LN(y / R)
                 hbuf = None if not later else hbuf
                 outs = [o * (1.0 / (hi - lo)) for o, (lo, hi, _, _) in zip(outs, blocks)]
+            if root is not None:
+                outs = ops.root_linear(outs, tys, self._root_inputs(h, tys, [b[3] for b in blocks]), root,
+                                       None if (drops or site is not None) else [nxt.get(sc.node_types[t]) for t in tys],
+                                       premasked=(l < self.num_layers) or last_premasked, relu=site is None, x_premasked=l > 1)
             if site is not None:
                 outs = ops.layer_norm_relu(outs, tys, site[0], site[1], self.hidden_logical,
                                            None if drops else [nxt.get(sc.node_types[t]) for t in tys], premasked=True)
@@ -1091,7 +1168,7 @@ class HeteroGNN(nn.Module):
                     ws.append(pack.w_src_t[i])
                     bs = bs + pack.bias[i]
                 h_next[name] = ops.linear(x, torch.cat(ws, 0), bs, w_kn=True)
-            h = self._activate(l, h_next, relu=not raw)                      # model.py:75 / no ReLU at utils.py:460
+            h = self._activate(l, self._add_root(l, h, h_next), relu=not raw)        # model.py:75 / no ReLU at utils.py:460
 
         return h, per_layer
 
@@ -1230,6 +1307,16 @@ class HeteroGNN(nn.Module):
                     v = p.grad if grad else (p if keep_vars else p.detach())
                     yield f'norms.{l}.{self.node_types[t]}.{f}', None if v is None else v[t, :cl]
 
+    def _root_items(self, grad: bool = False, keep_vars: bool = False):
+        """(``roots.<l>.<node type>.weight``, the type's slice of layer l + 1's packed root weights at the model's own width) --
+        nothing for a model without ``gnn_root_weight``.  ``grad``: slices of the packed gradient; a type without rows in the batch
+        has a ZERO slice there (ops.root_linear), not None."""
+        cl = self.hidden_logical
+        for l, w in enumerate(self.root_weight):
+            for t in self.root_types:
+                v = w.grad if grad else (w if keep_vars else w.detach())
+                yield f'roots.{l}.{self.node_types[t]}.weight', None if v is None else v[t, :cl, :cl]
+
     def named_reference_tensors(self, grad: bool = False) -> "OrderedDict[str, Optional[torch.Tensor]]":
         """Parameters (or their gradients) under the reference's names.  Lazy lin_dst of same-type relations
         is omitted; structurally dead relations have gradient None."""
@@ -1242,6 +1329,8 @@ class HeteroGNN(nn.Module):
             out[k] = t
         for k, t in self._norm_items(grad):
             out[k] = t
+        for k, t in self._root_items(grad):
+            out[k] = t
         return out
 
     def state_dict(self, *args, destination=None, prefix='', keep_vars=False):
@@ -1251,6 +1340,8 @@ class HeteroGNN(nn.Module):
         for k, t in self._dense_items(keep_vars=keep_vars):
             out[prefix + k] = t
         for k, t in self._norm_items(keep_vars=keep_vars):
+            out[prefix + k] = t.clone()
+        for k, t in self._root_items(keep_vars=keep_vars):
             out[prefix + k] = t.clone()
         return out
 
@@ -1276,16 +1367,16 @@ class HeteroGNN(nn.Module):
         missing = [k for k, (l, r, f) in want.items() if k not in seen and
                    not (f == 'lin_dst.weight' and self.edge_types[r][0] == self.edge_types[r][2])]
         unexpected = []
-        known = ('snp_feat_mlp.', 'go_feat_mlp.', 'gene_feat_mlp.', 'lin.', 'norms.')
+        known = ('snp_feat_mlp.', 'go_feat_mlp.', 'gene_feat_mlp.', 'lin.', 'norms.', 'roots.')
         with torch.no_grad():
-            for k, dst in list(self._dense_items()) + list(self._norm_items()):     # (views of the padded storage at the model's own width)
+            for k, dst in list(self._dense_items()) + list(self._norm_items()) + list(self._root_items()):     # (views of the padded storage at the model's own width)
                 if k in rest:
                     if tuple(rest[k].shape) != tuple(dst.shape):
                         raise RuntimeError(f'load_state_dict: {k} has shape {tuple(rest[k].shape)}, the model expects {tuple(dst.shape)}')
                     dst.copy_(rest[k])
                 else:
                     missing.append(k)
-        have = {k for k, _ in self._dense_items()} | {k for k, _ in self._norm_items()}
+        have = {k for k, _ in self._dense_items()} | {k for k, _ in self._norm_items()} | {k for k, _ in self._root_items()}
         unexpected += [k for k in rest if k.startswith(known) and k not in have]
         unexpected += [k for k in rest if not k.startswith(known)]
         if strict and (missing or unexpected):

@@ -474,13 +474,18 @@ class _GatAggregate(torch.autograd.Function):
         # Z, stat and the backward's d a_dst all start from zero (rows without edges are never visited): one fill
         zr = max(z_rows, 1)
         if zbuf is None:
-            zbuf = torch.zeros(zr * (KGW_C + 3), device=dev)
+            # (e_edge rides in the same fill: the kernel writes the edges of the relations the layer computes and no others -- the
+            #  last layer of a full block leaves half of them alone -- and a caller that reads e_edge[:n_edges] then sees zeros
+            #  there, not whatever the allocator's block held; no launch is added)
+            e0 = (zr * (KGW_C + 3) + 3) & ~3
+            zbuf = torch.zeros(e0 + max(n_edges, 1), device=dev)
+            e_edge = zbuf[e0:]
         else:                                       # cleared by the caller (rel_vectors did it in its launch)
             assert zbuf.dtype == torch.float32 and zbuf.is_contiguous() and zbuf.numel() >= zr * (KGW_C + 3)
+            e_edge = torch.empty(max(n_edges, 1), device=dev)
         Z = zbuf[:zr * KGW_C].view(zr, KGW_C)
         stat = zbuf[zr * KGW_C:zr * (KGW_C + 2)].view(zr, 2)
         ctx.da_dst = zbuf[zr * (KGW_C + 2):zr * (KGW_C + 3)]
-        e_edge = torch.empty(max(n_edges, 1), device=dev)
         any_multi = batch.static or any(int(m.multi_cnt[h]) for h in range(dg.n_hops))
         part = torch.empty(max(n_chunks, 1) * PART_STRIDE if any_multi else 4, device=dev)
         a = _layer_args(batch, layer, neg_slope, inv_temp)
@@ -621,11 +626,13 @@ class _GatAggregateHeads(torch.autograd.Function):
         dev = H.device
         # Z, stat and the backward's d a_dst all start from zero (rows without edges are never visited): one fill, planes of
         # exactly z_rows rows (the stride the kernels take from the layout)
-        zbuf = torch.zeros(max(NH * z_rows * (KGW_C + 3), 1), device=dev)
+        # (e_edge rides in the same fill, as in _GatAggregate: the edges of relations the layer skips are never written)
+        e0 = (max(NH * z_rows * (KGW_C + 3), 1) + 3) & ~3
+        zbuf = torch.zeros(e0 + NH * n_edges, device=dev)
         Z = zbuf[:NH * z_rows * KGW_C].view(NH, z_rows, KGW_C)
         stat = zbuf[NH * z_rows * KGW_C:NH * z_rows * (KGW_C + 2)].view(NH, z_rows, 2)
         ctx.da_dst = zbuf[NH * z_rows * (KGW_C + 2):NH * z_rows * (KGW_C + 3)]
-        e_edge = torch.empty(NH, n_edges, device=dev)
+        e_edge = zbuf[e0:].view(NH, n_edges)
         any_multi = batch.static or any(int(m.multi_cnt[h]) for h in range(dg.n_hops))
         part = torch.empty(max(NH * n_chunks * PART_STRIDE if any_multi else 4, 4), device=dev)
         a = _layer_args(batch, layer, neg_slope, inv_temp)
@@ -2617,6 +2624,110 @@ def layer_norm_relu(outs, types, weight: torch.Tensor, bias: torch.Tensor, c_log
     if not _lib.has_layer_norm():
         raise _lib.KgwasHipError('this libkgwas_hip.so predates layer normalisation (kgw_layer_norm_relu_fwd)')
     return list(_LayerNormReLU.apply(types, int(c_logical), out_blocks, bool(premasked), weight, bias, *outs))
+
+
+def _root_weight_grad(pairs, weight):
+    """d W_root [n_types, 128, 128] of one site: slice t = gm_t^T x_t for ``pairs`` = [(t, gm, x)], zero for every other type -- the
+    products as kgw_tn_gemm_multi jobs, four per call, each writing its own slice.  They FINISH their sums (both launches of the
+    pair): the packed tensor has one slice per destination type and so up to eight producers, which the one-source-per-tensor
+    records of the fused optimiser launch (KgwGradSrc) do not describe; the optimiser reads the finished gradient."""
+    dW = torch.zeros_like(weight)
+    live = [(t, g, x) for t, g, x in pairs if x.shape[0] > 0]
+    L = _lib.lib()
+    for i in range(0, len(live), 4):
+        chunk = live[i:i + 4]
+        jobs = (_lib.KgwTnJob * len(chunk))()
+        keep = []
+        for j, (t, g, x) in zip(jobs, chunk):
+            rows = x.shape[0]
+            nws = int(L.kgw_tn_gemm_workspace_floats(rows, KGW_C, KGW_C))
+            ws = torch.empty(nws, device=x.device)
+            keep.append(ws)
+            out = dW[t]
+            j.A, j.lda, j.B, j.ldb, j.rows = _p(g), g.stride(0), _p(x), x.stride(0), rows
+            j.C, j.ldc, j.colsum_a, j.colsum_ld = _p(out), KGW_C, None, KGW_C
+            j.workspace, j.workspace_floats, j.rows_dev = _p(ws), nws, None
+            j.M, j.N, j.c_transposed, j.colsum_repeat = KGW_C, KGW_C, 0, 1
+        _lib.check(L.kgw_tn_gemm_multi(len(chunk), jobs, _lib.stream_ptr()), 'kgw_tn_gemm_multi')
+    return dW
+
+
+class _RootLinear(torch.autograd.Function):
+    """dst_t = act(y_t + x_t W_t^T) for the per-type pre-activations y_t of one layer and the destination rows' own layer input x_t
+    (kgwroot_* in include/kgwas_hip.h): one launch forward, one backward for every dx (and the masked gradient, when the kernel
+    has to mask), and the weight-gradient products of _root_weight_grad.  Saves x and W and -- unless the consumer masks the
+    gradient itself or no ReLU is applied -- out; y is not saved (d y is the masked gradient itself)."""
+
+    @staticmethod
+    def forward(ctx, types, out_blocks, premasked, relu, x_premasked, weight, *yx):
+        ctx.set_materialize_grads(False)
+        n = len(types)
+        ys, xs = [_hdrop_rows(y) for y in yx[:n]], [_hdrop_rows(x) for x in yx[n:]]
+        jobs = (_lib.KgwRootJob * n)()
+        outs = []
+        for k, (j, y, x, t) in enumerate(zip(jobs, ys, xs, types)):
+            ob = out_blocks[k] if out_blocks is not None else None
+            o = ob.view() if ob is not None and ob.n == y.shape[0] and ob.buf.data_ptr() % 16 == 0 else torch.empty_like(y, memory_format=torch.contiguous_format)
+            j.x, j.ldx, j.y, j.ldy, j.dst, j.ldd = _p(x), x.stride(0), _p(y), y.stride(0), _p(o), o.stride(0)
+            j.rows, j.type, j.W = y.shape[0], t, _p(weight[t])
+            outs.append(o)
+        _lib.check(_lib.lib().kgw_root_linear_fwd(n, jobs, int(relu), _lib.stream_ptr()), 'kgw_root_linear_fwd')
+        masks = relu and not premasked
+        ctx.args = (types, masks, x_premasked)
+        ctx.save_for_backward(weight, *xs, *(outs if masks else []))
+        return tuple(outs)
+
+    @staticmethod
+    def backward(ctx, *gs):
+        types, masks, x_premasked = ctx.args
+        n = len(types)
+        weight = ctx.saved_tensors[0]
+        xs = ctx.saved_tensors[1:1 + n]
+        outs = ctx.saved_tensors[1 + n:] if masks else [None] * n
+        live = [k for k, g in enumerate(gs) if g is not None]
+        dys, dxs = [None] * n, [None] * n
+        if not live:
+            return (None,) * 6 + tuple(dys) + tuple(dxs)
+        jobs = (_lib.KgwRootBwdJob * len(live))()
+        keep, pairs = [], []
+        for j, k in zip(jobs, live):
+            g, x, o = _hdrop_rows(gs[k]), xs[k], outs[k]
+            dx = torch.empty_like(x, memory_format=torch.contiguous_format)
+            gm = torch.empty_like(g, memory_format=torch.contiguous_format) if o is not None else g
+            keep.append(g)
+            dys[k], dxs[k] = gm, dx
+            pairs.append((types[k], gm, x))
+            j.g, j.ldg, j.dx, j.lddx, j.x, j.ldx = _p(g), g.stride(0), _p(dx), dx.stride(0), _p(x), x.stride(0)
+            j.out, j.ldo, j.gm, j.ldgm = (_p(o), o.stride(0), _p(gm), gm.stride(0)) if o is not None else (None, 0, None, 0)
+            j.rows, j.type, j.W, j.x_premasked = x.shape[0], types[k], _p(weight[types[k]]), int(x_premasked)
+        _lib.check(_lib.lib().kgw_root_linear_bwd(len(live), jobs, _lib.stream_ptr()), 'kgw_root_linear_bwd')
+        dW = _root_weight_grad(pairs, weight) if ctx.needs_input_grad[5] else None
+        return (None,) * 5 + (dW,) + tuple(dys) + tuple(dxs)
+
+
+def root_linear(outs, types, xs, weight: torch.Tensor, out_blocks=None, premasked=False, relu=True, x_premasked=False):
+    """The root weight of a message-passing layer: ``outs`` = the per-type PRE-ACTIVATION outputs [rows_t, 128] of the relation
+    combine, ``types`` = their (distinct) node type ids, ``xs`` = the same rows' own layer input [rows_t, 128] (the leading rows of
+    each type's layer input), ``weight`` = the site's packed bias-free Linears [n_types <= 8, 128, 128], slice t for node type t
+    in nn.Linear layout [out, in].  Returns act(out_t + x_t W_t^T), act = ReLU iff ``relu`` (include/kgwas_hip.h).  ``out_blocks``:
+    optional RowBlock per output to write into (the next layer's input) -- given when this is the site's last launch; a norm or
+    dropout behind it takes temporaries.  ``premasked``: whoever consumes the outputs multiplies their gradient by (out > 0) itself
+    (gat_aggregate(relu_input=True) / readout_weighted_mse(h_is_relu=True)); otherwise, with ``relu``, the backward kernel does
+    from the saved out and hands the masked gradient on as d out_t (the transform behind it runs premasked).  ``x_premasked``: the
+    xs are ReLU outputs whose producer runs premasked (layers >= 2 of the fused and multi-head routes): d x_t comes out multiplied
+    by (x_t > 0).  One autograd node over all types; d weight comes back whole, ZERO slices for types not in ``types`` or without
+    rows (not ``None``)."""
+    outs, xs = list(outs), list(xs)
+    if not outs:
+        return []
+    types = tuple(int(t) for t in types)
+    assert len(outs) == len(xs) == len(types) == len(set(types)) <= 8
+    assert all(o.dim() == 2 and o.shape[1] == KGW_C and x.shape == o.shape for o, x in zip(outs, xs))
+    assert weight.dim() == 3 and weight.shape[1:] == (KGW_C, KGW_C) and max(types) < weight.shape[0] <= 8
+    assert weight.is_contiguous() and weight.dtype == torch.float32 and weight.data_ptr() % 16 == 0
+    if not _lib.has_root_weight():
+        raise _lib.KgwasHipError('this libkgwas_hip.so predates the root weight (kgw_root_linear_fwd)')
+    return list(_RootLinear.apply(types, out_blocks, bool(premasked), bool(relu), bool(x_premasked), weight, *outs, *xs))
 
 
 class _FoldFC(torch.autograd.Function):
