@@ -30,7 +30,7 @@ from __future__ import annotations
 import math
 import os
 from collections import OrderedDict
-from typing import Dict, List, Optional, Tuple
+from typing import Dict, List, NamedTuple, Optional, Tuple
 
 import torch
 import torch.nn as nn
@@ -270,6 +270,38 @@ class SagePack(nn.Module):
                 self.bias[i, :cl].copy_(value)
             else:
                 (self.w_l_t if field == 'lin_l.weight' else self.w_r_t)[i, :cl, :cl].copy_(value.t())
+
+
+class LayerSite(NamedTuple):
+    """What follows the transform of layer ``layer`` on the fused and the multi-head route (HeteroGNN._layer_site decides it,
+    HeteroGNN._finish_layer runs it): up to three launches, the LAST of which (``writer``) writes the next layer's row blocks, so
+    no join_blocks copy is added; the others write temporaries.  ``premasked``: the consumer masks the gradient by (out > 0).
+    * root weight: the transform stops at the pre-activation as at a norm site; the root launch adds W_root x of the destination
+      rows' own layer input and applies the ReLU (or leaves it to the norm).  From layer 2 on x is a ReLU output whose producer
+      runs premasked: ``x_premasked``.
+    * layer normalisation: the transform then stops at the pre-activation (its backward has no ReLU left: premasked), the norm's
+      launch applies LN and the ReLU.  The next aggregate folds dH *= (H > 0) with H the norm's output: premasked for the norm too.
+    * hidden-state dropout: the producer keeps its own (undropped) rows -- it saves them -- and the dropout launch writes the
+      dropped state.  The next aggregate folds dH *= (H > 0) with H the DROPPED state (kept and positive); the dropout's backward
+      supplies the scale."""
+    layer: int
+    root: Optional[torch.Tensor]        # the packed root weights (HeteroGNN._root_site) or None
+    norm: Optional[tuple]               # the norm's (weight, bias) (HeteroGNN._norm_site) or None
+    drop: Optional[tuple]               # the dropout's (p, word) or None
+    writer: str                         # 'transform', 'root', 'norm' or 'drop'
+    premasked: bool                     # of the transform
+    relu: bool                          # of the transform
+    root_premasked: bool
+    root_relu: bool
+    x_premasked: bool
+    norm_premasked: bool
+
+    def out_blocks(self, stage: str, nxt):
+        return nxt if stage == self.writer else None
+
+    def hbuf_after_mean(self, hbuf):
+        """'mean' scales the transform's outputs: they are no longer its blocks, so only a later launch's writing keeps ``hbuf``."""
+        return hbuf if self.writer != 'transform' else None
 
 
 class HeteroGNN(nn.Module):
@@ -600,6 +632,36 @@ class HeteroGNN(nn.Module):
                   for t, name in enumerate(sc.node_types) if int(m.lay_src[l - 1][t])}
         return buf, blocks
 
+    def _layer_parts(self, batch: SampledBatch, l: int, h: Dict[str, torch.Tensor]):
+        """The state of every node type that sends or receives messages in layer l (its leading ``lay_src`` rows), in type order, and
+        their (row offset, rows) spans in the type-major layer input (src_base)."""
+        m = batch.meta
+        parts, spans = [], []
+        for t, name in enumerate(self.schema.node_types):
+            ns = int(m.lay_src[l - 1][t])
+            if ns:
+                if name not in h or h[name].shape[0] < ns:
+                    raise RuntimeError(f'layer {l}: node type {name!r} takes part in the layer but has no '
+                                       f'incoming relation to produce its layer-{l - 1} state')
+                parts.append(h[name] if h[name].shape[0] == ns else h[name][:ns])
+                spans.append((int(m.src_base[l - 1][t]), ns))
+        return parts, spans
+
+    def _join_layer_input(self, batch: SampledBatch, l: int, h: Dict[str, torch.Tensor], hbuf=None):
+        """The type-major input matrix H of layer l from the per-type states ``h``, joined in ``hbuf`` (``_layer_input(batch, l)``,
+        allocated here when the caller carries none), or the one part itself when it is the whole matrix."""
+        parts, spans = self._layer_parts(batch, l, h)
+        if hbuf is None:
+            hbuf, _ = self._layer_input(batch, l)
+        return ops.join_blocks(hbuf, spans, parts) if len(parts) != 1 or parts[0].shape[0] != hbuf.shape[0] else parts[0]
+
+    def _dst_blocks(self, batch: SampledBatch, l: int):
+        """The destination blocks of layer l, one per node type that receives messages: (``tys``, the type ids; ``blocks`` =
+        [(lo, hi, z0, rows)]: the type's relation slots [lo, hi) in the layer's pack, its offset in the aggregate Z, its rows)."""
+        m, rng = batch.meta, self._dst_range[l - 1]
+        tys = [t for t in range(self.schema.NT) if int(m.lay_rows[l - 1][t])]
+        return tys, [(rng[t][0], rng[t][1], int(m.z_base[l - 1][t]), int(m.lay_rows[l - 1][t])) for t in tys]
+
     def _embed_all(self, batch: SampledBatch, x_dict, blocks=None, fold=False):
         """All feature MLPs (model.py:56-60).  The three GO types share ``go_feat_mlp`` (model.py:58-60): their
         rows go through it as ONE matrix.  ``blocks``: RowBlocks of the first layer's input to write into."""
@@ -658,50 +720,39 @@ class HeteroGNN(nn.Module):
             return o[0]
         return getattr(torch, self.aggr)(o, dim=0).values
 
+    def _relation_products(self, zr: torch.Tensor, w_t: torch.Tensor, bias: torch.Tensor, lo: int, hi: int, what: str):
+        """'min' / 'max': the per-relation outputs o[r] = zr[r] @ w_t[lo + r] + bias[lo + r] of one destination type, [R, rows, C]: one
+        own-kernel product per relation (the library-free form) or, where the library is allowed, one batched product, noted."""
+        if ops.LIBRARY_GEMM.own_first:
+            return torch.stack([ops.linear_act(zr[r].contiguous(), w_t[lo + r], bias[lo + r], relu=False) for r in range(hi - lo)])
+        ops.LIBRARY_GEMM.note(what, hi - lo, zr.shape[1], self.hidden)
+        return torch.baddbmm(bias[lo:hi].unsqueeze(1), zr, w_t[lo:hi])
+
     def _sage_layers(self, batch: SampledBatch, h: Dict[str, torch.Tensor], hbuf=None, hdrop=None):
         """SAGE backbone (kgwas/model.py:38,74-75): out_d = relu(sum_r [lin_l^r(mean_{j->i} h_s[j]) + lin_r^r(h_d[i])]).
         The neighbour mean IS the attention aggregate with all logits equal: the same kernels run with zero attention
         vectors (alpha = 1/deg; rows without in-edges stay zero like PyG's mean), forward and backward; the root
         term is one more product per destination type with the relation-summed lin_r."""
-        sc, m, C = self.schema, batch.meta, self.hidden
+        sc, C = self.schema, self.hidden
         dev = self.lin.weight.device
         zeros = torch.zeros(sc.NR, C, device=dev)
         for l in range(1, self.num_layers + 1):
             P: SagePack = self.live_packs[l - 1]
-            rng = self._dst_range[l - 1]
-            parts, spans = [], []
-            for t, name in enumerate(sc.node_types):
-                ns = int(m.lay_src[l - 1][t])
-                if ns:
-                    if name not in h or h[name].shape[0] < ns:
-                        raise RuntimeError(f'layer {l}: node type {name!r} takes part in the layer but has no '
-                                           f'incoming relation to produce its layer-{l - 1} state')
-                    parts.append(h[name] if h[name].shape[0] == ns else h[name][:ns])
-                    spans.append((int(m.src_base[l - 1][t]), ns))
-            if hbuf is None:
-                hbuf, _ = self._layer_input(batch, l)
-            H = ops.join_blocks(hbuf, spans, parts) if len(parts) != 1 or parts[0].shape[0] != hbuf.shape[0] else parts[0]
+            H = self._join_layer_input(batch, l, h, hbuf)
             hbuf = None
             Z, _, _ = ops.gat_aggregate(batch, l, H, zeros, zeros, self.negative_slope, self.temperature)
             h_next = {}
-            for t, name in enumerate(sc.node_types):
-                rows = int(m.lay_rows[l - 1][t])
-                if not rows:
-                    continue
-                lo, hi = rng[t]
-                R = hi - lo
-                z0 = int(m.z_base[l - 1][t])
+            for t, (lo, hi, z0, rows) in zip(*self._dst_blocks(batch, l)):
+                name, R = sc.node_types[t], hi - lo
                 if self.aggr in ('min', 'max'):
                     zr = Z[z0:z0 + rows * R].view(rows, R, C).transpose(0, 1)                    # [R, rows, C]
+                    o = self._relation_products(zr, P.w_l_t, P.bias, lo, hi, 'sage min/max per-relation outputs')
                     if ops.LIBRARY_GEMM.own_first:          # (library-free form: one own-kernel product per relation and term)
                         hr = h[name][:rows].contiguous()
                         zero = torch.zeros(C, device=dev)
-                        o = torch.stack([ops.linear_act(zr[r].contiguous(), P.w_l_t[lo + r], P.bias[lo + r], relu=False) +
-                                         ops.linear_act(hr, P.w_r_t[lo + r], zero, relu=False) for r in range(R)])
+                        o = o + torch.stack([ops.linear_act(hr, P.w_r_t[lo + r], zero, relu=False) for r in range(R)])
                     else:
-                        ops.LIBRARY_GEMM.note('sage min/max per-relation outputs', R, rows, C)
-                        o = torch.baddbmm(P.bias[lo:hi].unsqueeze(1), zr, P.w_l_t[lo:hi]) + \
-                            torch.matmul(h[name][:rows].unsqueeze(0), P.w_r_t[lo:hi])
+                        o = o + torch.matmul(h[name][:rows].unsqueeze(0), P.w_r_t[lo:hi])
                     h_next[name] = self._combine_relations(o)
                     continue
                 x = Z[z0:z0 + rows * R].view(rows, R * C)
@@ -720,27 +771,18 @@ class HeteroGNN(nn.Module):
     def _all_layer_params(self, batch: SampledBatch, folded: bool):
         """_layer_params for every layer with the relation vectors of ALL layers from one launch (ops.rel_vectors_all): they
         depend on the parameters only.  Their backward then is one launch too, after the first layer's."""
-        sc, m = self.schema, batch.meta
         dev = self.lin.weight.device
-        blocks_all, zeros = [], []
-        for l in range(1, self.num_layers + 1):
-            rng = self._dst_range[l - 1]
-            tys = [t for t in range(sc.NT) if int(m.lay_rows[l - 1][t])]
-            blocks_all.append([(rng[t][0], rng[t][1], int(m.z_base[l - 1][t]), int(m.lay_rows[l - 1][t])) for t in tys])
-            zeros.append(ops.aggregate_workspace(batch, l, dev))
-        rv = ops.rel_vectors_all([self.live_packs[l] for l in range(self.num_layers)], blocks_all, zeros)
+        blocks_all = [self._dst_blocks(batch, l)[1] for l in range(1, self.num_layers + 1)]
+        zeros = [ops.aggregate_workspace(batch, l, dev) for l in range(1, self.num_layers + 1)]
+        rv =ops.rel_vectors_all([self.live_packs[l] for l in range(self.num_layers)], blocks_all, zeros)
         return [self._layer_params(batch, l, folded, relvec=rv[l - 1], zbuf=zeros[l - 1]) for l in range(1, self.num_layers + 1)]
 
     def _layer_params(self, batch: SampledBatch, l: int, folded: bool, relvec=None, zbuf=None):
         """Everything layer l needs that depends on the PARAMETERS only (and on the batch's static row counts): the destination
         blocks, the zeroed aggregate workspace, u_r / v_r / summed biases (ops.rel_vectors) and, for a folded layer 1, the
         fold of FC_output into them.  No activation enters."""
-        sc, m = self.schema, batch.meta
         P: RelationPack = self.live_packs[l - 1]
-        rng = self._dst_range[l - 1]
-        # destination blocks of the layer: one per node type that receives messages
-        tys = [t for t in range(sc.NT) if int(m.lay_rows[l - 1][t])]
-        blocks = [(rng[t][0], rng[t][1], int(m.z_base[l - 1][t]), int(m.lay_rows[l - 1][t])) for t in tys]
+        tys, blocks = self._dst_blocks(batch, l)
         # u_r = W_src^T att_src ; v_r = W_dst^T att_dst (W_src^T att_dst for same-type relations) and the summed
         # bias of every destination block: one launch
         # ... and the zero fill of the aggregate's workspace rides in the same launch
@@ -811,50 +853,19 @@ class HeteroGNN(nn.Module):
         That column-block product runs on the layer-transform kernels with the heads as H x R stacked "relations" of column-masked
         weights W_r^T * mask_h (H times the transform's FLOPs: DESIGN.md section 8).  Unfused: no FC_output fold, no parameter
         riders; u^h, v^h and the summed bias come from element-wise framework ops."""
-        sc, m, C, NH = self.schema, batch.meta, self.hidden, self.heads
         for l in range(1, self.num_layers + 1):
             P: RelationPack = self.live_packs[l - 1]
-            rng = self._dst_range[l - 1]
-            tys = [t for t in range(sc.NT) if int(m.lay_rows[l - 1][t])]
-            blocks = [(rng[t][0], rng[t][1], int(m.z_base[l - 1][t]), int(m.lay_rows[l - 1][t])) for t in tys]
+            tys, blocks = self._dst_blocks(batch, l)
             U, V = self._head_vectors(P)
-            parts, spans = [], []
-            for t, name in enumerate(sc.node_types):
-                ns = int(m.lay_src[l - 1][t])
-                if ns:
-                    if name not in h or h[name].shape[0] < ns:
-                        raise RuntimeError(f'layer {l}: node type {name!r} takes part in the layer but has no '
-                                           f'incoming relation to produce its layer-{l - 1} state')
-                    parts.append(h[name] if h[name].shape[0] == ns else h[name][:ns])
-                    spans.append((int(m.src_base[l - 1][t]), ns))
-            if hbuf is None:
-                hbuf, _ = self._layer_input(batch, l)
-            H = ops.join_blocks(hbuf, spans, parts) if len(parts) != 1 or parts[0].shape[0] != hbuf.shape[0] else parts[0]
+            H = self._join_layer_input(batch, l, h, hbuf)
             # (from layer 2 on, H is the previous layer's ReLU output and its backward is folded into this node's)
-            Z, _, _ = ops.gat_aggregate(batch, l, H, U, V, self.negative_slope, self.temperature, relu_input=(l > 1), heads=NH)
-            hbuf, nxt = self._layer_input(batch, l + 1) if l < self.num_layers else (None, {})
-            drops = hdrop is not None and l < self.num_layers
-            site = self._norm_site(l)
-            root = self._root_site(l)
-            # (a layer whose output gets a root term, is normalised or dropped leaves the next layer's blocks to the LAST of those
-            #  launches: see _fused_layers)
-            later = drops or site is not None or root is not None
-            outs = ops.layer_transform_heads(P, Z, blocks, self.head_mask, None if later else [nxt.get(sc.node_types[t]) for t in tys],
-                                             premasked=(l < self.num_layers) or last_premasked or root is not None,
-                                             relu=site is None and root is None)
-            if self.aggr == 'mean':
-                hbuf = None if not later else hbuf
-                outs = [o * (1.0 / (hi - lo)) for o, (lo, hi, _, _) in zip(outs, blocks)]
-            if root is not None:        # (the root Linear is full width, as PyG's ``res`` is H * C wide)
-                outs = ops.root_linear(outs, tys, self._root_inputs(h, tys, [b[3] for b in blocks]), root,
-                                       None if (drops or site is not None) else [nxt.get(sc.node_types[t]) for t in tys],
-                                       premasked=(l < self.num_layers) or last_premasked, relu=site is None, x_premasked=l > 1)
-            if site is not None:
-                outs = ops.layer_norm_relu(outs, tys, site[0], site[1], self.hidden_logical,
-                                           None if drops else [nxt.get(sc.node_types[t]) for t in tys], premasked=True)
-            if drops:
-                outs = ops.hidden_dropout(outs, tys, l, hdrop[0], hdrop[1], [nxt.get(sc.node_types[t]) for t in tys])
-            h = {sc.node_types[t]: o for t, o in zip(tys, outs)}
+            Z, _, _ = ops.gat_aggregate(batch, l, H, U, V, self.negative_slope, self.temperature, relu_input=(l > 1), heads=self.heads)
+            hbuf, nxt = self._next_blocks(batch, l, tys)
+            site = self._layer_site(l, hdrop, last_premasked)
+            outs = ops.layer_transform_heads(P, Z, blocks, self.head_mask, site.out_blocks('transform', nxt),
+                                             premasked=site.premasked, relu=site.relu)
+            # (a root Linear behind it is full width, as PyG's ``res`` is H * C wide)
+            h, hbuf = self._finish_layer(site, h, tys, blocks, outs, nxt, hbuf)
         return h, []
 
     def _edge_weights(self, batch: SampledBatch, l: int, stat, e_edge):
@@ -939,6 +950,42 @@ class HeteroGNN(nn.Module):
             outs = [a - b for a, b in zip(outs, neg)]
         return dict(zip(names, outs))
 
+    def _next_blocks(self, batch: SampledBatch, l: int, tys):
+        """(``_layer_input(batch, l + 1)``'s matrix, its RowBlock or None for each type of ``tys``); (None, Nones) after the last layer."""
+        hbuf, nxt = self._layer_input(batch, l + 1) if l < self.num_layers else (None, {})
+        return hbuf, [nxt.get(self.schema.node_types[t]) for t in tys]
+
+    def _layer_site(self, l: int, hdrop=None, last_premasked=False) -> LayerSite:
+        """``hdrop``: see ``_hidden_dropout``; ``last_premasked``: the consumer of the LAST layer's output masks its gradient by
+        (out > 0) itself (the fused read-out + loss node), as the next layer's aggregate does for every other layer."""
+        last = l == self.num_layers
+        root, norm = self._root_site(l), self._norm_site(l)
+        drop = None if (hdrop is None or last) else (hdrop[0], hdrop[1])
+        writer = 'drop' if drop is not None else 'norm' if norm is not None else 'root' if root is not None else 'transform'
+        consumer_masks = (not last) or bool(last_premasked)
+        return LayerSite(layer=l, root=root, norm=norm, drop=drop, writer=writer,
+                         premasked=consumer_masks or root is not None, relu=norm is None and root is None,
+                         root_premasked=consumer_masks, root_relu=norm is None, x_premasked=l > 1, norm_premasked=True)
+
+    def _finish_layer(self, site: LayerSite, h: Dict[str, torch.Tensor], tys, blocks, outs, nxt, hbuf):
+        """The stages of ``site`` on the transform's per-type outputs ``outs``: the 1 / R of 'mean', the root term (x from the layer's
+        input ``h``), the norm, the dropout.  ``nxt`` / ``hbuf``: see ``_next_blocks``.  Returns (the new h, the hbuf to carry)."""
+        if self.aggr == 'mean':
+            # mean over the relations of a destination type = the sum scaled by 1/R; relu(s/R) = relu(s)/R, and the
+            # positive scale commutes with the folded ReLU masks.  At a norm site the scale goes in BEFORE the norm: LN(y / R);
+            # the root term is added to the scaled relation part
+            hbuf = site.hbuf_after_mean(hbuf)
+            outs = [o * (1.0 / (hi - lo)) for o, (lo, hi, _, _) in zip(outs, blocks)]
+        if site.root is not None:
+            outs = ops.root_linear(outs, tys, self._root_inputs(h, tys, [b[3] for b in blocks]), site.root, site.out_blocks('root', nxt),
+                                   premasked=site.root_premasked, relu=site.root_relu, x_premasked=site.x_premasked)
+        if site.norm is not None:
+            outs = ops.layer_norm_relu(outs, tys, site.norm[0], site.norm[1], self.hidden_logical, site.out_blocks('norm', nxt),
+                                       premasked=site.norm_premasked)
+        if site.drop is not None:
+            outs = ops.hidden_dropout(outs, tys, site.layer, site.drop[0], site.drop[1], site.out_blocks('drop', nxt))
+        return {self.schema.node_types[t]: o for t, o in zip(tys, outs)}, hbuf
+
     def _fused_layers(self, batch: SampledBatch, h: Dict[str, torch.Tensor], want_attention=False, hbuf=None,
                       last_premasked=False, folded=False, prep=None, dropout=None, hdrop=None):
         """``folded``: h holds the feature MLPs' hidden state h2 (``_embed_all(fold=True)``), not their output: layer 1 runs
@@ -953,29 +1000,14 @@ class HeteroGNN(nn.Module):
             if want_attention:
                 raise NotImplementedError('gat_num_head > 1: the attention queries are single-head (kgw_edge_alpha)')
             return self._head_layers(batch, h, hbuf, last_premasked, hdrop)
-        sc = self.schema
-        m = batch.meta
-        C = self.hidden
-        dev = self.lin.weight.device
+        sc, C = self.schema, self.hidden
         attn = []
         if prep is None and self.num_layers > 1 and _RELVEC_ALL:
             prep = self._all_layer_params(batch, folded)
         for l in range(1, self.num_layers + 1):
             P: RelationPack = self.live_packs[l - 1]
             tys, blocks, zws, U, V, bsum, Wv, kap, Wp, gam, term = prep[l - 1] if prep is not None else self._layer_params(batch, l, folded)
-            # layer input, type-major (src_base): every type that sends or receives messages in this layer
-            parts, spans = [], []
-            for t, name in enumerate(sc.node_types):
-                ns = int(m.lay_src[l - 1][t])
-                if ns:
-                    if name not in h or h[name].shape[0] < ns:
-                        raise RuntimeError(f'layer {l}: node type {name!r} takes part in the layer but has no '
-                                           f'incoming relation to produce its layer-{l - 1} state')
-                    parts.append(h[name] if h[name].shape[0] == ns else h[name][:ns])
-                    spans.append((int(m.src_base[l - 1][t]), ns))
-            if hbuf is None:
-                hbuf, _ = self._layer_input(batch, l)
-            H = ops.join_blocks(hbuf, spans, parts) if len(parts) != 1 or parts[0].shape[0] != hbuf.shape[0] else parts[0]
+            H = self._join_layer_input(batch, l, h, hbuf)
             # (from layer 2 on, H is the previous layer's ReLU output: with the fused transform its backward is folded
             # into this node's)
             fused = self.aggr in ('sum', 'mean')
@@ -992,50 +1024,18 @@ class HeteroGNN(nn.Module):
                 for (lo, hi, z0, rows) in blocks:
                     R = hi - lo
                     zr = Z[z0:z0 + rows * R].view(rows, R, C).transpose(0, 1)
-                    if ops.LIBRARY_GEMM.own_first:
-                        o = torch.stack([ops.linear_act(zr[r].contiguous(), Wv[lo + r], P.bias[lo + r], relu=False) for r in range(R)])
-                    else:
-                        ops.LIBRARY_GEMM.note('gat min/max per-relation outputs', R, rows, C)
-                        o = torch.baddbmm(P.bias[lo:hi].unsqueeze(1), zr, Wv[lo:hi])
+                    o = self._relation_products(zr, Wv, P.bias, lo, hi, 'gat min/max per-relation outputs')
                     outs.append(self._combine_relations(o))
                 pre = self._add_root(l, h, {sc.node_types[t]: o for t, o in zip(tys, outs)})
                 h = self._drop_hidden(l, self._activate(l, pre), hdrop)
                 continue
             # per-relation linear maps + bias + relation sum + ReLU: one GEMM per destination type, one autograd node
-            hbuf, nxt = self._layer_input(batch, l + 1) if l < self.num_layers else (None, {})
-            # hidden-state dropout on this layer's output: the transform keeps its own (undropped) rows -- it saves them -- and the
-            # dropout launch writes the dropped state into the next layer's blocks, so no join_blocks copy is added.  The next
-            # aggregate folds dH *= (H > 0) with H the DROPPED state (kept and positive); the dropout's backward supplies the scale.
-            drops = hdrop is not None and l < self.num_layers
-            # layer normalisation of this layer's output: the transform then stops at the pre-activation (its backward has no ReLU
-            # left: premasked), the norm's launch applies LN and the ReLU and writes the next layer's blocks (or, with dropout
-            # behind it, a temporary).  The next aggregate folds dH *= (H > 0) with H the norm's output: premasked for the norm too.
-            site = self._norm_site(l)
-            # root weight: the transform stops at the pre-activation as at a norm site; the root launch adds W_root x of the
-            # destination rows' own layer input and applies the ReLU (or leaves it to the norm), writing the next layer's blocks when
-            # it is the site's last launch.  From layer 2 on x is a ReLU output whose producer runs premasked: x_premasked.
-            root = self._root_site(l)
-            later = drops or site is not None or root is not None
-            outs = ops.layer_transform(P, Z, blocks, None if later else [nxt.get(sc.node_types[t]) for t in tys],
-                                       premasked=(l < self.num_layers) or last_premasked or root is not None, bias_sum=bsum,
+            hbuf, nxt = self._next_blocks(batch, l, tys)
+            site = self._layer_site(l, hdrop, last_premasked)
+            outs = ops.layer_transform(P, Z, blocks, site.out_blocks('transform', nxt), premasked=site.premasked, bias_sum=bsum,
                                        weight=Wp if Wp is not None else Wv, gamma=gam, stat=stat if gam is not None else None,
-                                       relu=site is None and root is None)
-            if self.aggr == 'mean':
-                # mean over the relations of a destination type = the sum scaled by 1/R; relu(s/R) = relu(s)/R, and the
-                # positive scale commutes with the folded ReLU masks.  At a norm site the scale goes in BEFORE the norm: LN(y / R)
-                hbuf = None if not later else hbuf
-                outs = [o * (1.0 / (hi - lo)) for o, (lo, hi, _, _) in zip(outs, blocks)]
-            if root is not None:
-                outs = ops.root_linear(outs, tys, self._root_inputs(h, tys, [b[3] for b in blocks]), root,
-                                       None if (drops or site is not None) else [nxt.get(sc.node_types[t]) for t in tys],
-                                       premasked=(l < self.num_layers) or last_premasked, relu=site is None, x_premasked=l > 1)
-            if site is not None:
-                outs = ops.layer_norm_relu(outs, tys, site[0], site[1], self.hidden_logical,
-                                           None if drops else [nxt.get(sc.node_types[t]) for t in tys], premasked=True)
-            if drops:
-                outs = ops.hidden_dropout(outs, tys, l, hdrop[0], hdrop[1], [nxt.get(sc.node_types[t]) for t in tys])
-            h_next = {sc.node_types[t]: o for t, o in zip(tys, outs)}
-            h = h_next
+                                       relu=site.relu)
+            h, hbuf = self._finish_layer(site, h, tys, blocks, outs, nxt, hbuf)
         return h, attn
 
     def forward(self, x_dict, edge_index_dict, batch_size, genotype=None, return_h=False,
@@ -1141,14 +1141,7 @@ class HeteroGNN(nn.Module):
                 if len(pack.rel_ids):
                     u, v = ops.rel_vectors(pack)           # rows of the pack's relations, zeros elsewhere
                     U += u; V += v
-            parts = []
-            for t, name in enumerate(sc.node_types):
-                ns = int(m.lay_src[l - 1][t])
-                if ns:
-                    if name not in h or h[name].shape[0] < ns:
-                        raise RuntimeError(f'layer {l}: node type {name!r} has no layer-{l - 1} state')
-                    parts.append(h[name][:ns])
-            H = torch.cat(parts, 0)
+            H = torch.cat(self._layer_parts(batch, l, h)[0], 0)       # (no preallocated layer input on this route)
             gate = self.gat_sigmoid
             Z, stat, e_edge = ops.gat_aggregate(batch, l, H, U, V, self.negative_slope, self.temperature, raw_weights=raw and not gate,
                                                 sigmoid_gate=gate,

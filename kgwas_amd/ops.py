@@ -2480,11 +2480,32 @@ def _hdrop_launch(pairs, types, layer, thresh, scale, word):
                'kgw_hidden_dropout')
 
 
-def _hdrop_rows(x):
-    """``x`` as the kernel reads it: fp32 rows of 128, 16-byte aligned, row stride a multiple of 4 floats (a copy only if not)."""
+def _site_rows(x):
+    """``x`` [rows, 128] as the site kernels read it: fp32, 16-byte aligned, row stride a multiple of 4 floats (a copy only if not)."""
     ok = x.dtype == torch.float32 and x.stride(1) == 1 and x.stride(0) % 4 == 0 and x.data_ptr() % 16 == 0 and \
         (x.stride(0) >= KGW_C or x.shape[0] <= 1)
     return x if ok else x.float().contiguous()
+
+
+def _site_dst(out_blocks, k: int, x):
+    """Where a site operator writes its k-th output: the RowBlock ``out_blocks[k]``'s alias when it has x's row count and is 16-byte
+    aligned, else a fresh contiguous tensor.  (Never x's own rows: the node that produced them may have saved them -- _LayerTransform does.)"""
+    ob = out_blocks[k] if out_blocks is not None else None
+    if ob is not None and ob.n == x.shape[0] and ob.buf.data_ptr() % 16 == 0:
+        return ob.view()
+    return torch.empty_like(x, memory_format=torch.contiguous_format)
+
+
+def _site_args(outs, types, distinct: bool):
+    """The argument checks the site operators share: (``outs`` as a list, ``types`` as a tuple of ints) -- one type per output, at
+    most 8 of them, every output [rows, 128] and, where ``distinct``, no type twice.  No outputs: ([], ()), unchecked."""
+    outs = list(outs)
+    if not outs:
+        return [], ()
+    types = tuple(int(t) for t in types)
+    assert len(outs) == len(types) <= 8 and all(o.dim() == 2 and o.shape[1] == KGW_C for o in outs)
+    assert not distinct or len(set(types)) == len(types)
+    return outs, types
 
 
 class _HiddenDropout(torch.autograd.Function):
@@ -2495,14 +2516,9 @@ class _HiddenDropout(torch.autograd.Function):
     @staticmethod
     def forward(ctx, types, layer, thresh, scale, word, out_blocks, *outs):
         ctx.set_materialize_grads(False)
-        pairs = []
-        for k, x in enumerate(outs):
-            x = _hdrop_rows(x)
-            ob = out_blocks[k] if out_blocks is not None else None
-            # (never the input's own rows: the node that produced them may have saved them -- _LayerTransform does)
-            y = ob.view() if ob is not None and ob.n == x.shape[0] and ob.buf.data_ptr() % 16 == 0 else torch.empty_like(x, memory_format=torch.contiguous_format)
-            assert y.data_ptr() != x.data_ptr() or x.shape[0] == 0
-            pairs.append((x, y))
+        xs = [_site_rows(x) for x in outs]
+        pairs = [(x, _site_dst(out_blocks, k, x)) for k, x in enumerate(xs)]
+        assert all(y.data_ptr() != x.data_ptr() or x.shape[0] == 0 for x, y in pairs)
         _hdrop_launch(pairs, types, layer, thresh, scale, word)
         ctx.args = (types, layer, thresh, scale)
         ctx.word = word
@@ -2511,7 +2527,7 @@ class _HiddenDropout(torch.autograd.Function):
     @staticmethod
     def backward(ctx, *dys):
         types, layer, thresh, scale = ctx.args
-        live = [(k, _hdrop_rows(d)) for k, d in enumerate(dys) if d is not None]
+        live = [(k, _site_rows(d)) for k, d in enumerate(dys) if d is not None]
         dxs = [None] * len(dys)
         if live:
             pairs = [(d, torch.empty_like(d, memory_format=torch.contiguous_format)) for _, d in live]
@@ -2528,15 +2544,14 @@ def hidden_dropout(outs, types, layer: int, p: float, word: torch.Tensor, out_bl
     (include/kgwas_hip.h).  ``word``: int64 device tensor of one element, READ WHEN THE KERNEL RUNS (a captured step replays with
     whatever it then holds).  ``out_blocks``: optional RowBlock per output to write the dropped rows into (the next layer's input);
     the inputs themselves are never overwritten.  Returns the dropped outputs, in order."""
-    outs = list(outs)
+    outs, types = _site_args(outs, types, distinct=False)
     if not outs:
         return []
-    assert len(outs) == len(types) <= 8 and all(o.dim() == 2 and o.shape[1] == KGW_C for o in outs)
     assert word.dtype == torch.int64 and word.numel() == 1 and word.is_cuda and word.is_contiguous()
     if not _lib.has_hidden_dropout():
         raise _lib.KgwasHipError('this libkgwas_hip.so predates hidden-state dropout (kgw_hidden_dropout)')
     thresh, scale = dropout_params(p)
-    return list(_HiddenDropout.apply(tuple(int(t) for t in types), int(layer), thresh, scale, word, out_blocks, *outs))
+    return list(_HiddenDropout.apply(types, int(layer), thresh, scale, word, out_blocks, *outs))
 
 
 LNORM_EPS = 1e-5            # KGW_LNORM_EPS (include/kgwas_hip.h): torch.nn.LayerNorm's default
@@ -2552,17 +2567,14 @@ class _LayerNormReLU(torch.autograd.Function):
     def forward(ctx, types, c_logical, out_blocks, premasked, weight, bias, *ys):
         ctx.set_materialize_grads(False)
         L = _lib.lib()
-        xs = [_hdrop_rows(y) for y in ys]
+        xs = [_site_rows(y) for y in ys]
         stat = torch.empty(max(sum(x.shape[0] for x in xs), 1), 2, device=weight.device)
         jobs = (_lib.KgwLNormJob * len(xs))()
-        outs, r0 = [], 0
-        for k, (j, x, t) in enumerate(zip(jobs, xs, types)):
-            ob = out_blocks[k] if out_blocks is not None else None
-            o = ob.view() if ob is not None and ob.n == x.shape[0] and ob.buf.data_ptr() % 16 == 0 else torch.empty_like(x, memory_format=torch.contiguous_format)
+        outs, r0 = [_site_dst(out_blocks, k, x) for k, x in enumerate(xs)], 0
+        for j, x, o, t in zip(jobs, xs, outs, types):
             j.src, j.lds, j.dst, j.ldd, j.rows, j.type = _p(x), x.stride(0), _p(o), o.stride(0), x.shape[0], t
             j.weight, j.bias, j.stat = _p(weight[t]), _p(bias[t]), _p(stat[r0:])
             r0 += x.shape[0]
-            outs.append(o)
         _lib.check(L.kgw_layer_norm_relu_fwd(len(xs), jobs, c_logical, LNORM_EPS, _lib.stream_ptr()), 'kgw_layer_norm_relu_fwd')
         ctx.args = (types, c_logical, premasked)
         ctx.save_for_backward(weight, stat, *xs, *([] if premasked else outs))
@@ -2586,7 +2598,7 @@ class _LayerNormReLU(torch.autograd.Function):
         jobs = (_lib.KgwLNormBwdJob * len(live))()
         keep = []
         for j, k in zip(jobs, live):
-            g, x, o = _hdrop_rows(gs[k]), xs[k], outs[k]
+            g, x, o = _site_rows(gs[k]), xs[k], outs[k]
             dy = torch.empty_like(x, memory_format=torch.contiguous_format)
             keep.append(g)
             dys[k] = dy
@@ -2612,11 +2624,9 @@ def layer_norm_relu(outs, types, weight: torch.Tensor, bias: torch.Tensor, c_log
     their gradient by (out > 0) itself (gat_aggregate(relu_input=True)); otherwise the backward kernel does, from the saved out.
     One autograd node over all types: d weight / d bias come back whole -- a type whose output received no gradient, or that is
     not in ``types``, has ZERO rows there (not ``None``).  Returns the outputs, in order."""
-    outs = list(outs)
+    outs, types = _site_args(outs, types, distinct=True)
     if not outs:
         return []
-    types = tuple(int(t) for t in types)
-    assert len(outs) == len(types) == len(set(types)) <= 8 and all(o.dim() == 2 and o.shape[1] == KGW_C for o in outs)
     assert weight.shape == bias.shape and weight.dim() == 2 and weight.shape[1] == KGW_C and max(types) < weight.shape[0] <= 8
     assert weight.is_contiguous() and bias.is_contiguous() and weight.dtype == bias.dtype == torch.float32
     if not 1 <= int(c_logical) <= KGW_C:
@@ -2662,15 +2672,12 @@ class _RootLinear(torch.autograd.Function):
     def forward(ctx, types, out_blocks, premasked, relu, x_premasked, weight, *yx):
         ctx.set_materialize_grads(False)
         n = len(types)
-        ys, xs = [_hdrop_rows(y) for y in yx[:n]], [_hdrop_rows(x) for x in yx[n:]]
+        ys, xs = [_site_rows(y) for y in yx[:n]], [_site_rows(x) for x in yx[n:]]
         jobs = (_lib.KgwRootJob * n)()
-        outs = []
-        for k, (j, y, x, t) in enumerate(zip(jobs, ys, xs, types)):
-            ob = out_blocks[k] if out_blocks is not None else None
-            o = ob.view() if ob is not None and ob.n == y.shape[0] and ob.buf.data_ptr() % 16 == 0 else torch.empty_like(y, memory_format=torch.contiguous_format)
+        outs = [_site_dst(out_blocks, k, y) for k, y in enumerate(ys)]
+        for j, y, x, o, t in zip(jobs, ys, xs, outs, types):
             j.x, j.ldx, j.y, j.ldy, j.dst, j.ldd = _p(x), x.stride(0), _p(y), y.stride(0), _p(o), o.stride(0)
             j.rows, j.type, j.W = y.shape[0], t, _p(weight[t])
-            outs.append(o)
         _lib.check(_lib.lib().kgw_root_linear_fwd(n, jobs, int(relu), _lib.stream_ptr()), 'kgw_root_linear_fwd')
         masks = relu and not premasked
         ctx.args = (types, masks, x_premasked)
@@ -2691,7 +2698,7 @@ class _RootLinear(torch.autograd.Function):
         jobs = (_lib.KgwRootBwdJob * len(live))()
         keep, pairs = [], []
         for j, k in zip(jobs, live):
-            g, x, o = _hdrop_rows(gs[k]), xs[k], outs[k]
+            g, x, o = _site_rows(gs[k]), xs[k], outs[k]
             dx = torch.empty_like(x, memory_format=torch.contiguous_format)
             gm = torch.empty_like(g, memory_format=torch.contiguous_format) if o is not None else g
             keep.append(g)
@@ -2717,12 +2724,11 @@ def root_linear(outs, types, xs, weight: torch.Tensor, out_blocks=None, premaske
     xs are ReLU outputs whose producer runs premasked (layers >= 2 of the fused and multi-head routes): d x_t comes out multiplied
     by (x_t > 0).  One autograd node over all types; d weight comes back whole, ZERO slices for types not in ``types`` or without
     rows (not ``None``)."""
-    outs, xs = list(outs), list(xs)
+    outs, types = _site_args(outs, types, distinct=True)
     if not outs:
         return []
-    types = tuple(int(t) for t in types)
-    assert len(outs) == len(xs) == len(types) == len(set(types)) <= 8
-    assert all(o.dim() == 2 and o.shape[1] == KGW_C and x.shape == o.shape for o, x in zip(outs, xs))
+    xs = list(xs)
+    assert len(xs) == len(outs) and all(x.shape == o.shape for o, x in zip(outs, xs))
     assert weight.dim() == 3 and weight.shape[1:] == (KGW_C, KGW_C) and max(types) < weight.shape[0] <= 8
     assert weight.is_contiguous() and weight.dtype == torch.float32 and weight.data_ptr() % 16 == 0
     if not _lib.has_root_weight():

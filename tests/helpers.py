@@ -62,6 +62,24 @@ def assert_close(a, b, rtol, atol, what='', rel_to_max=1e-5):
                            f'{float(err.max()):.3e}, max |ref| {float(b.abs().max()):.3e}')
 
 
+def kernel_launches(fn):
+    """Names of the kernels ``fn()`` launches, in the order they started (the profiler's device events; memcpy / memset dropped:
+    they are no kernels)."""
+    from torch.profiler import ProfilerActivity, profile
+    torch.cuda.synchronize()
+    with profile(activities=[ProfilerActivity.CUDA]) as prof:
+        fn()
+        torch.cuda.synchronize()
+    ev = sorted((e for e in prof.events() if e.device_type == torch.autograd.DeviceType.CUDA), key=lambda e: e.time_range.start)
+    return [e.name for e in ev if 'memcpy' not in e.name.lower() and 'memset' not in e.name.lower()]
+
+
+def launches_of_one_step(gs):
+    """``kernel_launches`` of one training step issued eagerly through the body the trainer ``gs`` (GraphTrainStep) captured."""
+    gs._sample_now(0, 0)
+    return kernel_launches(lambda: gs._step_body(0))
+
+
 def global_edge_set(batch, et):
     """Set of (global src, global dst) pairs of relation ``et`` in a sampled batch (multiset as sorted array)."""
     ei = batch.edge_index_dict[et].cpu().numpy()

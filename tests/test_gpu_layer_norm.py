@@ -21,7 +21,7 @@ import torch
 
 from tests import hidden_dropout_ref as HD
 from tests import layer_norm_ref as R
-from tests.helpers import assert_close, batch_cpu, grads_by_name, oracle_from_product, params_by_name
+from tests.helpers import assert_close, batch_cpu, grads_by_name, launches_of_one_step, oracle_from_product, params_by_name
 
 pytestmark = pytest.mark.gpu
 
@@ -455,16 +455,9 @@ def test_the_default_model_is_unchanged(small_kg):
 # trainer
 # ------------------------------------------------------------------------------------------------------------------------------
 def _launches_of_one_step(gs):
-    """Kernel launches of one training step issued eagerly through the body the trainer captured (the profiler hook of
-    tools/bench_layer_norm.py): (all, [names of the k_layer_norm_* among them])."""
-    from torch.profiler import ProfilerActivity, profile
-    gs._sample_now(0, 0)
-    torch.cuda.synchronize()
-    with profile(activities=[ProfilerActivity.CUDA]) as prof:
-        gs._step_body(0)
-        torch.cuda.synchronize()
-    ev = [e for e in prof.events() if e.device_type == torch.autograd.DeviceType.CUDA]
-    names = [e.name for e in ev if 'memcpy' not in e.name.lower() and 'memset' not in e.name.lower()]
+    """Kernel launches of one training step issued eagerly through the body the trainer captured (tests/helpers.py):
+    (all, [names of the k_layer_norm_* among them])."""
+    names = launches_of_one_step(gs)
     return len(names), sorted(re.search(r'k_layer_norm\w*', n).group(0) for n in names if 'k_layer_norm' in n)
 
 

@@ -18,7 +18,7 @@ import torch
 
 from tests import hidden_dropout_ref as HD
 from tests import root_weight_ref as R
-from tests.helpers import assert_close, batch_cpu, grads_by_name, oracle_from_product, params_by_name
+from tests.helpers import assert_close, batch_cpu, grads_by_name, launches_of_one_step, oracle_from_product, params_by_name
 from tests.test_gpu_aggregate_parity import layer_edges
 from tests.test_gpu_mlp2_kernels import ORDER, U, _chain_ceiling
 
@@ -555,16 +555,9 @@ def test_root_with_hidden_dropout_alone(small_kg):
 # trainer
 # ------------------------------------------------------------------------------------------------------------------------------
 def _launches_of_one_step(gs):
-    """Kernel launches of one training step issued eagerly through the body the trainer captured (the profiler hook of
-    tests/test_gpu_layer_norm.py): (all, sorted names of the k_root_linear* among them, number of k_tn_gemm* / k_tn_reduce*)."""
-    from torch.profiler import ProfilerActivity, profile
-    gs._sample_now(0, 0)
-    torch.cuda.synchronize()
-    with profile(activities=[ProfilerActivity.CUDA]) as prof:
-        gs._step_body(0)
-        torch.cuda.synchronize()
-    ev = [e for e in prof.events() if e.device_type == torch.autograd.DeviceType.CUDA]
-    names = [e.name for e in ev if 'memcpy' not in e.name.lower() and 'memset' not in e.name.lower()]
+    """Kernel launches of one training step issued eagerly through the body the trainer captured (tests/helpers.py):
+    (all, sorted names of the k_root_linear* among them, number of k_tn_gemm* / k_tn_reduce*)."""
+    names = launches_of_one_step(gs)
     root = sorted(re.search(r'k_root_linear<\w+>|k_root_linear\w*', n).group(0) for n in names if 'k_root_linear' in n)
     return len(names), root, sum(1 for n in names if 'k_tn_gemm' in n or 'k_tn_reduce' in n), names
 
