@@ -10,8 +10,8 @@
  * enqueues work on `stream` (a hipStream_t) and returns a status:
  *      0 = ok, <0 = argument error (KGW_E_*), >0 = hipError_t from a launch.
  * No C++ exceptions cross this boundary.  Functions are re-entrant (no global mutable state).  What the library keeps per
- * process is immutable after first use: a handful of launch-shape constants read ONCE from KGW_* environment variables (timing
- * experiments: KGW_AGG_GRID_CAP, KGW_G3_NW, KGW_SPLITK_BLOCKS, ... -- unset in normal use) and the one-time
+ * process is immutable after first use: a handful of routing constants read ONCE from KGW_* environment variables (A/B
+ * experiments: KGW_TN_SPLIT, KGW_TN_DIRECT_ROWS, KGW_MLP2_SPLIT, KGW_TS_MIN_SHIFT -- unset in normal use) and the one-time
  * hipFuncSetAttribute calls of the kernels that take more than 64 KB of LDS.
  *
  * Vocabulary (the reference's domain): node types, relations (= edge types), seeds, hops,
@@ -596,7 +596,8 @@ int kgw_accumulate_stats_tick(const KgwBatchMeta* meta_dev, int32_t n_layers, in
 /* A sampled batch kept for later epochs.  The reference's training loader has a fixed batch order (NeighborLoader without
  * shuffle, kgwas/kgwas.py:93-101), so epoch >= 2 asks the sampler for exactly the structures of epoch 1.  kgw_segments_copy moves
  * up to KGW_SEGCOPY_MAX device segments (the arrays of a KgwBatchBuf the training step reads) to slot *slot_index of a resident
- * cache (to_slot != 0) or back, in ONE launch; the slot index is read on the DEVICE, so the launch is captured once.  Pointers,
+ * cache (to_slot != 0) or back, in ONE launch; the slot index is read on the DEVICE, so one record serves every batch (the
+ * trainer issues the launch eagerly on the sampler's stream, after an asynchronous copy of the index).  Pointers,
  * slot offsets and the stride are 16-byte aligned; units = 16-byte units of the segment.                                      */
 #define KGW_SEGCOPY_MAX 40
 typedef struct KgwSegCopy {

@@ -832,10 +832,11 @@ __global__ void __launch_bounds__(512, 1) k_mlp2_fwd3(Mlp2Args a) {
 // ------------------------------------------------------------------------------------------------------
 // kgw_mlp2w_fwd: the same two hidden layers for a 128-wide input on FEW rows (the three GO node types of a batch share
 // go_feat_mlp, kgwas/model.py:58-60: ~7 k rows), rows gathered from up to four resident feature matrices -- one launch
-// instead of gather + Linear + Linear.  A wavefront takes (32-row tile, half of the OUTPUT columns): it computes all of
-// h1 for its rows (256 MFMAs, first-layer operands from LDS) and its half of h2 (128 MFMAs) -- the duplicated first
-// product buys twice the wavefronts for a launch that has ~220 tiles for 1024 SIMDs.  Hidden state handed over in
-// registers as in k_mlp2_fwd; the column-half-0 wavefront also writes the gathered rows and h1 for the backward.
+// instead of gather + Linear + Linear.  A wavefront takes (32-row tile, half of the columns): it computes ITS two column
+// tiles of h1 (128 MFMAs, first-layer operands from LDS), gets the other two from its partner wavefront through LDS -- the
+// exchange reuses the region that held W1 (W1l) and relies on the two __syncthreads() around it -- and then computes its
+// half of h2 (128 MFMAs): twice the wavefronts for a launch that has ~220 tiles for 1024 SIMDs, no product computed twice.
+// Each half writes its own 64 columns of h1 for the backward; the column-half-0 wavefront also writes the gathered rows.
 // ------------------------------------------------------------------------------------------------------
 struct Mlp2wArgs {
     const float* src[4]; const int32_t* ids[4]; int64_t row0[5];     // job j covers rows [row0[j], row0[j+1])

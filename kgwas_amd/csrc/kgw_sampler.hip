@@ -1315,7 +1315,7 @@ extern "C" int kgw_accumulate_stats(const KgwBatchMeta* meta_dev, int32_t n_laye
 // ---- a sampled batch kept for later epochs (the loader's batch order is fixed: kgwas/kgwas.py:93-101 builds it without shuffle) ----
 // One launch moves every array of a batch the training step reads -- KgwSegCopy: up to KGW_SEGCOPY_MAX (pointer, 16-byte units,
 // offset in the slot) segments -- into slot ``*slot_index`` of a resident cache, or back.  The slot index is DEVICE data, so the
-// launch is captured once and replayed for any batch.  HBM-bound: ~20 MB each way per 512-seed batch of the benchmark graph.
+// same record serves any batch (launched eagerly by the trainer, not captured).  HBM-bound: ~20 MB each way per 512-seed batch of the benchmark graph.
 namespace {
 __global__ void __launch_bounds__(KGW_BLK) k_segments_copy(KgwSegCopy P) {
     uint8_t* slot = P.slots + *P.slot_index * P.slot_stride;

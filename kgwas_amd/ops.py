@@ -218,11 +218,9 @@ class GradSink:
         kernel's (the caller launches it itself)."""
         rows, M = dY.shape
         N = X.shape[1]
-        # (a tall product -- the SNP MLP's 122 k rows: 512 blocks that fill the chip for 43 us -- is launched where it is: grouped with
-        #  it the short ones queue behind its blocks, measured in round 4)
-        if not (_DEFER_PRODUCTS and 0 < rows < 32768 and X.shape[0] == rows and dY.dtype == torch.float32 and X.dtype == torch.float32 and
-                dY.stride(1) == 1 and X.stride(1) == 1 and M % 2 == 0 and N % 2 == 0 and M >= 64 and N >= 64 and dY.stride(0) % 2 == 0 and
-                X.stride(0) % 2 == 0 and dY.data_ptr() % 8 == 0 and X.data_ptr() % 8 == 0):
+        # (beside the shared rule, the row window: a tall product -- the SNP MLP's 122 k rows: 512 blocks that fill the chip for 43 us --
+        #  is launched where it is: grouped with it the short ones queue behind its blocks, measured in round 4)
+        if not (_DEFER_PRODUCTS and rows < 32768 and _tn_multi_ok(dY, X)):
             return None
         dW = torch.empty(M, N, device=dY.device)
         db = torch.empty(M, device=dY.device)
@@ -232,20 +230,10 @@ class GradSink:
         return dW, db
 
     def _tn_jobs(self, chunk):
-        L = _lib.lib()
         jobs = (_lib.KgwTnJob * max(len(chunk), 1))()
         src = (_lib.KgwGradSrc * max(2 * len(chunk), 1))()
-        keep = []
-        for j, (dY, X, dW_ptr, db_ptr, _sw, _sb, rows_dev) in zip(jobs, chunk):
-            rows, M = dY.shape
-            N = X.shape[1]
-            nws = int(L.kgw_tn_gemm_workspace_floats(rows, M, N))
-            ws = torch.empty(nws, device=dY.device)
-            keep.append(ws)
-            j.A, j.lda, j.B, j.ldb, j.rows = _p(dY), dY.stride(0), _p(X), X.stride(0), rows
-            j.C, j.ldc, j.colsum_a, j.colsum_ld = dW_ptr, N, db_ptr, M
-            j.workspace, j.workspace_floats, j.rows_dev = _p(ws), nws, _p(rows_dev)
-            j.M, j.N, j.c_transposed, j.colsum_repeat = M, N, 0, 1
+        keep = [_tn_job(j, dY, X, dW_ptr, X.shape[1], db_ptr, dY.shape[1], rows_dev=rows_dev)
+                for j, (dY, X, dW_ptr, db_ptr, _sw, _sb, rows_dev) in zip(jobs, chunk)]
         return jobs, src, keep
 
     def take_reduce(self):
@@ -878,6 +866,50 @@ def edge_alpha(batch, layer: int, stat: torch.Tensor, e_edge: torch.Tensor, temp
 _TN_MIN_ROWS = 1024       # below this a library GEMM is fine
 
 
+def _tn_job(j, A, B, C_ptr, ldc, colsum_ptr, colsum_ld, *, c_transposed=False, colsum_repeat=1, rows_dev=None):
+    """Every field of the KgwTnJob ``j`` for C = A^T B (C^T with ``c_transposed``) and the column sums of A, and the product's
+    workspace, which is returned for the caller's keep-alive list.  The outputs are ADDRESSES (``colsum_ptr`` 0: no column sums):
+    GradSink._tn_jobs holds no tensor for them -- a second reference to a gradient tensor makes autograd copy it."""
+    rows, M = A.shape
+    N = B.shape[1]
+    nws = int(_lib.lib().kgw_tn_gemm_workspace_floats(rows, M, N))
+    ws = torch.empty(nws, device=A.device)
+    j.A, j.lda, j.B, j.ldb, j.rows = _p(A), A.stride(0), _p(B), B.stride(0), rows
+    j.C, j.ldc, j.colsum_a, j.colsum_ld = C_ptr, ldc, colsum_ptr, colsum_ld
+    j.workspace, j.workspace_floats, j.rows_dev = _p(ws), nws, _p(rows_dev)
+    j.M, j.N, j.c_transposed, j.colsum_repeat = M, N, int(c_transposed), colsum_repeat
+    return ws
+
+
+def _tn_multi_ok(A: torch.Tensor, B: torch.Tensor, narrow: bool = False) -> bool:
+    """Whether the grouped split-K kernel (kgw_tn_gemm_multi and the launches built on it) takes A^T B: what it demands of a job --
+    even M, N, lda, ldb, 8-byte aligned operands (float2 loads) -- and what every site asks besides: fp32, inner stride 1, the same
+    non-zero row count, and M, N >= 64 (where kgw_tn_gemm_ex runs the same <2,2> tiling: the same bits grouped or alone).  A site's
+    further conditions stand beside its call.  ``narrow``: without the width clause -- ``weight_grads`` alone, whose callers DO reach
+    it with narrow operands (_MLP2.backward's general path on the 20-wide SNP features at 1 024 .. 16 383 rows outside a GradSink:
+    grouped on <2,2> where kgw_tn_gemm_ex runs <2,1>); that route stays.  The dtype clause weight_grads lacked is unreachable
+    there: its callers, the MLP backward passes, hand it ``linear`` outputs and their gradients, fp32 throughout the package."""
+    return (A.dtype == torch.float32 and B.dtype == torch.float32 and A.stride(1) == 1 and B.stride(1) == 1
+            and A.shape[0] == B.shape[0] and A.shape[0] > 0 and A.shape[1] % 2 == 0 and B.shape[1] % 2 == 0
+            and (narrow or (A.shape[1] >= 64 and B.shape[1] >= 64)) and A.stride(0) % 2 == 0 and B.stride(0) % 2 == 0
+            and A.data_ptr() % 8 == 0 and B.data_ptr() % 8 == 0)
+
+
+def _hand_off(sink, grads, launch):
+    """The producer / optimiser fork of a product with a two-launch form.  ``launch(src)`` issues it: ``src`` None -- the finishing
+    entry (``sink`` None: nobody takes the partial sums); else the entry that stops after the first launch and describes the partial
+    sums of ``grads`` = [(gradient tensor or None, workspace)] in src[k], which go to the sink (GradSink.add).  ``launch`` returns
+    False when it launched nothing (the caller takes another route): no records then, and False from here."""
+    src = (_lib.KgwGradSrc * len(grads))() if sink is not None else None
+    if launch(src) is False:
+        return False
+    if sink is not None:
+        for (g, ws), rec in zip(grads, src):
+            if g is not None:
+                sink.add(g, rec, ws)
+    return True
+
+
 def tn_gemm(A: torch.Tensor, B: torch.Tensor, colsum: bool = False, out: torch.Tensor = None,
             transpose_out: bool = False, colsum_out: torch.Tensor = None, rows_dev: torch.Tensor = None, defer: bool = False):
     """C = A^T @ B for tall row-major A [rows, M], B [rows, N] (fp32, inner stride 1); optionally also the
@@ -911,28 +943,24 @@ def tn_gemm(A: torch.Tensor, B: torch.Tensor, colsum: bool = False, out: torch.T
     L = _lib.lib()
     nws = int(L.kgw_tn_gemm_workspace_floats(rows, M, N))
     ws = torch.empty(nws, device=dev)
-    sink = GRAD_SINK
-    if defer and sink is not None and colsum_out is None and out.is_contiguous():
-        # ``defer``: the caller hands (out, cs) to autograd as the gradients of two parameters and nothing else reads them before
-        # the optimiser: the row blocks' partial sums are added inside its launch (GradSink)
-        src = (_lib.KgwGradSrc * 2)()
+    # ``defer``: the caller hands (out, cs) to autograd as the gradients of two parameters and nothing else reads them before
+    # the optimiser: the row blocks' partial sums are added inside its launch (GradSink)
+    sink = GRAD_SINK if (defer and colsum_out is None and out.is_contiguous()) else None
+    head = (_p(A), A.stride(0), M, _p(B), B.stride(0), N, rows, _p(out), out.stride(0), 1 if transpose_out else 0, _p(cs))
+    tail = (_p(ws), nws, _p(rows_dev))
+
+    def launch(src):
+        if src is None:
+            _lib.check(L.kgw_tn_gemm_ex(*head, rep, cs_ld, *tail, _lib.stream_ptr()), 'kgw_tn_gemm_ex')
+            return
         ride = sink.take_reduce()
         if ride is not None:           # (a product group's pending second launch rides in this product's: GradSink.pending_reduce)
-            _lib.check(L.kgw_tn_gemm_partial_ride(_p(A), A.stride(0), M, _p(B), B.stride(0), N, rows, _p(out), out.stride(0),
-                                                  1 if transpose_out else 0, _p(cs), _p(ws), nws, _p(rows_dev), src, C.byref(ride[0]),
-                                                  _lib.stream_ptr()), 'kgw_tn_gemm_partial_ride')
+            _lib.check(L.kgw_tn_gemm_partial_ride(*head, *tail, src, C.byref(ride[0]), _lib.stream_ptr()), 'kgw_tn_gemm_partial_ride')
             sink.reduces_ridden += 1
         else:
-            _lib.check(L.kgw_tn_gemm_partial(_p(A), A.stride(0), M, _p(B), B.stride(0), N, rows, _p(out), out.stride(0),
-                                             1 if transpose_out else 0, _p(cs), _p(ws), nws, _p(rows_dev), src, _lib.stream_ptr()),
-                       'kgw_tn_gemm_partial')
-        sink.add(out, src[0], ws)
-        if cs is not None:
-            sink.add(cs, src[1], ws)
-        return (out, cs) if colsum else out
-    _lib.check(L.kgw_tn_gemm_ex(_p(A), A.stride(0), M, _p(B), B.stride(0), N, rows, _p(out), out.stride(0),
-                                1 if transpose_out else 0, _p(cs), rep, cs_ld, _p(ws), nws, _p(rows_dev), _lib.stream_ptr()),
-               'kgw_tn_gemm_ex')
+            _lib.check(L.kgw_tn_gemm_partial(*head, *tail, src, _lib.stream_ptr()), 'kgw_tn_gemm_partial')
+
+    _hand_off(sink, [(out, ws), (cs, ws)], launch)
     return (out, cs) if (colsum or colsum_out is not None) else out
 
 
@@ -942,26 +970,14 @@ def _tn_gemm_group(jobs) -> bool:
     if not (2 <= len(jobs) <= 4):
         return False
     for A, B, out, cs in jobs:
-        if not (A.dtype == torch.float32 and B.dtype == torch.float32 and A.stride(1) == 1 and B.stride(1) == 1 and out.stride(1) == 1 and
-                cs.stride(1) == 1 and A.shape[0] == B.shape[0] and A.shape[0] > 0 and A.shape[1] % 2 == 0 and B.shape[1] % 2 == 0 and
-                A.shape[1] >= 64 and B.shape[1] >= 64 and A.stride(0) % 2 == 0 and B.stride(0) % 2 == 0 and A.data_ptr() % 8 == 0 and
-                B.data_ptr() % 8 == 0 and out.shape == (B.shape[1], A.shape[1]) and cs.shape[1] == A.shape[1]):
+        # (beside the shared rule: the outputs are row-major views of the transposed product and of q copies of the column sums)
+        if not (_tn_multi_ok(A, B) and out.stride(1) == 1 and cs.stride(1) == 1 and out.shape == (B.shape[1], A.shape[1]) and
+                cs.shape[1] == A.shape[1]):
             return False
-    L = _lib.lib()
     arr = (_lib.KgwTnJob * len(jobs))()
-    keep = []
-    for q, (A, B, out, cs) in enumerate(jobs):
-        rows, M = A.shape
-        N = B.shape[1]
-        nws = int(L.kgw_tn_gemm_workspace_floats(rows, M, N))
-        ws = torch.empty(nws, device=A.device)
-        keep.append(ws)
-        j = arr[q]
-        j.A, j.lda, j.B, j.ldb, j.rows = _p(A), A.stride(0), _p(B), B.stride(0), rows
-        j.C, j.ldc, j.colsum_a, j.colsum_ld = _p(out), out.stride(0), _p(cs), cs.stride(0)
-        j.workspace, j.workspace_floats, j.rows_dev = _p(ws), nws, None
-        j.M, j.N, j.c_transposed, j.colsum_repeat = M, N, 1, cs.shape[0]
-    _lib.check(L.kgw_tn_gemm_multi(len(jobs), arr, _lib.stream_ptr()), 'kgw_tn_gemm_multi')
+    keep = [_tn_job(j, A, B, _p(out), out.stride(0), _p(cs), cs.stride(0), c_transposed=True, colsum_repeat=cs.shape[0])
+            for j, (A, B, out, cs) in zip(arr, jobs)]
+    _lib.check(_lib.lib().kgw_tn_gemm_multi(len(jobs), arr, _lib.stream_ptr()), 'kgw_tn_gemm_multi')
     return True
 
 
@@ -970,40 +986,29 @@ def weight_grads(pairs, rows_dev: torch.Tensor = None):
     TOGETHER (the Linears of one MLP at the end of its backward): one kgw_tn_gemm_multi launch pair for all of them
     instead of one pair each; falls back to per-product calls where the grouped kernel does not apply."""
     pairs = [(dY if dY.stride(1) == 1 else dY.contiguous(), X if X.stride(1) == 1 else X.contiguous()) for dY, X in pairs]
-    if GRAD_SINK is not None and _DEFER_PRODUCTS:          # (not launched now: GradSink.defer_product)
-        return [linear_weight_grad(dY, X, rows_dev=rows_dev) for dY, X in pairs]
-    # (tall products fill the chip on their own: grouping only pays while a product is launch-bound)
-    ok = 1 < len(pairs) <= 4 and all(_TN_MIN_ROWS <= X.shape[0] < 32768 and X.shape[1] <= 1024 and X.shape[1] % 2 == 0 and dY.shape[1] % 2 == 0 and
-                                     X.stride(0) % 2 == 0 and dY.stride(0) % 2 == 0 and X.data_ptr() % 8 == 0 and dY.data_ptr() % 8 == 0
-                                     for dY, X in pairs)
+    # (with a sink that defers them the products are not launched now: linear_weight_grad -> GradSink.defer_product.  Beside the
+    #  shared rule -- without its width clause, see _tn_multi_ok -- the rows and widths at which grouping pays: below _TN_MIN_ROWS
+    #  linear_weight_grad may choose the library; tall or wide products fill the chip on their own)
+    ok = not (GRAD_SINK is not None and _DEFER_PRODUCTS) and 1 < len(pairs) <= 4 and all(
+        _TN_MIN_ROWS <= X.shape[0] < 32768 and X.shape[1] <= 1024 and _tn_multi_ok(dY, X, narrow=True) for dY, X in pairs)
     if not ok:
         return [linear_weight_grad(dY, X, rows_dev=rows_dev) for dY, X in pairs]
     L = _lib.lib()
     jobs = (_lib.KgwTnJob * len(pairs))()
     outs, keep = [], []
-    for q, (dY, X) in enumerate(pairs):
-        rows, M = dY.shape
-        N = X.shape[1]
-        dW = torch.empty(M, N, device=dY.device)
-        db = torch.empty(M, device=dY.device)
-        nws = int(L.kgw_tn_gemm_workspace_floats(rows, M, N))
-        ws = torch.empty(nws, device=dY.device)
-        keep.append(ws)
-        j = jobs[q]
-        j.A, j.lda, j.B, j.ldb, j.rows = _p(dY), dY.stride(0), _p(X), X.stride(0), rows
-        j.C, j.ldc, j.colsum_a, j.colsum_ld = _p(dW), N, _p(db), M
-        j.workspace, j.workspace_floats, j.rows_dev = _p(ws), nws, _p(rows_dev)
-        j.M, j.N, j.c_transposed, j.colsum_repeat = M, N, 0, 1
+    for j, (dY, X) in zip(jobs, pairs):
+        dW = torch.empty(dY.shape[1], X.shape[1], device=dY.device)
+        db = torch.empty(dY.shape[1], device=dY.device)
+        keep.append(_tn_job(j, dY, X, _p(dW), X.shape[1], _p(db), dY.shape[1], rows_dev=rows_dev))
         outs.append((dW, db))
-    sink = GRAD_SINK
-    if sink is not None:            # (every caller returns these to autograd as parameter gradients: see tn_gemm(defer=True))
-        src = (_lib.KgwGradSrc * (2 * len(pairs)))()
-        _lib.check(L.kgw_tn_gemm_multi_partial(len(pairs), jobs, src, _lib.stream_ptr()), 'kgw_tn_gemm_multi_partial')
-        for q, (dW, db) in enumerate(outs):
-            sink.add(dW, src[2 * q], keep[q])
-            sink.add(db, src[2 * q + 1], keep[q])
-        return outs
-    _lib.check(L.kgw_tn_gemm_multi(len(pairs), jobs, _lib.stream_ptr()), 'kgw_tn_gemm_multi')
+
+    def launch(src):       # (with a sink every caller returns these to autograd as parameter gradients: see tn_gemm(defer=True))
+        if src is None:
+            _lib.check(L.kgw_tn_gemm_multi(len(pairs), jobs, _lib.stream_ptr()), 'kgw_tn_gemm_multi')
+        else:
+            _lib.check(L.kgw_tn_gemm_multi_partial(len(pairs), jobs, src, _lib.stream_ptr()), 'kgw_tn_gemm_multi_partial')
+
+    _hand_off(GRAD_SINK, [(g, ws) for pair, ws in zip(outs, keep) for g in pair], launch)
     return outs
 
 
@@ -1246,10 +1251,8 @@ def gemm3(A: torch.Tensor, packed: torch.Tensor, bias=None, relu: bool = False, 
     if defer and sink is not None and transpose_out and M % 32 == 0 and out.is_contiguous() and bias is None and not relu and row_map is None:
         # ``defer``: ``out`` goes to autograd as a parameter's gradient and to nothing else: the K ranges are added tile by tile
         # inside the optimiser's launch (GradSink, KGW_GRAD_G3T)
-        src = _lib.KgwGradSrc()
-        _lib.check(L.kgw_gemm3_partial(_p(A), lda, M, K, _p(packed), _p(ws), nws, _p(out), out.stride(0), C.byref(src), _lib.stream_ptr()),
-                   'kgw_gemm3_partial')
-        sink.add(out, src, ws)
+        _hand_off(sink, [(out, ws)], lambda src: _lib.check(L.kgw_gemm3_partial(
+            _p(A), lda, M, K, _p(packed), _p(ws), nws, _p(out), out.stride(0), src, _lib.stream_ptr()), 'kgw_gemm3_partial'))
         return out
     args = (_p(A), lda, M, K, _p(packed), _p(ws), nws, _p(bias), 1 if relu else 0, _p(out), out.stride(0),
             1 if transpose_out else 0, _p(row_map), _p(out_rows), out_rows.stride(0) if out_rows is not None else 0,
@@ -1641,6 +1644,45 @@ class _MLP3(torch.autograd.Function):
         return None, dW1, db1, dW2, db2, dW3, db3, None, None
 
 
+def _mlp2_bwd_first(dh2, W2, h1, *, x=None, rows_dev=None, in_ids=None, dz=None, packed=None):
+    """(d W1 or None, d b1) of a two-layer MLP's first Linear: dh1 = (dh2 @ W2) * (h1 > 0) formed tile by tile in ONE kernel and
+      ``x`` [rows, K1]: multiplied into d W1 [128, K1] on the spot, neither written nor re-read (kgw_mlp2_bwd_first);
+      ``in_ids`` [N] int32 (row of dh2 for every row of h1, -1: none) + ``dz`` [N, 128]: written there for the caller's d W1 product;
+      ``in_ids`` + ``packed``: written as that product's kgw_gemm3 B operand image instead (kgw_mlp2_bwd_first_packed) -- None when
+          the kernel does not take this form (KGW_E_UNSUPPORTED, nothing launched): call again with ``dz``.
+    Inside a GradSink the second launch (the fold of the blocks' partial sums) is the optimiser's (_hand_off)."""
+    L = _lib.lib()
+    rows, K1 = h1.shape[0], (x.shape[1] if x is not None else 0)
+    dW1 = torch.empty(KGW_C, K1, device=h1.device) if x is not None else None
+    db1 = torch.empty(KGW_C, device=h1.device)
+    nws = int(L.kgw_mlp2_bwd_first_workspace_floats(rows))
+    ws = torch.empty(nws, device=h1.device)
+    head = (_p(dh2), dh2.stride(0), _p(W2), W2.stride(0), _p(h1), h1.stride(0), _p(x), x.stride(0) if x is not None else 0, K1, rows)
+    tail = (_p(rows_dev), _p(dW1), K1, _p(db1), _p(ws), nws, _p(in_ids), _p(dz), dz.stride(0) if dz is not None else 0)
+
+    def launch(src):
+        if packed is not None:
+            rc = L.kgw_mlp2_bwd_first_packed(*head, None, 0, _p(db1), _p(ws), nws, _p(in_ids), None, 0, _p(packed), int(L.kgw_gemm3_flip()),
+                                             src, _lib.stream_ptr())
+            if rc == _lib.KGW_E_UNSUPPORTED:
+                return False
+            _lib.check(rc, 'kgw_mlp2_bwd_first_packed')
+        elif src is not None:
+            _lib.check(L.kgw_mlp2_bwd_first_partial(*head, *tail, src, _lib.stream_ptr()), 'kgw_mlp2_bwd_first_partial')
+        else:
+            _lib.check(L.kgw_mlp2_bwd_first(*head, *tail, _lib.stream_ptr()), 'kgw_mlp2_bwd_first')
+
+    return (dW1, db1) if _hand_off(GRAD_SINK, [(dW1, ws), (db1, ws)], launch) else None
+
+
+def _mlp2_general_bwd(dh2, W2, h1, x, rows_dev=None):
+    """(d W1, d b1, d W2, d b2) of a two-layer MLP from the gradient of its output (already multiplied by (h2 > 0)), no input
+    gradient: one dX launch with the first layer's ReLU mask in its epilogue, then both weight-gradient products together."""
+    dh1 = linear(dh2, W2, mask=h1, w_kn=True, rows_dev=rows_dev)     # (dh2 @ W2) * (h1 > 0)
+    (dW2, db2), (dW1, db1) = weight_grads([(dh2, h1), (dh1, x)], rows_dev=rows_dev)
+    return dW1, db1, dW2, db2
+
+
 class _MLP2(torch.autograd.Function):
     """h2 = relu(FC_hidden2(relu(FC_hidden(x)))) -- SimpleMLP without its last Linear (kgwas/model.py:18-20), for a
     feature matrix that needs no gradient.  FC_output is folded into the layer-1 relation parameters (fold_fc_output_hip),
@@ -1689,27 +1731,10 @@ class _MLP2(torch.autograd.Function):
                 and dh2.data_ptr() % 16 == 0 and h1.data_ptr() % 16 == 0 and W2.data_ptr() % 16 == 0):
             # narrow first layer, no input gradient: dh1 = (dh2 @ W2) * (h1 > 0) is consumed tile by tile by the d W1 / d b1
             # product inside ONE kernel (kgw_mlp2_bwd_first) -- neither written nor re-read
-            L = _lib.lib()
-            dW1 = torch.empty(KGW_C, K1, device=x.device)
-            db1 = torch.empty(KGW_C, device=x.device)
-            nws = int(L.kgw_mlp2_bwd_first_workspace_floats(rows))
-            ws = torch.empty(nws, device=x.device)
-            sink = GRAD_SINK
-            if sink is not None:        # the blocks' partial d W1 / d b1 are added inside the optimiser's launch (GradSink)
-                src = (_lib.KgwGradSrc * 2)()
-                _lib.check(L.kgw_mlp2_bwd_first_partial(_p(dh2), dh2.stride(0), _p(W2), W2.stride(0), _p(h1), h1.stride(0), _p(x), x.stride(0),
-                                                        K1, rows, _p(rd), _p(dW1), K1, _p(db1), _p(ws), nws, None, None, 0, src,
-                                                        _lib.stream_ptr()), 'kgw_mlp2_bwd_first_partial')
-                sink.add(dW1, src[0], ws)
-                sink.add(db1, src[1], ws)
-            else:
-                _lib.check(L.kgw_mlp2_bwd_first(_p(dh2), dh2.stride(0), _p(W2), W2.stride(0), _p(h1), h1.stride(0), _p(x), x.stride(0), K1,
-                                                rows, _p(rd), _p(dW1), K1, _p(db1), _p(ws), nws, None, None, 0, _lib.stream_ptr()), 'kgw_mlp2_bwd_first')
+            dW1, db1 = _mlp2_bwd_first(dh2, W2, h1, x=x, rows_dev=rd)
             dW2, db2 = linear_weight_grad(dh2, h1, rows_dev=rd)
             return None, dW1, db1, dW2, db2, None, None, None
-        dh1 = linear(dh2, W2, mask=h1, w_kn=True, rows_dev=rd)   # (dh2 @ W2) * (h1 > 0)
-        (dW2, db2), (dW1, db1) = weight_grads([(dh2, h1), (dh1, x)], rows_dev=rd)
-        return None, dW1, db1, dW2, db2, None, None, None
+        return (None,) + _mlp2_general_bwd(dh2, W2, h1, x, rd) + (None, None, None)
 
 
 def mlp2(x, W1, b1, W2, b2, out=None, rows_dev=None, ids=None):
@@ -1749,10 +1774,7 @@ class _MLP2Gathered(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dh2):
         x, h1, W2 = ctx.saved_tensors
-        dh2 = dh2.contiguous()
-        dh1 = linear(dh2, W2, mask=h1, w_kn=True)       # (dh2 @ W2) * (h1 > 0)
-        (dW2, db2), (dW1, db1) = weight_grads([(dh2, h1), (dh1, x)])
-        return (dW1, db1, dW2, db2, None) + (None,) * (len(ctx.needs_input_grad) - 5)
+        return _mlp2_general_bwd(dh2.contiguous(), W2, h1, x) + (None,) * (len(ctx.needs_input_grad) - 4)
 
 
 def mlp2_gathered(jobs, W1, b1, W2, b2, out=None):
@@ -1815,6 +1837,23 @@ class _LinearReLU(torch.autograd.Function):
         return dx, dW, db, None
 
 
+def _resident_first_rows(ctx, X, W, b, ids, g2l, rows_real=None):
+    """(h, rows ``ids`` of h) for h = relu(X W^T + b) over a RESIDENT feature matrix X -- the forward of the resident first layer;
+    ``ctx.shard`` is set to the GeneLayerShard the layer runs on (or None).  The rows past the batch's real node count (static
+    capacity of a captured step) are written by nobody on the fused route and must be zero -- 0 x garbage must stay 0 in the weight
+    gradients downstream: a zero fill, or, with ``rows_real`` (their count on the device), the product's range-sum launch zeroes
+    exactly those rows itself -- no fill launch over the whole block."""
+    n = int(ids.numel())
+    ok = _resident_ok(X, W)
+    ctx.shard = active_gene_shard(ctx, 1, X, W, b) if ok else None
+    in_kernel = rows_real is not None and n > 0 and ctx.shard is None and ok
+    out = torch.zeros(n, KGW_C, device=X.device) if (ok and not in_kernel) else torch.empty(n, KGW_C, device=X.device)
+    h, done = resident_first_linear(X, W, b, g2l, out, ctx.shard, rows_real if in_kernel else None)
+    if n and not done:
+        _lib.check(_lib.lib().kgw_gather_rows(_p(h), _p(ids), n, h.shape[1], _p(out), _lib.stream_ptr()), 'kgw_gather_rows')
+    return h, out
+
+
 class _ResidentLinearReLURows(torch.autograd.Function):
     """rows ``ids`` of relu(X W^T + b) where X is a RESIDENT feature matrix (the 5120 / 57742-wide gene features): the
     product runs on all of X (kgw_gemm3; small or unaligned shapes: the tuned library GEMM) and the batch takes its rows -- no x[n_id]
@@ -1824,14 +1863,7 @@ class _ResidentLinearReLURows(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, X, W, b, ids, g2l):
-        n = int(ids.numel())
-        # zeros: the rows past the batch's real node count (static capacity of a captured step) are written by nobody on the
-        # fused route, and 0 x garbage must stay 0 in the weight gradients downstream
-        out = torch.zeros(n, KGW_C, device=X.device) if _resident_ok(X, W) else torch.empty(n, KGW_C, device=X.device)
-        ctx.shard = active_gene_shard(ctx, 1, X, W, b) if _resident_ok(X, W) else None
-        h, done = resident_first_linear(X, W, b, g2l, out, ctx.shard)
-        if n and not done:
-            _lib.check(_lib.lib().kgw_gather_rows(_p(h), _p(ids), n, h.shape[1], _p(out), _lib.stream_ptr()), 'kgw_gather_rows')
+        h, out = _resident_first_rows(ctx, X, W, b, ids, g2l)
         ctx.save_for_backward(X, h, g2l, W)
         return out
 
@@ -1860,17 +1892,7 @@ class _ResidentMLP2(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, X, W1, b1, W2, b2, ids, g2l, out, rows_real=None):
-        n = int(ids.numel())
-        ctx.shard = active_gene_shard(ctx, 1, X, W1, b1) if _resident_ok(X, W1) else None
-        # the rows past the batch's real node count (static capacity of a captured step) are written by nobody on the fused
-        # route and must be zero (see _ResidentLinearReLURows): with ``rows_real`` (their count on the device) the product's
-        # range-sum launch zeroes exactly those rows itself -- no fill launch over the whole block
-        in_kernel = rows_real is not None and n > 0 and ctx.shard is None and _resident_ok(X, W1)
-        h1g = (torch.zeros(n, KGW_C, device=X.device) if (_resident_ok(X, W1) and not in_kernel)
-               else torch.empty(n, KGW_C, device=X.device))
-        h, done = resident_first_linear(X, W1, b1, g2l, h1g, ctx.shard, rows_real if in_kernel else None)
-        if n and not done:
-            _lib.check(_lib.lib().kgw_gather_rows(_p(h), _p(ids), n, h.shape[1], _p(h1g), _lib.stream_ptr()), 'kgw_gather_rows')
+        h, h1g = _resident_first_rows(ctx, X, W1, b1, ids, g2l, rows_real)
         h2 = linear(h1g, W2, b2, relu=True, out=out.view() if out is not None else None)
         ctx.save_for_backward(X, h, h1g, W2, g2l, W1)
         return h2
@@ -1879,39 +1901,20 @@ class _ResidentMLP2(torch.autograd.Function):
     def backward(ctx, dh2):
         X, h, h1g, W2, g2l, W1 = ctx.saved_tensors
         dh2 = dh2.contiguous()
-        N = h.shape[0]
-        L = _lib.lib()
-        db1 = torch.empty(KGW_C, device=h.device)
-        nws = int(L.kgw_mlp2_bwd_first_workspace_floats(N))
-        ws = torch.empty(nws, device=h.device)
-        sink = GRAD_SINK
+        first = None
         if _PACK_FUSED and ctx.shard is None and _resident_ok(X, W1):
             # the masked dh1 rows leave the kernel as kgw_gemm3's B operand image (the weight gradient's): no fp32 rows, no
             # kgw_gemm3_pack launch
             Xt = _resident_copies(X)[1]                  # image of X^T [K, Np], Np = the node count rounded up to 32
-            packed = torch.empty(int(L.kgw_gemm3_packed_bytes(Xt.shape[1] * 32)), dtype=torch.uint8, device=h.device)
-            src = (_lib.KgwGradSrc * 2)()
-            rc = L.kgw_mlp2_bwd_first_packed(_p(dh2), dh2.stride(0), _p(W2), W2.stride(0), _p(h), h.stride(0), None, 0, 0, N, None, 0,
-                                             _p(db1), _p(ws), nws, _p(g2l), None, 0, _p(packed), int(L.kgw_gemm3_flip()),
-                                             src if sink is not None else None, _lib.stream_ptr())
-            if rc != _lib.KGW_E_UNSUPPORTED:
-                _lib.check(rc, 'kgw_mlp2_bwd_first_packed')
-                if sink is not None:
-                    sink.add(db1, src[1], ws)
-                dW1 = gemm3(Xt, packed, transpose_out=True, defer=True, image_rows=X.shape[1])
-                dW2, db2 = linear_weight_grad(dh2, h1g)
-                return None, dW1, db1, dW2, db2, None, None, None, None
-        dz = _dz_buffer(h, ctx.shard)
-        if sink is not None:
-            src = (_lib.KgwGradSrc * 2)()
-            _lib.check(L.kgw_mlp2_bwd_first_partial(_p(dh2), dh2.stride(0), _p(W2), W2.stride(0), _p(h), h.stride(0), None, 0, 0, N, None,
-                                                    None, 0, _p(db1), _p(ws), nws, _p(g2l), _p(dz), dz.stride(0), src, _lib.stream_ptr()),
-                       'kgw_mlp2_bwd_first_partial')
-            sink.add(db1, src[1], ws)
+            packed = torch.empty(int(_lib.lib().kgw_gemm3_packed_bytes(Xt.shape[1] * 32)), dtype=torch.uint8, device=h.device)
+            first = _mlp2_bwd_first(dh2, W2, h, in_ids=g2l, packed=packed)
+        if first is not None:
+            db1 = first[1]
+            dW1 = gemm3(Xt, packed, transpose_out=True, defer=True, image_rows=X.shape[1])
         else:
-            _lib.check(L.kgw_mlp2_bwd_first(_p(dh2), dh2.stride(0), _p(W2), W2.stride(0), _p(h), h.stride(0), None, 0, 0, N, None, None, 0,
-                                            _p(db1), _p(ws), nws, _p(g2l), _p(dz), dz.stride(0), _lib.stream_ptr()), 'kgw_mlp2_bwd_first')
-        dW1 = resident_first_weight_grad(dz, X, W1, ctx.shard)
+            dz = _dz_buffer(h, ctx.shard)
+            db1 = _mlp2_bwd_first(dh2, W2, h, in_ids=g2l, dz=dz)[1]
+            dW1 = resident_first_weight_grad(dz, X, W1, ctx.shard)
         dW2, db2 = linear_weight_grad(dh2, h1g)
         return None, dW1, db1, dW2, db2, None, None, None, None
 
@@ -2246,22 +2249,12 @@ def _transform_bwd_merged(live_blocks, dW, db, dZ, w_src_t, gamma, stat, dgamma,
     for q, (lo, hi, z0, rows, R, x, dz) in enumerate(live_blocks):
         out, bs = dW[lo:hi].view(R * C, C), db[lo:hi]
         A, B = dz, x                                         # C^T = (A^T B)^T with column sums of A: see _tn_gemm_group
-        if not (A.dtype == torch.float32 and B.dtype == torch.float32 and A.stride(1) == 1 and B.stride(1) == 1 and out.stride(1) == 1 and
-                bs.stride(1) == 1 and A.shape[0] == B.shape[0] and A.shape[0] > 0 and A.shape[1] % 2 == 0 and B.shape[1] % 2 == 0 and
-                A.shape[1] >= 64 and B.shape[1] >= 64 and A.stride(0) % 2 == 0 and B.stride(0) % 2 == 0 and A.data_ptr() % 8 == 0 and
-                B.data_ptr() % 8 == 0):
+        if not (_tn_multi_ok(A, B) and out.stride(1) == 1 and bs.stride(1) == 1):          # (row-major output views)
             return False
+        # (the launch's other blocks: dz is also the few-rows split-K kernel's X operand -- the dZ twin and the d gamma sums)
         if not (rows < _SPLITK_MAX_ROWS and dz.stride(0) % 4 == 0 and dz.data_ptr() % 16 == 0 and C == KGW_C):
             return False
-        M, N = A.shape[1], B.shape[1]
-        nws = int(L.kgw_tn_gemm_workspace_floats(rows, M, N))
-        ws = torch.empty(nws, device=A.device)
-        keep.append(ws)
-        j = tn[q]
-        j.A, j.lda, j.B, j.ldb, j.rows = _p(A), A.stride(0), _p(B), B.stride(0), rows
-        j.C, j.ldc, j.colsum_a, j.colsum_ld = _p(out), out.stride(0), _p(bs), bs.stride(0)
-        j.workspace, j.workspace_floats, j.rows_dev = _p(ws), nws, None
-        j.M, j.N, j.c_transposed, j.colsum_repeat = M, N, 1, bs.shape[0]
+        keep.append(_tn_job(tn[q], A, B, _p(out), out.stride(0), _p(bs), bs.stride(0), c_transposed=True, colsum_repeat=bs.shape[0]))
         if dZ is not None:
             W = w_src_t[lo:hi].view(R * C, C)
             y = dZ[z0:z0 + rows * R].view(rows, R * C)
@@ -2647,17 +2640,7 @@ def _root_weight_grad(pairs, weight):
     for i in range(0, len(live), 4):
         chunk = live[i:i + 4]
         jobs = (_lib.KgwTnJob * len(chunk))()
-        keep = []
-        for j, (t, g, x) in zip(jobs, chunk):
-            rows = x.shape[0]
-            nws = int(L.kgw_tn_gemm_workspace_floats(rows, KGW_C, KGW_C))
-            ws = torch.empty(nws, device=x.device)
-            keep.append(ws)
-            out = dW[t]
-            j.A, j.lda, j.B, j.ldb, j.rows = _p(g), g.stride(0), _p(x), x.stride(0), rows
-            j.C, j.ldc, j.colsum_a, j.colsum_ld = _p(out), KGW_C, None, KGW_C
-            j.workspace, j.workspace_floats, j.rows_dev = _p(ws), nws, None
-            j.M, j.N, j.c_transposed, j.colsum_repeat = KGW_C, KGW_C, 0, 1
+        keep = [_tn_job(j, g, x, _p(dW[t]), KGW_C, 0, KGW_C) for j, (t, g, x) in zip(jobs, chunk)]       # (no column sums)
         _lib.check(L.kgw_tn_gemm_multi(len(chunk), jobs, _lib.stream_ptr()), 'kgw_tn_gemm_multi')
     return dW
 
