@@ -387,6 +387,7 @@ def lib():
 
 
 KGW_E_UNSUPPORTED = -3
+KGW_GRAD_G3T = 5                # KgwGradSrc.kind: partial sums of kgw_gemm3_partial (include/kgwas_hip.h)
 
 
 def has_heads() -> bool:

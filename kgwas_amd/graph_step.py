@@ -437,7 +437,7 @@ class GraphTrainStep:
             self.opt.step(tick=False)                              # (the counter advances in the statistics launch)
             self._stats_tick(cur, self.opt.step_dev.data_ptr())
             return loss
-        self.deferred_gradients = sum(1 for r in sink.records.values() if r[0] is not None) + 2 * len(sink.products)   # (gradients whose last sums the optimiser launch takes)
+        self.deferred_gradients = sink.deferred_gradients            # (gradients whose last sums the optimiser launch takes)
         self.opt.step_fused(sink, self.bufs[cur].meta.data_ptr(), self.run.gnn_num_layers, self.dg.n_hops, self.stats)
         # (launches of the step that carried its parameter-only forward work as rider blocks: the gene layer's kgw_gemm3)
         self.riders_taken = getattr(self.model, 'last_riders_taken', 0)
@@ -501,7 +501,7 @@ class GraphTrainStep:
             if staged:
                 self._flat_grads[w1] = self._flat_b[n_live:].view_as(w1)
         if sink is not None:
-            self.deferred_gradients = sum(1 for r in sink.records.values() if r[0] is not None) + 2 * len(sink.products)
+            self.deferred_gradients = sink.deferred_gradients
             self.opt.finish_into(sink, [(p, self._flat_grads[p]) for p in live])
         else:
             torch.cat([p.grad.reshape(-1) for p in live], out=self._flat_b[:n_live])

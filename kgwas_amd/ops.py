@@ -11,6 +11,7 @@ import ctypes as C
 import os
 import weakref
 import sys
+from typing import NamedTuple
 
 import torch
 
@@ -188,32 +189,56 @@ class GradSinkMismatch(RuntimeError):
     wrote the record for (autograd copied or accumulated it): the fused optimiser launch cannot be used for this model."""
 
 
+# What a GradSink holds, one record type per thing.  GradRecord: the value of ``records``, per gradient tensor's address -- ``src``: the
+# KgwGradSrc whose partial sums the optimiser's launch finishes, or None: the tensor is (or will be, by a launch ahead of the
+# optimiser's) complete, nothing is left to sum, but it must arrive at a parameter unchanged; ``keep``: workspace and gradient STORAGE,
+# alive until the optimiser's launch is enqueued.  DeferredProduct: see GradSink.defer_product (``keep``: the outputs' storages).
+GradRecord = NamedTuple('GradRecord', [('src', object), ('numel', int), ('keep', object)])
+DeferredProduct = NamedTuple('DeferredProduct', [('dY', torch.Tensor), ('X', torch.Tensor), ('dW_ptr', int), ('db_ptr', int),
+                                                 ('keep', object), ('rows_dev', object)])
+# the four launches a GradSink parks.  ``outs``: [(address, numel, storage)] of the leaf gradients the launch writes, see _outs
+ParkedFoldBwd = NamedTuple('ParkedFoldBwd', [('args', object), ('keep', object), ('outs', list)])              # kgw_fold_bwd
+ParkedRelvecBwd = NamedTuple('ParkedRelvecBwd', [('n', int), ('jobs', object), ('keep', object), ('outs', list)])   # kgw_relvec_bwd_multi
+ParkedReduce = NamedTuple('ParkedReduce', [('plan', object), ('keep', object)])                                # kgw_tn_reduce_launch
+ParkedReadoutFold = NamedTuple('ParkedReadoutFold', [('fold', object), ('keep', object)])                      # kgw_readout_train_fold
+
+
+def _outs(tensors):
+    """(addresses + STORAGES, not the tensors: a second reference to a gradient tensor would make autograd's accumulation clone it --
+    before a deferred launch has written it -- instead of adopting it; the storage only keeps the memory from being handed out again)"""
+    return [(t.data_ptr(), t.numel(), t.untyped_storage()) for t in tensors]
+
+
 class GradSink:
     """While one is active (``grad_sink_scope``: the backward pass of a captured single-GPU training step), the weight-gradient
-    products that feed NOTHING but the optimiser stop after their first launch and leave a KgwGradSrc record here, keyed by the
-    address of the gradient tensor they return to autograd; ``FusedAdam.step_fused`` looks every parameter's ``.grad`` up, finishes
-    the sums inside the optimiser's own launch (kgw_adam_fused: same order, bit-identical values, the gradient tensors filled in
-    as a by-product) and fails loudly if a record is left over.  The records keep the partial-sum workspaces alive -- inside a
-    graph capture a freed block would be handed to the next allocation of the same capture."""
+    products that feed NOTHING but the optimiser stop after their first launch and leave a GradRecord here, keyed by the
+    address of the gradient tensor they return to autograd; ``FusedAdam.step_fused`` claims every parameter's ``.grad`` (``claim``),
+    finishes the sums inside the optimiser's own launch (kgw_adam_fused: same order, bit-identical values, the gradient tensors
+    filled in as a by-product) and fails loudly if a record is left over.  The records keep the partial-sum workspaces alive --
+    inside a graph capture a freed block would be handed to the next allocation of the same capture.
+
+    Launches that feed only the optimiser are PARKED here (``park_*``) and issued later: merged into one launch by ``flush``, as
+    rider blocks of a launch that takes them (``ride_*``), or on their own by ``settle``.  The one rule: a launch that reads what a
+    parked launch writes calls ``settle`` first; a launch that can carry a parked one calls ``ride_*`` and passes what it gets."""
 
     def __init__(self):
-        self.records = {}           # data_ptr of the gradient tensor -> (KgwGradSrc, numel, workspace)
-        self.products = []          # weight-gradient products not launched yet, see defer_product
+        self.records = {}           # data_ptr of the gradient tensor -> GradRecord
+        self.products = []          # DeferredProduct: weight-gradient products not launched yet, see defer_product
         # the parameter-only END of the backward pass -- kgw_fold_bwd and kgw_relvec_bwd_multi: they feed nothing but the optimiser --
         # not launched where autograd reaches them but by ``flush``, as blocks of the deferred products' launch (kgw_param_tail)
-        self.fold_bwd = None        # (KgwFoldArgs, keep-alive, [(address, numel, storage) of the leaf gradients it writes])
-        self.relvec_bwd = None      # (n jobs, jobs, keep-alive, [(address, numel, storage)])
+        self.fold_bwd = None        # ParkedFoldBwd
+        self.relvec_bwd = None      # ParkedRelvecBwd
         self.tail_taken = 0         # kgw_param_tail launches issued
-        self.pending_reduce = None  # (KgwTnReducePlan, keep-alive) of a product group whose second launch is waiting for a carrier
+        self.pending_reduce = None  # ParkedReduce: a product group's second launch, waiting for a carrier
         self.reduces_ridden = 0     # plans that rode in a later launch
         self.keep = []              # operands of launches issued on behalf of others: alive until the optimiser's launch is enqueued
-        self.pending_fold = None    # (KgwReadoutFold, keep-alive): the read-out node's second launch, waiting for a carrier
+        self.pending_fold = None    # ParkedReadoutFold: the read-out node's second launch, waiting for a carrier
         self.folds_ridden = 0
 
     def defer_product(self, dY: torch.Tensor, X: torch.Tensor, rows_dev=None):
         """(dW [out, in], db [out]) = (dY^T X, column sums of dY) of a Linear whose gradients feed only the optimiser -- not launched
         now: the MLPs' backward passes end in one such product each (gene 20 k rows, SNP 122 k, GO 2 x 7 k), 15 - 40 us launches that
-        depend on nothing but their own operands; ``flush`` (called by FusedAdam.step_fused) issues them as ONE kgw_tn_gemm_multi
+        depend on nothing but their own operands; ``flush`` (called by ``claim``) issues them as ONE kgw_tn_gemm_multi
         launch ahead of the optimiser's, where the short ones fill the slots the tall one leaves.  None: the shape is not the grouped
         kernel's (the caller launches it itself)."""
         rows, M = dY.shape
@@ -224,65 +249,107 @@ class GradSink:
             return None
         dW = torch.empty(M, N, device=dY.device)
         db = torch.empty(M, device=dY.device)
-        # (addresses + STORAGES, not the tensors: a second reference to the tensor would make autograd copy the gradient instead of
-        #  adopting it -- the storage reference only keeps the memory from being handed out again before the product has run)
-        self.products.append((dY, X, dW.data_ptr(), db.data_ptr(), dW.untyped_storage(), db.untyped_storage(), rows_dev))
+        # (addresses + STORAGES, not the tensors, as in _outs: the storages keep the memory until the product has run)
+        self.products.append(DeferredProduct(dY, X, dW.data_ptr(), db.data_ptr(), (dW.untyped_storage(), db.untyped_storage()), rows_dev))
         return dW, db
 
     def _tn_jobs(self, chunk):
         jobs = (_lib.KgwTnJob * max(len(chunk), 1))()
         src = (_lib.KgwGradSrc * max(2 * len(chunk), 1))()
-        keep = [_tn_job(j, dY, X, dW_ptr, X.shape[1], db_ptr, dY.shape[1], rows_dev=rows_dev)
-                for j, (dY, X, dW_ptr, db_ptr, _sw, _sb, rows_dev) in zip(jobs, chunk)]
+        keep = [_tn_job(j, p.dY, p.X, p.dW_ptr, p.X.shape[1], p.db_ptr, p.dY.shape[1], rows_dev=p.rows_dev) for j, p in zip(jobs, chunk)]
         return jobs, src, keep
 
-    def take_reduce(self):
-        """The pending reduce plan for a launch that will carry it (or None); the caller reports with ``rode``."""
+    def expect(self, *outs):
+        """The one way to write a source-less record, per (address, numel, storage) of ``outs``: that tensor goes straight to its
+        parameter, written by its producer or by a launch parked here -- a copy autograd made on the way is then noticed as a
+        left-over record."""
+        for ptr, numel, storage in outs:
+            self.records[ptr] = GradRecord(None, numel, storage)
+
+    # ---- parking: each method holds its own condition and says whether it took the launch (False: the caller issues it)
+    def park_fold_bwd(self, args, keep, outs) -> bool:
+        """kgw_fold_bwd writing the leaf gradients ``outs``: its other outputs reach the relation vectors' backward (parked the same
+        way, behind it) and nothing else.  Needs BOTH slots free: a fold behind parked relation vectors would be issued after them."""
+        ok = _PARAM_TAIL and _DEFER_PRODUCTS and self.fold_bwd is None and self.relvec_bwd is None
+        if ok:
+            self.fold_bwd = ParkedFoldBwd(args, keep, _outs(outs))
+        return ok
+
+    def park_relvec_bwd(self, n, jobs, keep, outs) -> bool:
+        """kgw_relvec_bwd_multi (``n`` jobs) writing the leaf gradients ``outs``; a fold may be parked ahead of it."""
+        ok = _PARAM_TAIL and _DEFER_PRODUCTS and self.relvec_bwd is None
+        if ok:
+            self.relvec_bwd = ParkedRelvecBwd(n, jobs, keep, _outs(outs))
+        return ok
+
+    def park_reduce(self, plan, keep, dW, db) -> bool:
+        """The second launch (k_tn_reduce) of a transform's weight-gradient products, finishing ``dW`` and ``db``.  Too many blocks
+        to ride are refused: they would run a few at a time with the carrier's registers and LDS."""
+        ok = _DEFER_REDUCE and plan.blocks <= _RIDE_MAX_BLOCKS
+        if ok:
+            self.pending_reduce = ParkedReduce(plan, (keep, dW.untyped_storage(), db.untyped_storage()))
+            self.expect(*_outs([db]))                    # (d bias goes straight to its parameter; d W through the relation vectors' node)
+        return ok
+
+    def park_readout_fold(self, fold, keep, dw, db) -> bool:
+        """The read-out node's second launch, finishing d w_lin / d b_lin (and the loss); both go straight to their parameters."""
+        ok = self.pending_fold is None
+        if ok:
+            self.pending_fold = ParkedReadoutFold(fold, (keep, dw.untyped_storage(), db.untyped_storage()))
+            self.expect(*_outs([dw, db]))
+        return ok
+
+    # ---- riding: the parked record for a launch that carries it, or None.  Counted here, at take time: a carrier used to count after
+    #      its launch had returned, and a launch that raises ends the step, so the two are equivalent
+    def ride_reduce(self):
         r, self.pending_reduce = self.pending_reduce, None
         if r is not None:
             self.keep.append(r)
+            self.reduces_ridden += 1
         return r
 
-    def take_fold(self):
+    def ride_fold(self):
         f, self.pending_fold = self.pending_fold, None
         if f is not None:
             self.keep.append(f)
+            self.folds_ridden += 1
         return f
 
-    def launch_pending_fold(self):
-        f = self.take_fold()
-        if f is not None:
-            _lib.check(_lib.lib().kgw_readout_train_fold(C.byref(f[0]), _lib.stream_ptr()), 'kgw_readout_train_fold')
-
-    def launch_pending_reduce(self):
-        r = self.take_reduce()
+    def _launch_reduce(self):
+        r, self.pending_reduce = self.pending_reduce, None
         if r is not None:
-            _lib.check(_lib.lib().kgw_tn_reduce_launch(C.byref(r[0]), _lib.stream_ptr()), 'kgw_tn_reduce_launch')
+            self.keep.append(r)
+            _lib.check(_lib.lib().kgw_tn_reduce_launch(C.byref(r.plan), _lib.stream_ptr()), 'kgw_tn_reduce_launch')
 
-    def launch_pending_tail(self):
-        """kgw_fold_bwd / kgw_relvec_bwd_multi left pending, as launches of their own, in that order (a consumer of their outputs is
-        about to be launched, or the merged launch does not take them)."""
+    def _expect_outs(self, *parked):
+        for t in parked:
+            if t is not None:
+                self.expect(*t.outs)
+
+    def settle(self):
+        """Issue, as launches of their own, whatever is parked that a launch about to be issued may read: the pending reduce
+        (kgw_fold_bwd / kgw_relvec_bwd_multi read the transform's weight gradient it finishes, and so may the caller), kgw_fold_bwd,
+        kgw_relvec_bwd_multi -- in that order.  The read-out fold stays parked: only the optimiser reads what it writes."""
         L = _lib.lib()
         fb, rb = self.fold_bwd, self.relvec_bwd
         self.fold_bwd = self.relvec_bwd = None
-        if fb is not None or rb is not None:
-            self.launch_pending_reduce()                 # (they read the transform's weight gradient)
+        self._launch_reduce()
         if fb is not None:
-            _lib.check(L.kgw_fold_bwd(C.byref(fb[0]), _lib.stream_ptr()), 'kgw_fold_bwd')
+            _lib.check(L.kgw_fold_bwd(C.byref(fb.args), _lib.stream_ptr()), 'kgw_fold_bwd')
         if rb is not None:
-            _lib.check(L.kgw_relvec_bwd_multi(rb[0], rb[1], _lib.stream_ptr()), 'kgw_relvec_bwd_multi')
-        for t in (fb, rb):
-            if t is not None:
-                for ptr, numel, st in t[-1]:
-                    self.records[ptr] = (None, numel, st)
+            _lib.check(L.kgw_relvec_bwd_multi(rb.n, rb.jobs, _lib.stream_ptr()), 'kgw_relvec_bwd_multi')
+        self._expect_outs(fb, rb)
 
     def flush(self):
         """Launch the deferred products (first launch only: their row blocks' partial sums are taken by the optimiser's launch) and,
         in the same launch, the parameter-only end of the backward pass (kgw_param_tail)."""
         L = _lib.lib()
-        self.launch_pending_reduce()                     # (nothing came by to carry it: the tail reads what it finishes)
-        self.launch_pending_fold()
-        todo, self.products = sorted(self.products, key=lambda p: -p[0].shape[0]), []       # the tall ones first in the grid
+        self._launch_reduce()                            # (nothing came by to carry it: the tail reads what it finishes)
+        f, self.pending_fold = self.pending_fold, None   # (nor the read-out fold)
+        if f is not None:
+            self.keep.append(f)
+            _lib.check(L.kgw_readout_train_fold(C.byref(f.fold), _lib.stream_ptr()), 'kgw_readout_train_fold')
+        todo, self.products = sorted(self.products, key=lambda p: -p.dY.shape[0]), []       # the tall ones first in the grid
         chunks = [todo[i:i + 4] for i in range(0, len(todo), 4)]
         fb, rb = self.fold_bwd, self.relvec_bwd
         if (fb is not None or rb is not None) and not chunks:
@@ -294,53 +361,62 @@ class GradSink:
                 # (the fold's outputs must BE the inputs of one of the relation-vector jobs: that job's blocks then compute them)
                 fold_job = -1
                 if fb is not None:
-                    a = fb[0]
-                    fold_job = next((k for k in range(rb[0]) if rb[1][k].dU_full == a.dU and rb[1][k].dV == a.dV and
-                                     rb[1][k].dw_src_acc == a.dws and not rb[1][k].duv_pieces), -1)
+                    a = fb.args
+                    fold_job = next((k for k in range(rb.n) if rb.jobs[k].dU_full == a.dU and rb.jobs[k].dV == a.dV and
+                                     rb.jobs[k].dw_src_acc == a.dws and not rb.jobs[k].duv_pieces), -1)
                 if fb is None or fold_job >= 0:
-                    rc = L.kgw_param_tail(len(chunk), jobs, src, C.byref(fb[0]) if fb is not None else None, rb[0], rb[1], fold_job,
+                    rc = L.kgw_param_tail(len(chunk), jobs, src, C.byref(fb.args) if fb is not None else None, rb.n, rb.jobs, fold_job,
                                           _lib.stream_ptr())
                     if rc != _lib.KGW_E_UNSUPPORTED:
                         _lib.check(rc, 'kgw_param_tail')
                         merged = True
                         self.tail_taken += 1
-                        for t in (fb, rb):
-                            if t is not None:
-                                for ptr, numel, st in t[-1]:
-                                    self.records[ptr] = (None, numel, st)
-                        self._tail_keep = (fb, rb)           # (operands alive until the optimiser's launch is enqueued)
+                        self._expect_outs(fb, rb)
+                        self.keep.append((fb, rb))           # (operands alive until the optimiser's launch is enqueued)
                         self.fold_bwd = self.relvec_bwd = None
-            if ci == 0 and not merged:
-                self.launch_pending_tail()
+            if ci == 0 and not merged:                   # (also a fold without relation vectors behind it: there is always a chunk 0)
+                self.settle()
             if not merged and chunk:
                 _lib.check(L.kgw_tn_gemm_multi_partial(len(chunk), jobs, src, _lib.stream_ptr()), 'kgw_tn_gemm_multi_partial')
-            for q, (dY, X, dW_ptr, db_ptr, _sw, _sb, rows_dev) in enumerate(chunk):
-                M, N = dY.shape[1], X.shape[1]
-                for ptr, numel, rec_src in ((dW_ptr, M * N, src[2 * q]), (db_ptr, M, src[2 * q + 1])):
+            for q, p in enumerate(chunk):
+                M, N = p.dY.shape[1], p.X.shape[1]
+                for ptr, numel, rec_src in ((p.dW_ptr, M * N, src[2 * q]), (p.db_ptr, M, src[2 * q + 1])):
                     # (a product with one row block is complete -- KGW_GRAD_DIRECT -- but was still written to the address handed to
                     #  autograd: it gets a record WITHOUT a source, so that a gradient autograd copied instead of adopting is noticed)
-                    rec = None
-                    if rec_src.kind != 0:
-                        rec = _lib.KgwGradSrc()
-                        C.memmove(C.byref(rec), C.byref(rec_src), C.sizeof(rec))
-                    self.records[ptr] = (rec, numel, keep[q])
-        if self.fold_bwd is not None or self.relvec_bwd is not None:      # (a fold without relation vectors behind it)
-            self.launch_pending_tail()
+                    rec = _lib.KgwGradSrc.from_buffer_copy(rec_src) if rec_src.kind != 0 else None
+                    self.records[ptr] = GradRecord(rec, numel, (keep[q], p.keep))
 
     def add(self, grad: torch.Tensor, src, ws: torch.Tensor):
         if src.kind != 0:           # (KGW_GRAD_DIRECT: the producer finished the tensor itself)
-            rec = _lib.KgwGradSrc()
-            C.memmove(C.byref(rec), C.byref(src), C.sizeof(rec))
+            rec = _lib.KgwGradSrc.from_buffer_copy(src)
             # (NOT the tensor: autograd must be able to steal it -- but its STORAGE, like defer_product: were autograd to clone the
             #  gradient and drop the original, the caching allocator could hand the block to another gradient of the same size,
             #  which would then inherit this record; with the block held a clone is noticed as a left-over record)
-            self.records[grad.data_ptr()] = (rec, grad.numel(), ws, grad.untyped_storage())
+            self.records[grad.data_ptr()] = GradRecord(rec, grad.numel(), (ws, grad.untyped_storage()))
 
     def take(self, grad: torch.Tensor):
         rec = self.records.pop(grad.data_ptr(), None)
-        if rec is not None and rec[1] != grad.numel():
+        if rec is not None and rec.numel != grad.numel():
             raise GradSinkMismatch('a deferred gradient record does not describe the tensor found at its address')
         return rec
+
+    @property
+    def deferred_gradients(self):
+        """Gradients whose last sums the optimiser's launch takes: the sourced records and two per product not flushed yet."""
+        return sum(1 for r in self.records.values() if r.src is not None) + 2 * len(self.products)
+
+    def claim(self, grads):
+        """The reconcile ahead of the optimiser's launch: ``flush``, then every gradient tensor of ``grads`` = {parameter: its
+        gradient} is looked up.  Returns {parameter: record} of the gradients whose partial sums the launch has to finish (a complete
+        tensor has no record, or a source-less one that is only matched).  GradSinkMismatch, with the books cleared, when a record
+        is left: a gradient did not reach a parameter as written."""
+        self.flush()
+        recs = {p: self.take(g) for p, g in grads.items()}
+        if self.records:
+            n = len(self.records)
+            self.records.clear()
+            raise GradSinkMismatch(f'{n} deferred gradient(s) did not reach a parameter as written')
+        return {p: r for p, r in recs.items() if r is not None and r.src is not None}
 
 
 GRAD_SINK = None           # the GradSink of the backward pass being issued, or None (every product finishes its own sums)
@@ -953,10 +1029,9 @@ def tn_gemm(A: torch.Tensor, B: torch.Tensor, colsum: bool = False, out: torch.T
         if src is None:
             _lib.check(L.kgw_tn_gemm_ex(*head, rep, cs_ld, *tail, _lib.stream_ptr()), 'kgw_tn_gemm_ex')
             return
-        ride = sink.take_reduce()
+        ride = sink.ride_reduce()
         if ride is not None:           # (a product group's pending second launch rides in this product's: GradSink.pending_reduce)
-            _lib.check(L.kgw_tn_gemm_partial_ride(*head, *tail, src, C.byref(ride[0]), _lib.stream_ptr()), 'kgw_tn_gemm_partial_ride')
-            sink.reduces_ridden += 1
+            _lib.check(L.kgw_tn_gemm_partial_ride(*head, *tail, src, C.byref(ride.plan), _lib.stream_ptr()), 'kgw_tn_gemm_partial_ride')
         else:
             _lib.check(L.kgw_tn_gemm_partial(*head, *tail, src, _lib.stream_ptr()), 'kgw_tn_gemm_partial')
 
@@ -2049,13 +2124,11 @@ class _RelVectors(torch.autograd.Function):
         dwd = torch.empty_like(w_dst_t)
         das = torch.empty_like(att_src)
         dad = torch.empty_like(att_dst)
-        sink = GRAD_SINK
-        if sink is not None:
+        if GRAD_SINK is not None:
             # (inside a captured step a fold's kgw_fold_bwd or a transform's k_tn_reduce may still be PENDING in the sink -- parked
             #  there for _RelVectorsMulti / k_param_tail -- and this launch reads what they write: dU, dV, dW_in.  The per-layer node
             #  is the one a 1-layer model or KGW_RELVEC_ALL=0 takes: tests/test_gpu_fallbacks.py)
-            sink.launch_pending_tail()
-            sink.launch_pending_reduce()
+            GRAD_SINK.settle()
         _lib.check(_lib.lib().kgw_relvec_bwd_acc(n, _p(pack.rel_ids_i32), _p(pack.bip_pos_i32), _p(w_src_t),
                                                  _p(w_dst_t) if w_dst_t.numel() else 0, _p(att_src), _p(att_dst), _p(dU), _p(dV),
                                                  _p(dW_in), _p(dws), _p(dwd) if dwd.numel() else 0, _p(das), _p(dad), 1,
@@ -2142,16 +2215,10 @@ class _RelVectorsMulti(torch.autograd.Function):
             made += [dws, dwd, das, dad]
         if live:
             sink = GRAD_SINK
-            if sink is not None and _PARAM_TAIL and _DEFER_PRODUCTS and sink.relvec_bwd is None:
-                # (feeds only the optimiser: launched by GradSink.flush.  The OUTPUT tensors are kept alive through their storages
-                #  only: a second reference to a gradient tensor would make autograd's accumulation clone it -- before the deferred
-                #  launch has written it -- instead of adopting it)
-                outs = [(t.data_ptr(), t.numel(), t.untyped_storage()) for t in made if t.numel()]
-                sink.relvec_bwd = (live, jobs, (keep, params), outs)
-            else:
+            # (feeds only the optimiser: parked, launched by GradSink.flush -- the OUTPUT tensors held through their storages only)
+            if sink is None or not sink.park_relvec_bwd(live, jobs, (keep, params), [t for t in made if t.numel()]):
                 if sink is not None:
-                    sink.launch_pending_tail()           # (a fold still pending feeds this launch)
-                    sink.launch_pending_reduce()         # (so does the transform's weight gradient)
+                    sink.settle()                        # (a fold still pending feeds this launch, and so does the transform's weight gradient)
                 _lib.check(_lib.lib().kgw_relvec_bwd_multi(live, jobs, _lib.stream_ptr()), 'kgw_relvec_bwd_multi')
         return (None, None, None, None) + tuple(ret)
 
@@ -2271,24 +2338,15 @@ def _transform_bwd_merged(live_blocks, dW, db, dZ, w_src_t, gamma, stat, dgamma,
     if sink is not None and (_DEFER_REDUCE or sink.pending_fold is not None):
         # the second launch of these products is left pending (the gradients it finishes wait for the end of the backward pass
         # anyway) and the one an earlier layer left rides in this launch
-        ride = sink.take_reduce()
-        fold = sink.take_fold()                    # (the read-out node's second launch: one more block of this one)
+        ride = sink.ride_reduce()
+        fold = sink.ride_fold()                    # (the read-out node's second launch: one more block of this one)
         plan = _lib.KgwTnReducePlan()
         _lib.check(L.kgw_transform_bwd_ex(n, tn, n if dZ is not None else 0, sk, n if gamma is not None else 0, cs,
-                                          _lib.C.byref(ride[0]) if ride is not None else None, _lib.C.byref(plan),
-                                          _lib.C.byref(fold[0]) if fold is not None else None, _lib.stream_ptr()),
+                                          _lib.C.byref(ride.plan) if ride is not None else None, _lib.C.byref(plan),
+                                          _lib.C.byref(fold.fold) if fold is not None else None, _lib.stream_ptr()),
                    'kgw_transform_bwd_ex')         # (``C`` is the channel count here)
-        if ride is not None:
-            sink.reduces_ridden += 1
-        if fold is not None:
-            sink.folds_ridden += 1
-        if plan.valid and (plan.blocks > _RIDE_MAX_BLOCKS or not _DEFER_REDUCE):
-            # (too many blocks to ride: they would run a few at a time with the carrier's registers and LDS -- launched here)
+        if plan.valid and not sink.park_reduce(plan, keep, dW, db):          # (not taken -- KGW_DEFER_REDUCE=0, too many blocks: here)
             _lib.check(L.kgw_tn_reduce_launch(_lib.C.byref(plan), _lib.stream_ptr()), 'kgw_tn_reduce_launch')
-        elif plan.valid:
-            # (workspaces + the STORAGES of the gradients it writes: see _RelVectorsMulti.backward)
-            sink.pending_reduce = (plan, keep, dW.untyped_storage(), db.untyped_storage())
-            sink.records[db.data_ptr()] = (None, db.numel(), db.untyped_storage())      # (d bias goes straight to its parameter: a copy made on the way must be noticed)
         return True
     _lib.check(L.kgw_transform_bwd(n, tn, n if dZ is not None else 0, sk, n if gamma is not None else 0, cs, _lib.stream_ptr()),
                'kgw_transform_bwd')
@@ -2787,15 +2845,11 @@ class _FoldFC(torch.autograd.Function):
             a.dUp, a.dVp, a.duv_pieces = pu[0], pv[0], 1
         a.dU, a.dV, a.dws = _p(dU), _p(dV), _p(dws)
         sink = GRAD_SINK
-        if sink is not None and _PARAM_TAIL and _DEFER_PRODUCTS and sink.fold_bwd is None and sink.relvec_bwd is None:
-            # its outputs reach the relation vectors' backward (queued the same way, behind it) and the optimiser, nothing else:
-            # launched by GradSink.flush (outputs: storages only, see _RelVectorsMulti.backward)
-            keep = (dUp, dVp, dkappa, dWp, dgamma, w_src_t, U, V, fc, tab, pu, pv, [t.untyped_storage() for t in (dU, dV, dws)])
-            sink.fold_bwd = (a, keep, [(t.data_ptr(), t.numel(), t.untyped_storage()) for t in dfc])
-        else:
+        # (parked, see GradSink.park_fold_bwd: launched by flush.  dU, dV, dws: storages only, like the leaf gradients -- see _outs)
+        keep = (dUp, dVp, dkappa, dWp, dgamma, w_src_t, U, V, fc, tab, pu, pv, [t.untyped_storage() for t in (dU, dV, dws)])
+        if sink is None or not sink.park_fold_bwd(a, keep, dfc):
             if sink is not None:
-                sink.launch_pending_tail()
-                sink.launch_pending_reduce()
+                sink.settle()
             _lib.check(_lib.lib().kgw_fold_bwd(C.byref(a), _lib.stream_ptr()), 'kgw_fold_bwd')
         return (dws, dU, dV, None, None) + tuple(dfc)
 
@@ -2939,14 +2993,9 @@ class _ReadoutWeightedMSE(torch.autograd.Function):
             is_unit = _is_unit_gradient(gloss)
             fold, ctx.fold = getattr(ctx, 'fold', None), None
             if fold is not None:
-                sink = GRAD_SINK
-                if sink is not None and is_unit and sink.pending_fold is None:
-                    # (d w_lin / d b_lin go straight to their parameters: storages only + a record, see _RelVectorsMulti.backward)
-                    sink.pending_fold = (fold[0], fold[1], dw.untyped_storage(), db.untyped_storage())
-                    sink.records[dw.data_ptr()] = (None, dw.numel(), dw.untyped_storage())
-                    sink.records[db.data_ptr()] = (None, db.numel(), db.untyped_storage())
-                else:
-                    _lib.check(_lib.lib().kgw_readout_train_fold(C.byref(fold[0]), _lib.stream_ptr()), 'kgw_readout_train_fold')
+                sink, (f, fkeep) = GRAD_SINK, fold
+                if not (sink is not None and is_unit and sink.park_readout_fold(f, fkeep, dw, db)):    # (rides in the next launch)
+                    _lib.check(_lib.lib().kgw_readout_train_fold(C.byref(f), _lib.stream_ptr()), 'kgw_readout_train_fold')
             return (*_for_gradient(gloss, (dH, dw, db)), None, None, None, None, None, None, None)
         H, w_lin, pred, n_id, y_all, w_all = ctx.saved_tensors
         gloss = gloss.contiguous().to(torch.float64)

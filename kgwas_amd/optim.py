@@ -47,23 +47,14 @@ class FusedAdam:
         launch.  Raises ops.GradSinkMismatch (nothing launched) when the fused form does not apply; the caller then runs the
         unfused step."""
         from . import ops
-        if sink is not None:
-            sink.flush()                     # the deferred weight-gradient products: one launch, just ahead of this one
         live = [p for p in self.params if p.grad is not None]
-        recs = {}
-        for p in live:
-            r = sink.take(p.grad) if sink is not None else None
-            if r is not None and r[0] is not None:           # (r[0] None: a deferred product that came out complete -- only matched)
-                recs[p] = r
-        if sink is not None and sink.records:
-            n = len(sink.records)
-            sink.records.clear()
-            raise ops.GradSinkMismatch(f'{n} deferred gradient(s) did not reach a parameter as written')
+        # (claim: the deferred weight-gradient products' one launch, just ahead of this one, then the sourced record of every gradient)
+        recs = sink.claim({p: p.grad for p in live}) if sink is not None else {}
         # a weight whose kgw_gemm3 operand image this launch keeps current must arrive as a KGW_GRAD_G3T record: updated from any other
         # kind of gradient (a complete tensor, a TN product, something autograd accumulated) the weight would change and the image the
         # next forward reads would not -- the HIP launches do not move the tensor's version counter, so nobody would notice
         for p in live:
-            if p in self.packed_images and (p not in recs or recs[p][0].kind != 5):
+            if p in self.packed_images and (p not in recs or recs[p].src.kind != _lib.KGW_GRAD_G3T):
                 raise ops.GradSinkMismatch('the gradient of a weight with a persistent kgw_gemm3 operand image did not arrive as the '
                                            'partial sums of kgw_gemm3_partial: its image would go stale')
         if len(live) > _lib.ADAM_FUSED_MAX or len(recs) > _lib.ADAM_FUSED_SRC:
@@ -82,9 +73,9 @@ class FusedAdam:
             st = self._state(p)
             P[k], G[k], M[k], V[k], N[k] = p.data_ptr(), g.data_ptr(), st['exp_avg'].data_ptr(), st['exp_avg_sq'].data_ptr(), p.numel()
             if p in recs:
-                C.memmove(C.byref(S[k]), C.byref(recs[p][0]), C.sizeof(_lib.KgwGradSrc))
+                C.memmove(C.byref(S[k]), C.byref(recs[p].src), C.sizeof(_lib.KgwGradSrc))
                 img = self.packed_images.get(p)
-                if img is not None and S[k].kind == 5:               # KGW_GRAD_G3T: the updated weight's operand image rides along
+                if img is not None and S[k].kind == _lib.KGW_GRAD_G3T:               # the updated weight's operand image rides along
                     S[k].packed, S[k].flip = img.data_ptr(), int(_lib.lib().kgw_gemm3_flip())
         rc = _lib.lib().kgw_adam_fused(n, P, G, M, V, N, S, self.step_dev.data_ptr(), self.lr, self.betas[0], self.betas[1], self.eps,
                                        self.weight_decay, meta_ptr, n_layers, n_hops, stats.data_ptr() if stats is not None else None,
@@ -99,16 +90,7 @@ class FusedAdam:
         producer left with ``sink`` otherwise -- instead of the producers' second launches + the bucket's concatenation.  Raises
         ops.GradSinkMismatch (nothing launched) like step_fused."""
         from . import ops
-        sink.flush()
-        recs = {}
-        for p, _ in pairs:
-            r = sink.take(p.grad)
-            if r is not None and r[0] is not None:
-                recs[p] = r
-        if sink.records:
-            n = len(sink.records)
-            sink.records.clear()
-            raise ops.GradSinkMismatch(f'{n} deferred gradient(s) did not reach a parameter as written')
+        recs = sink.claim({p: p.grad for p, _ in pairs})
         if len(recs) > _lib.ADAM_FUSED_SRC:
             raise ops.GradSinkMismatch(f'{len(recs)} deferred gradients exceed the fused launch\'s table')
         pairs = sorted(pairs, key=lambda pd: 0 if pd[0] in recs else 1)
@@ -124,7 +106,7 @@ class FusedAdam:
                     raise _lib.KgwasHipError('finish_into needs contiguous fp32 gradients and bucket slots of the same size')
                 D[k], G[k], N[k] = dst.data_ptr(), g.data_ptr(), g.numel()
                 if p in recs:
-                    C.memmove(C.byref(S[k]), C.byref(recs[p][0]), C.sizeof(_lib.KgwGradSrc))
+                    C.memmove(C.byref(S[k]), C.byref(recs[p].src), C.sizeof(_lib.KgwGradSrc))
             _lib.check(_lib.lib().kgw_grad_finish(n, D, G, N, S, _lib.stream_ptr()), 'kgw_grad_finish')
 
     @torch.no_grad()

@@ -42,7 +42,7 @@ def test_deferred_product_of_the_grad_sink():
     """GradSink._tn_jobs: raw addresses for the outputs (no second tensor reference), dense [M, N] and [M], the row count on the device."""
     dY, X, rows_dev = torch.randn(300, 128), torch.randn(300, 64), torch.tensor([290], dtype=torch.int32)
     dW, db = torch.empty(128, 64), torch.empty(128)
-    jobs, src, keep = ops.GradSink()._tn_jobs([(dY, X, dW.data_ptr(), db.data_ptr(), None, None, rows_dev)])
+    jobs, src, keep = ops.GradSink()._tn_jobs([ops.DeferredProduct(dY, X, dW.data_ptr(), db.data_ptr(), None, rows_dev)])
     assert len(jobs) == 1 and len(src) == 2 and len(keep) == 1
     _check(jobs[0], keep[0], dY, X, C=dW.data_ptr(), ldc=64, colsum_a=db.data_ptr(), colsum_ld=128, rows_dev=rows_dev.data_ptr(),
            c_transposed=0, colsum_repeat=1)
