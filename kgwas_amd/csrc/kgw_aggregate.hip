@@ -595,11 +595,12 @@ __global__ void __launch_bounds__(KGW_BLK) __attribute__((amdgpu_waves_per_eu(4,
         dsum += kgw_sum8(dsum_own);                            // lanes 0..7 of each half: the edges handled 8 at a time
         if (P.part_du) {
             ua.x += kgw_xhalf(ua.x); ua.y += kgw_xhalf(ua.y); ua.z += kgw_xhalf(ua.z); ua.w += kgw_xhalf(ua.w);
-            // (DROP: the lane's offset into the record is formed here, from an opaque copy of hl -- hoisted into the prologue, as the
-            //  plain instantiation's is, the address is the one value that no longer fits the 128 registers of four waves per SIMD
-            //  and goes through scratch once per chunk)
+            // (the lane's offset into the record is formed here, from an opaque copy of hl -- hoisted into the prologue, the
+            //  address P.part_du + 16 hl is the one value that no longer fits the 128 registers of four waves per SIMD: it was
+            //  spilled there and came back through scratch once per chunk, one more memory round trip at the end of the wave's
+            //  dependent chain.  Every instantiation: ScratchSize 0)
             int hls = hl;
-            if (DROP) __asm__ volatile("" : "+v"(hls));
+            __asm__ volatile("" : "+v"(hls));
             if (half == 0) ((float4*)(P.part_du + (int64_t)c * KGW_C))[hls] = ua;
         }
         esum += kgw_sum8(esum_own); bsum += kgw_sum8(bsum_own); ssum += kgw_sum8(ssum_own);

@@ -1217,35 +1217,29 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
     const int ntiles = (int)((rows + 31) / 32);
     const int nw = (int)gridDim.x * 4;
     float* Tw = Tl + wave * 32 * TS2;
-    // the operand image: entry (s, p, jt, lane) = piece p of W2[o = 64 lk + 8 s + i][32 jt + li], i = 0..7 -- the eight values of
-    // dH2 lane group lk multiplies in step s (its half row, in order)
-    for (int idx = tid; idx < 8 * 4 * 64; idx += 256) {
-        const int ln = idx & 63, jt = (idx >> 6) & 3, s_ = idx >> 8;
-        const float* wp = a.W2 + (int64_t)(64 * (ln >> 5) + 8 * s_) * a.ldw + 32 * jt + (ln & 31);
-        float x[8];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) x[i] = wp[(int64_t)i * a.ldw];
-        uint4 p1, p2, p3;
-        kgw_split3x8(x, p1, p2, p3);
-        uint4* o = W2p + ((s_ * 3) * 4 + jt) * 64 + ln;
-        o[0] = p1; o[4 * 64] = p2; o[8 * 64] = p3;
-    }
-    __syncthreads();
-    const uint4* w2p = W2p + lane;
-    f32x16 accw[4];
-#pragma unroll
-    for (int t = 0; t < 4; ++t)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) accw[t][e] = 0.f;
     const int K1 = a.K1;
     int tile = (int)blockIdx.x * 4 + wave;
-    f32x4 xa[16];
+    // Prologue, in the order of its memory round trips: the first tile's in_ids entry, the thread's 64 scalars of W2, then (behind
+    // in_ids) the first tile's dH2 half row and mask rows -- all requested before the first split, so that the image loop's waits
+    // are one vmcnt ladder and the tile's rows arrive under it (the gene launch has one tile per wavefront: nothing else hides them).
     int src_cur;                                              // input row of this lane's row (-1: none -> zero row)
+    int64_t r_first = (int64_t)(tile < ntiles ? tile : ntiles - 1) * 32 + li;
+    if (r_first >= rows) r_first = rows - 1;
+    src_cur = a.in_ids ? a.in_ids[r_first] : 0;
+    // the operand image: entry (s, p, jt, lane) = piece p of W2[o = 64 lk + 8 s + i][32 jt + li], i = 0..7 -- the eight values of
+    // dH2 lane group lk multiplies in step s (its half row, in order); thread tid holds (jt, lane) = (wave, lane) of every step s
+    float wx[8][8];
     {
-        int64_t r = (int64_t)(tile < ntiles ? tile : ntiles - 1) * 32 + li;
-        if (r >= rows) r = rows - 1;
-        src_cur = a.in_ids ? a.in_ids[r] : 0;
-        const float* xp = a.dH2 + (a.in_ids ? (int64_t)(src_cur < 0 ? 0 : src_cur) : r) * a.ldd + lk * 64;
+        const float* wp = a.W2 + (int64_t)(64 * lk) * a.ldw + 32 * wave + li;
+#pragma unroll
+        for (int s_ = 0; s_ < 8; ++s_)
+#pragma unroll
+            for (int i = 0; i < 8; ++i) wx[s_][i] = wp[(int64_t)(8 * s_ + i) * a.ldw];
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    f32x4 xa[16];
+    {
+        const float* xp = a.dH2 + (a.in_ids ? (int64_t)(src_cur < 0 ? 0 : src_cur) : r_first) * a.ldd + lk * 64;
 #pragma unroll
         for (int q = 0; q < 16; ++q) xa[q] = *(const f32x4*)(xp + 4 * q);
     }
@@ -1261,17 +1255,30 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
         MB[t_ >> 1] |= (MV[t_][g].w > 0.f ? 1u : 0u) << (b0 + 3);                                        \
     }
     unsigned mb[2] = {0u, 0u};
+    f32x4 mv0[4][4];
     {
-        int64_t r = (int64_t)(tile < ntiles ? tile : ntiles - 1) * 32 + li;
-        if (r >= rows) r = rows - 1;
-        const float* mp = a.H1 + r * a.ldm + 4 * lk;
-        f32x4 mv[4][4];
+        const float* mp = a.H1 + r_first * a.ldm + 4 * lk;
 #pragma unroll
         for (int t_ = 0; t_ < 4; ++t_)
 #pragma unroll
-            for (int g = 0; g < 4; ++g) mv[t_][g] = *(const f32x4*)(mp + t_ * 32 + 8 * g);
-        KGW_MLPB_BITS(mv, mb)
+            for (int g = 0; g < 4; ++g) mv0[t_][g] = *(const f32x4*)(mp + t_ * 32 + 8 * g);
     }
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int s_ = 0; s_ < 8; ++s_) {
+        uint4 p1, p2, p3;
+        kgw_split3x8(wx[s_], p1, p2, p3);
+        uint4* o = W2p + ((s_ * 3) * 4 + wave) * 64 + lane;
+        o[0] = p1; o[4 * 64] = p2; o[8 * 64] = p3;
+    }
+    __syncthreads();
+    const uint4* w2p = W2p + lane;
+    f32x16 accw[4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) accw[t][e] = 0.f;
+    KGW_MLPB_BITS(mv0, mb)
     for (; tile < ntiles; tile += nw) {
         const int64_t r0 = (int64_t)tile * 32;
         const int64_t row = r0 + li;
@@ -1287,14 +1294,19 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
             xn = a.dH2 + (a.in_ids ? (int64_t)(src_cur < 0 ? 0 : src_cur) : r) * a.ldd + lk * 64;
         }
         // x' in "k per lane" form for the second product: lane (k = li, row parity lk), step s = row pair (needed after
-        // the first product: the loads ride under its MFMAs)
+        // the first product: the loads ride under its MFMAs).  Every lane loads -- a clamped element where it has none, dH2 where
+        // there is no X at all -- and selects afterwards: a load under a lane condition is a branch, and behind 16 of them the wait
+        // for the dH2 half row (requested a tile ago) became vmcnt(0), one exposed round trip of these loads at every tile's start
         float xs[16];
+        {
+            const float* xb = K1 > 0 ? a.X + (li < K1 ? li : K1 - 1) : a.dH2;
+            const int64_t ldxs = K1 > 0 ? a.ldx : 0;
 #pragma unroll
-        for (int s2 = 0; s2 < 16; ++s2) {
-            const int64_t rr = r0 + 2 * s2 + lk;
-            float v = 0.f;
-            if (rr < rows) v = li < K1 ? a.X[rr * a.ldx + li] : (li == K1 ? 1.f : 0.f);
-            xs[s2] = v;
+            for (int s2 = 0; s2 < 16; ++s2) {
+                const int64_t rr = r0 + 2 * s2 + lk;
+                const float xv = xb[(rr < rows ? rr : rows - 1) * ldxs];
+                xs[s2] = rr < rows ? (li < K1 ? xv : (li == K1 ? 1.f : 0.f)) : 0.f;
+            }
         }
         // the NEXT tile's mask rows: requested now, read after this tile's second product
         f32x4 mvn[4][4];
@@ -1314,7 +1326,14 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
         for (int t = 0; t < 4; ++t)
 #pragma unroll
             for (int e = 0; e < 16; ++e) acc[t][e] = 0.f;
-        // first product on the bf16 pipe (three exact pieces per operand): 8 steps x 6 piece products x 4 column tiles
+        // first product on the bf16 pipe (three exact pieces per operand): 8 steps x 6 piece products x 4 column tiles; the W2
+        // operands of step s + 1 are asked for in front of step s's MFMAs (one wavefront per SIMD: a read issued right in front of
+        // the MFMA that needs it is a read waited for; the compiler keeps part of that distance, the SNP launch 52 -> 50 us)
+        kgw_bf8 wn[3][4];
+#pragma unroll
+        for (int p = 0; p < 3; ++p)
+#pragma unroll
+            for (int jt = 0; jt < 4; ++jt) wn[p][jt] = __builtin_bit_cast(kgw_bf8, w2p[(p * 4 + jt) * 64]);
 #pragma unroll
         for (int s_ = 0; s_ < 8; ++s_) {
             const f32x4 u = xa[2 * s_], v = xa[2 * s_ + 1];
@@ -1329,7 +1348,13 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
 #pragma unroll
             for (int p = 0; p < 3; ++p)
 #pragma unroll
-                for (int jt = 0; jt < 4; ++jt) wa[p][jt] = __builtin_bit_cast(kgw_bf8, w2p[((s_ * 3 + p) * 4 + jt) * 64]);
+                for (int jt = 0; jt < 4; ++jt) wa[p][jt] = wn[p][jt];
+            if (s_ + 1 < 8) {
+#pragma unroll
+                for (int p = 0; p < 3; ++p)
+#pragma unroll
+                    for (int jt = 0; jt < 4; ++jt) wn[p][jt] = __builtin_bit_cast(kgw_bf8, w2p[(((s_ + 1) * 3 + p) * 4 + jt) * 64]);
+            }
             constexpr int TW[6] = {0, 2, 1, 0, 1, 0}, TH[6] = {2, 0, 1, 1, 0, 0};       // (piece of W2, piece of dH2), smallest first
 #pragma unroll
             for (int t6 = 0; t6 < 6; ++t6)

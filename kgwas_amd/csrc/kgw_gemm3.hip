@@ -129,7 +129,9 @@ __global__ void __launch_bounds__(64 * NW, (8 / NW) / MT) k_g3_gemm(G3KArgs ka_)
     // the compute units the product leaves idle (240 blocks of one CU each on 256 CUs at the benchmark shape)
     if ((int)blockIdx.x >= a.per_xcd * 8) {
         // (the rider functions are real calls -- their registers are their own, the product's loop keeps its allocation -- and
-        //  take their tables by ADDRESS in the kernarg segment: a by-value struct whose address escapes would be copied to scratch)
+        //  take their tables by ADDRESS in the kernarg segment: a by-value struct whose address escapes would be copied to scratch.
+        //  The 156 bytes per lane of scratch the kernel reports are the stack of this one call: the kernel's own code holds a single
+        //  s_swappc, here, and no scratch instruction -- the product's blocks below never touch it)
         const char* kseg = (const char*)__builtin_amdgcn_kernarg_segment_ptr();
         const G3Riders* R = (const G3Riders*)(kseg + __builtin_offsetof(G3KArgs, R));
         if (ka_.R.n_blocks) g3_param_riders<NW>(*R, (int)blockIdx.x - a.per_xcd * 8);
