@@ -641,6 +641,28 @@ __global__ void __launch_bounds__(KGW_BLK) k_agg_bwd_combine(LayerTab T, AggPtrs
 // ------------------------------------------------------------------------------------------------
 // backward, src-major pass: one wavefront per source row
 // ------------------------------------------------------------------------------------------------
+// k_agg_bwd_src is pinned to 6 wavefronts per SIMD (80 VGPRs): its path is a chain of dependent loads, and what it wants is more
+// independent chains in flight, not longer ones (profiles/bwd_src_occupancy/).  The three row paths share one kernel, so whatever
+// the compiler hoists out of one path is live across the others; the helpers below keep that set small.
+//
+// The lane id of a row path, formed inside the path: opaque to the compiler, so the lane masks, per-lane addresses and
+// predicates derived from it are computed where they are used -- hoisted to the top of the kernel they stay live across all
+// three paths (it cost 14 VGPRs and part of the scalar spills).
+__device__ __forceinline__ int bsrc_lane() {
+    int l = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+    __asm__ volatile("" : "+v"(l));
+    return l;
+}
+// Shuffles of the row paths: the value of lane `src` (0..63), one ds_bpermute on a byte index.  __shfl adds the caller's own
+// lane id to the index: two more VALU operations per shuffle, and that lane id kept in a register for the whole kernel.
+__device__ __forceinline__ int bsrc_shfl(int v, int src) { return __builtin_amdgcn_ds_bpermute(src << 2, v); }
+__device__ __forceinline__ float bsrc_shfl(float v, int src) {
+    return __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(src << 2, __builtin_bit_cast(int, v)));
+}
+__device__ __forceinline__ float bsrc_readlane(float v, int k) {      // k wave-uniform
+    return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), k));
+}
+
 template <int G>
 __device__ __forceinline__ void src_group(const float4* __restrict__ dZ4, int tz, float al, int q0, int hn,
                                           int nb, int half, int hl, float4& acc) {
@@ -651,8 +673,8 @@ __device__ __forceinline__ void src_group(const float4* __restrict__ dZ4, int tz
         const int q = q0 + p;
         const int i = half * hn + q;
         const bool valid = (q < hn) && (i < nb);
-        const int z = __shfl(tz, valid ? i : 0, 64);
-        const float a = __shfl(al, valid ? i : 0, 64);
+        const int z = bsrc_shfl(tz, valid ? i : 0);
+        const float a = bsrc_shfl(al, valid ? i : 0);
         w[p] = valid ? a : 0.f;
         x[p] = dZ4[(int64_t)z * 32 + hl];
     }
@@ -662,7 +684,7 @@ __device__ __forceinline__ void src_group(const float4* __restrict__ dZ4, int tz
 
 // one wavefront, one source row (rows with many entries; rows whose neighbour cannot be paired)
 __device__ __forceinline__ void bwd_src_one_row(const LayerTab& T, const AggPtrs& P, int u) {
-    const int lane = kgw_lane(), half = lane >> 5, hl = lane & 31;
+    const int lane = bsrc_lane(), half = lane >> 5, hl = lane & 31;
     const float4* dZ4 = (const float4*)P.dZ;
     {
         int ty = 0;
@@ -671,15 +693,17 @@ __device__ __forceinline__ void bwd_src_one_row(const LayerTab& T, const AggPtrs
         const int Rs = T.type_R_src[ty];
         const int tb = T.type_t_base[ty] + j * Rs;
         if (j >= P.meta->n_src[P.layer - 1][ty]) {          // padding row of a static layout: no gradient
-            if (half == 0) ((float4*)(P.dH + (int64_t)u * KGW_C))[hl] = make_float4(0.f, 0.f, 0.f, 0.f);
+            float z0 = 0.f;
+            __asm__ volatile("" : "+v"(z0));                  // (formed here: a zero row held in registers across the three paths spilled)
+            if (half == 0) ((float4*)(P.dH + (int64_t)u * KGW_C))[hl] = make_float4(z0, z0, z0, z0);
             if (P.da_src) for (int c = lane; c < 2 * T.ld_da; c += 64) P.da_src[(int64_t)u * 2 * T.ld_da + c] = 0.f;
             return;
         }
         // all Rs + 1 row pointers of this source in ONE load (lane k holds t_ptr[tb + k]); the per-slot logic below
         // works on shuffles of it instead of a chain of dependent scalar loads
         const int tpv = (lane <= Rs) ? P.t_ptr[tb + lane] : 0;
-        const int p0 = __shfl(tpv, 0, 64), p1 = __shfl(tpv, Rs, 64);
-        const int tpn = __shfl_down(tpv, 1, 64);
+        const int p0 = __builtin_amdgcn_readlane(tpv, 0), p1 = __builtin_amdgcn_readlane(tpv, Rs);
+        const int tpn = bsrc_shfl(tpv, min(lane + 1, 63));
         const unsigned long long slots = __ballot(lane < Rs && tpn > tpv);      // bit k: slot k has entries
         float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
         float dasv = 0.f;                                    // lane k holds d a_src of slot k
@@ -703,12 +727,14 @@ __device__ __forceinline__ void bwd_src_one_row(const LayerTab& T, const AggPtrs
                 const int s0 = __builtin_amdgcn_readlane(tpv, k);
                 if (s0 > pb && s0 < pb + nb) heads |= 1ull << (s0 - pb);
             }
+            // (hd = the head of this lane's segment, bit 0 of `heads` being set: the value d lanes down belongs to the same
+            //  segment exactly when it is not below hd -- one register instead of a 64-bit lane mask per step)
+            const int hd = 63 - __builtin_clzll(heads & ((2ull << lane) - 1ull));
             float sv = (lane < nb) ? dp : 0.f;
 #pragma unroll
             for (int d = 1; d < 64; d <<= 1) {
-                const float o = __shfl_up(sv, d, 64);
-                const bool open = lane >= d && ((heads >> (lane - d + 1)) & ((1ull << d) - 1ull)) == 0ull;
-                sv += open ? o : 0.f;
+                const float o = bsrc_shfl(sv, lane >= d ? lane - d : lane);
+                sv += (lane - d >= hd) ? o : 0.f;
             }
             for (unsigned long long left = slots; left; left &= left - 1) {
                 const int k = __builtin_ctzll(left);
@@ -725,13 +751,13 @@ __device__ __forceinline__ void bwd_src_one_row(const LayerTab& T, const AggPtrs
                 else              { src_group<2>(dZ4, tz, al, q0, hn, nb, half, hl, acc); q0 += 2; }
             }
         }
-        acc.x += kgw_xhalf(acc.x); acc.y += kgw_xhalf(acc.y);
-        acc.z += kgw_xhalf(acc.z); acc.w += kgw_xhalf(acc.w);
+        acc.x += bsrc_shfl(acc.x, lane ^ 32); acc.y += bsrc_shfl(acc.y, lane ^ 32);
+        acc.z += bsrc_shfl(acc.z, lane ^ 32); acc.w += bsrc_shfl(acc.w, lane ^ 32);
         if (p1 > p0) {
             // d a_src flows back into h_src through a_s = <h_src, u_r>
             for (unsigned long long left = slots; left; left &= left - 1) {
                 const int k = __builtin_ctzll(left);
-                const float dk = __shfl(dasv, k, 64);
+                const float dk = bsrc_readlane(dasv, k);
                 if (dk != 0.f) {
                     const int r = T.rel_of_slot[ty][k];
                     const float4 u4 = ((const float4*)(P.U + (int64_t)r * KGW_C))[hl];
@@ -746,7 +772,7 @@ __device__ __forceinline__ void bwd_src_one_row(const LayerTab& T, const AggPtrs
         if (is_dst) {
             const float dav = (lane < Rd) ? P.da_dst[zb + lane] : 0.f;
             for (int k = 0; k < Rd; ++k) {
-                const float dk = __shfl(dav, k, 64);
+                const float dk = bsrc_readlane(dav, k);
                 if (dk != 0.f) {
                     const int r = T.rel_of_dslot[ty][k];
                     const float4 v4 = ((const float4*)(P.V + (int64_t)r * KGW_C))[hl];
@@ -768,7 +794,7 @@ __device__ __forceinline__ void bwd_src_one_row(const LayerTab& T, const AggPtrs
             for (int c0 = 0; c0 < 2 * ld; c0 += 64) {
                 const int col = c0 + lane;
                 const bool mine = col < T.n_rels && T.rel_src_type[col] == ty;
-                const float v = __shfl(dasv, mine ? T.rel_slot_src[col] : 0, 64);
+                const float v = bsrc_shfl(dasv, mine ? T.rel_slot_src[col] : 0);
                 float w = 0.f;
                 const int c = col - ld;
                 if (is_dst && c >= 0 && c < T.n_rels && T.rel_dst_type[c] == ty) w = P.da_dst[zb + T.rel_slot_dst[c]];
@@ -787,7 +813,7 @@ __device__ __forceinline__ void bwd_src_one_row(const LayerTab& T, const AggPtrs
 // SNP rows (mean 2 entries) and 99 % of the gene / GO rows (mean ~35, which hold 70 % of all entries).
 constexpr int KGW_PAIR_MAX = 128;
 __device__ __forceinline__ bool bwd_src_row_pair(const LayerTab& T, const AggPtrs& P, int u, float* wdp) {
-    const int lane = kgw_lane(), half = lane >> 5, hl = lane & 31, hb = half << 5;
+    const int lane = bsrc_lane(), half = lane >> 5, hl = lane & 31, hb = half << 5;
     int ty = 0;
     while (ty + 1 < T.n_types && u >= T.type_src_base[ty + 1]) ++ty;
     if (u + 1 >= T.type_src_base[ty + 1]) return false;                  // the neighbour is of another type
@@ -799,16 +825,16 @@ __device__ __forceinline__ bool bwd_src_row_pair(const LayerTab& T, const AggPtr
     const int j = j0 + half, uh = u + half;
     const int tb = T.type_t_base[ty] + j * Rs;
     const int tpv = (hl <= Rs) ? P.t_ptr[tb + hl] : 0;
-    const int p0 = __shfl(tpv, hb, 64), p1 = __shfl(tpv, hb + Rs, 64);
+    const int p0 = bsrc_shfl(tpv, hb), p1 = bsrc_shfl(tpv, hb + Rs);
     const int n = p1 - p0;
     if (__ballot(n > KGW_PAIR_MAX)) return false;
-    const int tpn = __shfl_down(tpv, 1, 64);
+    const int tpn = bsrc_shfl(tpv, min(lane + 1, 63));
     const unsigned long long bal = __ballot(hl < Rs && tpn > tpv);
     const unsigned slots_any = (unsigned)(bal | (bal >> 32));              // slots used by either row
     const float4* dZ4 = (const float4*)P.dZ;
     float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
     float dasv = 0.f;                                                      // lane hl == k of a half: d a_src of slot k
-    const int nall = max(__shfl(n, 0, 64), __shfl(n, 32, 64));
+    const int nall = max(bsrc_shfl(n, 0), bsrc_shfl(n, 32));
     // the rows' entries in blocks of 32 per half (gene / GO rows average ~35 entries: two blocks).  The load chain
     // entries -> (alpha, d pre-activation) / dZ rows is unrolled across blocks: the NEXT block's entries and this block's
     // alphas are requested before this block's gathers, and the gathers (which need the Z rows only) before the alphas
@@ -835,13 +861,13 @@ __device__ __forceinline__ bool bwd_src_row_pair(const LayerTab& T, const AggPtr
 #pragma unroll
             for (int q = 0; q < 8; ++q) {
                 const int i = i0 + q;
-                const int z = __shfl(tz, hb + (i < nb ? i : 0), 64);
+                const int z = bsrc_shfl(tz, hb + (i < nb ? i : 0));
                 x[q] = dZ4[(int64_t)z * 32 + hl];
             }
 #pragma unroll
             for (int q = 0; q < 8; ++q) {
                 const int i = i0 + q;
-                const float a = __shfl(a2.x, hb + (i < nb ? i : 0), 64);
+                const float a = bsrc_shfl(a2.x, hb + (i < nb ? i : 0));
                 fma4(acc, i < nb ? a : 0.f, x[q]);
             }
         }
@@ -850,13 +876,13 @@ __device__ __forceinline__ bool bwd_src_row_pair(const LayerTab& T, const AggPtr
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 const int i = i0 + q;
-                const int z = __shfl(tz, hb + (i < nb ? i : 0), 64);
+                const int z = bsrc_shfl(tz, hb + (i < nb ? i : 0));
                 x[q] = dZ4[(int64_t)z * 32 + hl];
             }
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 const int i = i0 + q;
-                const float a = __shfl(a2.x, hb + (i < nb ? i : 0), 64);
+                const float a = bsrc_shfl(a2.x, hb + (i < nb ? i : 0));
                 fma4(acc, i < nb ? a : 0.f, x[q]);
             }
         }
@@ -877,7 +903,7 @@ __device__ __forceinline__ bool bwd_src_row_pair(const LayerTab& T, const AggPtr
     // d a_src flows back into h_src through a_s = <h_src, u_r>
     for (unsigned left = slots_any; left; left &= left - 1) {
         const int k = __builtin_ctz(left);
-        const float dk = __shfl(dasv, hb + k, 64);
+        const float dk = bsrc_shfl(dasv, hb + k);
         const int r = T.rel_of_slot[ty][k];
         const float4 u4 = ((const float4*)(P.U + (int64_t)r * KGW_C))[hl];
         fma4(acc, dk, u4);
@@ -889,7 +915,7 @@ __device__ __forceinline__ bool bwd_src_row_pair(const LayerTab& T, const AggPtr
     if (__ballot(is_dst)) {
         const float dav = (is_dst && hl < Rd) ? P.da_dst[zb + hl] : 0.f;
         for (int k = 0; k < Rd; ++k) {
-            const float dk = __shfl(dav, hb + k, 64);
+            const float dk = bsrc_shfl(dav, hb + k);
             if (__ballot(dk != 0.f)) {
                 const int r = T.rel_of_dslot[ty][k];
                 const float4 v4 = ((const float4*)(P.V + (int64_t)r * KGW_C))[hl];
@@ -910,7 +936,7 @@ __device__ __forceinline__ bool bwd_src_row_pair(const LayerTab& T, const AggPtr
         for (int c0 = 0; c0 < ld; c0 += 32) {                 // (more than 32 relations: a second round)
             const int col = c0 + hl;
             const bool mine = col < T.n_rels && T.rel_src_type[col] == ty;
-            const float v = __shfl(dasv, hb + (mine ? T.rel_slot_src[col] : 0), 64);
+            const float v = bsrc_shfl(dasv, hb + (mine ? T.rel_slot_src[col] : 0));
             float w = 0.f;
             if (is_dst && col < T.n_rels && T.rel_dst_type[col] == ty) w = P.da_dst[zb + T.rel_slot_dst[col]];
             if (col < ld) { row[col] = mine ? v : 0.f; row[ld + col] = w; }
@@ -927,16 +953,24 @@ __device__ __forceinline__ bool bwd_src_row_pair(const LayerTab& T, const AggPtr
 // a_src is sum_e dpre_e u_rel(e), entry by entry.  Which octets qualify is decided by the sampler (oct_flags: eight real rows
 // of one short-row type, no destination row -- the seeds have a d a_dst term --, at most 8 entries each).
 __device__ __forceinline__ void bwd_src_octet(const LayerTab& T, const AggPtrs& P, int u0) {
-    const int lane = kgw_lane(), g = lane >> 3, gl = lane & 7, gb = g << 3;
+    const int lane = bsrc_lane(), g = lane >> 3, gl = lane & 7, gb = g << 3;
     int ty = 0;
     while (ty + 1 < T.n_types && u0 >= T.type_src_base[ty + 1]) ++ty;
     const int Rs = T.type_R_src[ty];
     const int tb = T.type_t_base[ty] + (u0 - T.type_src_base[ty]) * Rs;
     const int pv = (lane <= 8) ? P.t_ptr[tb + lane * Rs] : 0;
-    const int p0 = __shfl(pv, g, 64), n = __shfl(pv, g + 1, 64) - p0;
+    const int p0 = bsrc_shfl(pv, g), n = bsrc_shfl(pv, g + 1) - p0;
     const int u = u0 + g;
     const float4* dZ4 = (const float4*)P.dZ;
     const float4* U4 = (const float4*)P.U;
+    // the node's own row of the layer input only matters as a ReLU mask.  It depends on nothing but u: requested ahead of the
+    // row pointers' dependants and folded into 16 bits before the first gather is issued -- by then the entries, requested
+    // after it, have been waited for, so the fold waits for nothing and its 16 registers are free when the gathers land
+    float4 h4[4];
+    if (P.relu_in) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) h4[q] = ((const float4*)(P.H + (int64_t)u * KGW_C))[gl + 8 * q];
+    }
     int tz = 0, tr = 0;
     float2 a2 = make_float2(0.f, 0.f);
     if (gl < n) {
@@ -945,49 +979,37 @@ __device__ __forceinline__ void bwd_src_octet(const LayerTab& T, const AggPtrs& 
         tr = P.t_rel[p0 + gl];
         a2 = ((const float2*)P.adp)[te];
     }
-    // the node's own row of the layer input only matters as a ReLU mask: requested first, folded into 16 bits as soon as it
-    // lands (the gathers behind it stay in flight)
     unsigned mk = 0xffffu;
     float4 acc[4];
 #pragma unroll
     for (int q = 0; q < 4; ++q) acc[q] = make_float4(0.f, 0.f, 0.f, 0.f);
-    bool first = true;
-    float4 h4[4];
     if (P.relu_in) {
+        mk = 0u;
 #pragma unroll
-        for (int q = 0; q < 4; ++q) h4[q] = ((const float4*)(P.H + (int64_t)u * KGW_C))[gl + 8 * q];
+        for (int q = 0; q < 4; ++q)
+            mk |= ((h4[q].x > 0.f ? 1u : 0u) | (h4[q].y > 0.f ? 2u : 0u) | (h4[q].z > 0.f ? 4u : 0u) | (h4[q].w > 0.f ? 8u : 0u)) << (4 * q);
     }
-    // two entries per round: 8 gathers in flight per lane; the (L1-resident) u rows follow one entry at a time
-    for (int i = 0; __ballot(i < n); i += 2) {
-        float4 x[2][4];
-        float al[2], dp[2];
-        int rr[2];
+    // one entry per round: 4 gathers in flight per lane, then the entry's (L1-resident) u row -- x[4] and w[4] live once (two
+    // entries per round held them twice: 32 more registers for a path whose rows average two entries).  The rounds run to the
+    // octet's longest row rounded up to even, as the two-entry rounds did: a finished row adds 0 * x in exactly the same steps
+    int nr = 0;                                                   // (scalar: the nine row pointers sit in lanes 0..8 of pv)
 #pragma unroll
-        for (int e = 0; e < 2; ++e) {
-            const bool on = i + e < n;
-            const int z = __shfl(tz, gb + (on ? i + e : 0), 64);
-            rr[e] = __shfl(tr, gb + (on ? i + e : 0), 64);
-            const float a = __shfl(a2.x, gb + (on ? i + e : 0), 64);
-            const float d = __shfl(a2.y, gb + (on ? i + e : 0), 64);
-            al[e] = on ? a : 0.f; dp[e] = on ? d : 0.f;
+    for (int k = 0; k < 8; ++k) nr = max(nr, __builtin_amdgcn_readlane(pv, k + 1) - __builtin_amdgcn_readlane(pv, k));
+    nr = (nr + 1) & ~1;
+    for (int i = 0; i < nr; ++i) {
+        const bool on = i < n;
+        const int z = bsrc_shfl(tz, gb + (on ? i : 0));
+        const int rr = bsrc_shfl(tr, gb + (on ? i : 0));
+        const float a = bsrc_shfl(a2.x, gb + (on ? i : 0));
+        const float d = bsrc_shfl(a2.y, gb + (on ? i : 0));
+        const float al = on ? a : 0.f, dp = on ? d : 0.f;
+        float4 x[4], w[4];
 #pragma unroll
-            for (int q = 0; q < 4; ++q) x[e][q] = dZ4[(int64_t)z * 32 + gl + 8 * q];
-        }
-        if (first && P.relu_in) {
-            mk = 0u;
+        for (int q = 0; q < 4; ++q) x[q] = dZ4[(int64_t)z * 32 + gl + 8 * q];
 #pragma unroll
-            for (int q = 0; q < 4; ++q)
-                mk |= ((h4[q].x > 0.f ? 1u : 0u) | (h4[q].y > 0.f ? 2u : 0u) | (h4[q].z > 0.f ? 4u : 0u) | (h4[q].w > 0.f ? 8u : 0u)) << (4 * q);
-        }
-        first = false;
+        for (int q = 0; q < 4; ++q) w[q] = U4[rr * 32 + gl + 8 * q];
 #pragma unroll
-        for (int e = 0; e < 2; ++e) {
-            float4 w[4];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) w[q] = U4[rr[e] * 32 + gl + 8 * q];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) { fma4(acc[q], al[e], x[e][q]); fma4(acc[q], dp[e], w[q]); }
-        }
+        for (int q = 0; q < 4; ++q) { fma4(acc[q], al, x[q]); fma4(acc[q], dp, w[q]); }
     }
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
@@ -1007,8 +1029,8 @@ __device__ __forceinline__ void bwd_src_octet(const LayerTab& T, const AggPtrs& 
             float v[4] = {0.f, 0.f, 0.f, 0.f};
             for (int i = 0; __ballot(i < n); ++i) {
                 const bool on = i < n;
-                const int r = __shfl(tr, gb + (on ? i : 0), 64);
-                const float d = __shfl(a2.y, gb + (on ? i : 0), 64);
+                const int r = bsrc_shfl(tr, gb + (on ? i : 0));
+                const float d = bsrc_shfl(a2.y, gb + (on ? i : 0));
                 const int c = r - 4 * k;
                 if (on && c >= 0 && c < 4) {
                     v[0] += c == 0 ? d : 0.f; v[1] += c == 1 ? d : 0.f;
@@ -1119,22 +1141,28 @@ __global__ void __launch_bounds__(KGW_C) k_duv_fold(int n_rels, const float* __r
     (v ? dV : dU)[(int64_t)r * KGW_C + c] = s;
 }
 
-__global__ void __launch_bounds__(KGW_BLK) k_agg_bwd_src(LayerTab T, AggPtrs P, int n_src_rows, int main_blocks, int n_riders,
-                                                         float* __restrict__ rel_sums) {
+// Pinned to 6 wavefronts per SIMD: 79 VGPRs, no scratch (it compiled to 117 and 4 wavefronts unpinned).  Measured in the step,
+// layer 1 (profiles/bwd_src_occupancy/stages.txt): 4 / 5 / 6 wavefronts 105.6 / 99.0 / 91.7 us; 8 wavefronts need the row
+// paths cut to four gathers per group, which costs more than the two further wavefronts return (96.1).
+__global__ void __launch_bounds__(KGW_BLK) __attribute__((amdgpu_waves_per_eu(6, 6)))
+k_agg_bwd_src(LayerTab T, AggPtrs P, int n_src_rows, int main_blocks, int n_riders, float* __restrict__ rel_sums) {
     __shared__ float s_dp[KGW_BLK];                           // 64 floats per wavefront (bwd_src_row_pair)
     if ((int)blockIdx.x < n_riders) {
         bwd_src_rider(T, P, (int)blockIdx.x, rel_sums, s_dp);
         return;
     }
-    float* wdp = s_dp + (threadIdx.x & ~63);
+    float* wdp = s_dp + 64 * __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int nw = main_blocks * 4;
     // A wavefront takes source rows two at a time, LAST rows first: the layout is type-major with the SNPs (short rows,
     // most of the rows) in front and the genes / GO terms (longer rows) at the end -- the long rows must start at the
     // beginning of the kernel, not in its last round.  Pairs inside an octet that the sampler flagged for the short path
     // are skipped here and taken by the second loop, whose octets are dealt from the LAST wavefront down: with about
     // one pair per wavefront the low-numbered wavefronts hold the gene / GO pairs, the high-numbered ones only skipped.
-    // (Two plain loops on purpose: with the octet path inside the pair loop, or an inner loop over an unflagged octet's
-    // pairs, the general path's code got worse -- scalar-register spills -- and the kernel slower than without octets.)
+    // (Two plain loops on purpose.  About 40 k wavefronts of the benchmark's layer 1 are launched only to skip, and that is
+    //  the cheaper form: with one item per pair above oct_rows and one per octet -- an unflagged octet's four pairs in one
+    //  wavefront, or dealt over the four wavefronts of a block -- no wavefront skips, but the unflagged octets, the seeds' among
+    //  them, become chains four pairs long: layer 1 93.6 -> 99.9 us, layer 2, whose 64 SNP octets are all seeds, 8.5 -> 13.1 us.
+    //  Earlier: the octet path inside the pair loop spilled scalar registers in the general path.)
     const int npairs = (n_src_rows + 1) >> 1;
     const int w0 = ((int)blockIdx.x - n_riders) * 4 + (threadIdx.x >> 6);
     for (int i0 = w0; i0 < npairs; i0 += nw) {
