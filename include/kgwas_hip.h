@@ -20,6 +20,7 @@
 #ifndef KGWAS_HIP_H
 #define KGWAS_HIP_H
 
+#include <math.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -241,8 +242,8 @@ typedef struct KgwLayerArgs {
 
 int kgw_version(void);
 const char* kgw_status_string(int status);
-/* sizeof() of the ABI structs in the order Graph, BatchMeta, Chunk, BatchBuf, LayerArgs, TnJob, GradSrc, EdgeAttr -- lets a
- * binding verify its mirror structs (the first n; a library that predates an entry leaves it untouched).   */
+/* sizeof() of the ABI structs in the order Graph, BatchMeta, Chunk, BatchBuf, LayerArgs, TnJob, GradSrc, EdgeAttr, LrSchedule,
+ * OptimCtl -- lets a binding verify its mirror structs (the first n; a library that predates an entry leaves it untouched).   */
 int kgw_struct_sizes(int64_t* out, int n);
 
 /* Replaces: NeighborLoader.__next__ (kgwas/kgwas.py:99-113,129; torch_sparse/pyg_lib
@@ -381,6 +382,52 @@ KGWFAN_INLINE uint32_t kgwdrop_base(uint64_t word, int32_t layer) {
 }
 KGWFAN_INLINE int kgwdrop_keep(uint32_t base, uint32_t local_edge, uint32_t thresh) {
     return kgwfan_mix32(base ^ local_edge) >= thresh;
+}
+
+/* Learning-rate schedule: the rate of update t (1-based, the index the Adam kernels already form for their bias corrections:
+ * t = *step_dev + 1) as a pure function of t -- the reference trains at one rate (kgwas/kgwas.py:116), so like the dropouts this is
+ * an EXTENSION, off by default.  With s = t - 1, W = warmup_steps >= 0, N = total_steps >= 1, r = min_ratio in [0, 1] (min_lr / lr),
+ * step_size >= 1 and gamma > 0:
+ *      warm(s)  = W > 0 && s < W ? (s + 1) / W : 1
+ *      u(s)     = clamp((s - W) / max(N - W, 1), 0, 1)                    (0 while s < W, 1 from s = N on)
+ *      decay(s) = KGW_LR_CONSTANT: 1
+ *                 KGW_LR_LINEAR:   1 - (1 - r) u
+ *                 KGW_LR_COSINE:   r + (1 - r) (1 + cos(pi u)) / 2
+ *                 KGW_LR_STEP:     gamma ^ floor(max(s - W, 0) / step_size)
+ *      lr_t     = (float)((double)lr * warm * decay)                       (kgwlr_at: all arithmetic in double, rounded once)
+ * bc1, bc2 and step_size = lr_t / bc1 stay what they are.  KGW_LR_CONSTANT with W = 0 gives lr_t == lr to the bit.  t is READ FROM
+ * DEVICE MEMORY when the kernels run, so a captured step replays with a moving rate: no host copy, no capture per step.  Host and
+ * device evaluate cos / pow in double; they may differ in the last bit before the one rounding (1 float32 ulp of lr_t at most). */
+enum { KGW_LR_CONSTANT = 0, KGW_LR_LINEAR = 1, KGW_LR_COSINE = 2, KGW_LR_STEP = 3 };
+typedef struct KgwLrSchedule {
+    int32_t kind, warmup_steps, total_steps, step_size;     /* step_size: read by KGW_LR_STEP only                               */
+    float min_ratio, gamma;                                 /* min_ratio: LINEAR / COSINE; gamma: STEP                           */
+} KgwLrSchedule;
+/* 1: the schedule is one the rule above defines.  Otherwise (an unknown kind, W < 0, N < 1, step_size < 1 on STEP, min_ratio
+ * outside [0, 1], gamma not finite or <= 0) every entry point that takes it returns KGW_E_RANGE before any launch.              */
+KGWFAN_INLINE int kgwlr_valid(const KgwLrSchedule* S) {
+    if (S->kind < KGW_LR_CONSTANT || S->kind > KGW_LR_STEP || S->warmup_steps < 0 || S->total_steps < 1) return 0;
+    if (S->kind == KGW_LR_STEP && S->step_size < 1) return 0;
+    if (!(S->min_ratio >= 0.0f && S->min_ratio <= 1.0f)) return 0;
+    if (!(S->gamma > 0.0f && S->gamma <= 3.4028234663852886e38f)) return 0;
+    return 1;
+}
+KGWFAN_INLINE double kgwlr_warm(const KgwLrSchedule* S, int32_t s) {
+    return (S->warmup_steps > 0 && s < S->warmup_steps) ? (double)(s + 1) / (double)S->warmup_steps : 1.0;
+}
+KGWFAN_INLINE double kgwlr_decay(const KgwLrSchedule* S, int32_t s) {
+    const int32_t W = S->warmup_steps, span = S->total_steps - W > 1 ? S->total_steps - W : 1;
+    double u = ((double)s - (double)W) / (double)span;
+    u = u < 0.0 ? 0.0 : (u > 1.0 ? 1.0 : u);
+    const double r = (double)S->min_ratio;
+    if (S->kind == KGW_LR_LINEAR) return 1.0 - (1.0 - r) * u;
+    if (S->kind == KGW_LR_COSINE) return r + (1.0 - r) * (1.0 + cos(3.14159265358979323846 * u)) / 2.0;
+    if (S->kind == KGW_LR_STEP) return pow((double)S->gamma, (double)((s > W ? s - W : 0) / S->step_size));
+    return 1.0;
+}
+KGWFAN_INLINE float kgwlr_at(const KgwLrSchedule* S, float lr, int32_t t) {      /* t < 1 is taken as t = 1 */
+    const int32_t s = t > 1 ? t - 1 : 0;
+    return (float)((double)lr * kgwlr_warm(S, s) * kgwlr_decay(S, s));
 }
 
 /* Hidden-state dropout: x = F.dropout(x, p, training) on the OUTPUT of message-passing layer l, 1 <= l <= L - 1 (after its ReLU,
@@ -955,6 +1002,53 @@ int kgw_adam_fused(int32_t n_tensors, float* const* params, float* const* grads,
  * instead of the producers' second launches + the bucket's concatenation.                                                      */
 int kgw_grad_finish(int32_t n_tensors, float* const* dst, float* const* grads, const int64_t* numel, const KgwGradSrc* src,
                     kgw_stream_t stream);
+
+/* Optimiser controls (EXTENSIONS, see KgwLrSchedule above): a learning-rate schedule evaluated inside the Adam kernels and a
+ * clipping coefficient read from device memory.  New entry points only: the calls above keep their signatures and their bits, and
+ * the kernels behind them are the instantiations without the controls.  The feature is detected by symbol (the version stays).
+ *   sched           every thread forms lr_t = kgwlr_at(&sched, lr, t) from the t it loaded for the bias corrections.
+ *   grad_scale_dev  nullable device float: the gradient element is g * scale BEFORE + weight_decay * p -- torch's order, where
+ *                   clip_grad_norm_ scales and Adam then adds the L2 term.  The gradient TENSORS are left unscaled: unlike torch's
+ *                   in-place clip, p.grad after the step is what the backward pass wrote.
+ *   lr_out_dev      nullable device float: thread 0 of block 0 stores lr_t there.
+ * kgw_adam_ctl: kgw_adam_notick's arguments, tick (non-zero: advance *step_dev afterwards like kgw_adam) and ctl.
+ * kgw_adam_fused_ctl: kgw_adam_fused's arguments and ctl; grad_scale_dev != NULL: KGW_E_UNSUPPORTED (a deferred gradient is only
+ * finished inside the launch, so no norm of it exists before it -- clipping takes the unfused route).
+ * ctl == NULL forwards to the call without controls.  A schedule kgwlr_valid refuses: KGW_E_RANGE.  Both before any launch.      */
+typedef struct KgwOptimCtl {
+    KgwLrSchedule sched;
+    const float* grad_scale_dev;
+    float* lr_out_dev;
+} KgwOptimCtl;
+int kgw_adam_ctl(int32_t n_tensors, float* const* params, const float* const* grads, float* const* exp_avg,
+                 float* const* exp_avg_sq, const int64_t* numel, int32_t* step_dev, float lr, float beta1, float beta2,
+                 float eps, float weight_decay, int32_t tick, const KgwOptimCtl* ctl, kgw_stream_t stream);
+int kgw_adam_fused_ctl(int32_t n_tensors, float* const* params, float* const* grads, float* const* exp_avg,
+                       float* const* exp_avg_sq, const int64_t* numel, const KgwGradSrc* src, int32_t* step_dev, float lr,
+                       float beta1, float beta2, float eps, float weight_decay, const KgwBatchMeta* meta_dev, int32_t n_layers,
+                       int32_t n_hops, int64_t* stats, int32_t* done_counters, const KgwOptimCtl* ctl, kgw_stream_t stream);
+/* Host evaluation of the rule (bindings, tests): (double)kgwlr_at(sched, lr, t); NaN for a NULL or refused schedule.            */
+double kgw_lr_at(const KgwLrSchedule* sched, float lr, int32_t t);
+
+/* Global gradient norm and torch.nn.utils.clip_grad_norm_'s coefficient (norm_type 2), in two launches without atomics:
+ *   kgw_grad_norm_partial   one float64 sum of squares per work unit of KGW_GRAD_NORM_UNIT consecutive elements of ONE tensor, into
+ *                           partial[partial_offset + unit] (units numbered tensor after tensor; a tensor of n elements has
+ *                           ceil(n / unit) of them).  Inside a unit every thread squares and adds its four elements in double and
+ *                           the 256 threads' sums meet in a fixed binary tree: a unit's value depends on its elements alone.  Up to
+ *                           64 tensors per call; more tensors: further calls with the offset moved on.
+ *   kgw_grad_norm_fold      one block; one thread adds partial[0 .. count) in index order, norm = sqrt(sum) in double, and
+ *                           c = max_norm / (norm + 1e-6), scale = (float)(c >= 1 ? 1 : c).  *norm_out_dev (nullable) = (float)norm.
+ * Reruns give equal bits.  All-zero gradients: norm 0, scale exactly 1.  A NaN norm gives a NaN scale and an infinite norm the
+ * scale 0 (whose product with the infinite element is NaN): in both cases the update is not finite -- torch's default
+ * (error_if_nonfinite=False) does the same; nothing is skipped.  kgw_grad_norm_workspace_doubles: the units of n_tensors tensors =
+ * the doubles ``partial`` needs for them.  Refused before any launch: a NULL table, tensor or output: KGW_E_NULL; n_tensors outside
+ * [0, 64], a negative numel or offset, count < 1, max_norm not finite or <= 0: KGW_E_RANGE.                                      */
+#define KGW_GRAD_NORM_UNIT 1024
+int64_t kgw_grad_norm_workspace_doubles(int32_t n_tensors, const int64_t* numel);
+int kgw_grad_norm_partial(int32_t n_tensors, const float* const* grads, const int64_t* numel, double* partial,
+                          int64_t partial_offset, kgw_stream_t stream);
+int kgw_grad_norm_fold(const double* partial, int64_t count, double max_norm, float* norm_out_dev, float* scale_out_dev,
+                       kgw_stream_t stream);
 
 /* Attention vectors of all relations of a layer (kgwas/conv.py:138-151 reduced to what the path consumes):
  * U_full[r] = W_src^T att_src for every relation id r the layer computes (live_of_rel[r] = its index i in the

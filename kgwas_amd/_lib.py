@@ -133,6 +133,19 @@ class KgwSegCopy(C.Structure):
 
 ADAM_FUSED_MAX, ADAM_FUSED_SRC, ADAM_FUSED_COUNTERS = 40, 12, 65 * 32     # include/kgwas_hip.h: KGW_ADAM_FUSED_*
 
+KGW_LR_CONSTANT, KGW_LR_LINEAR, KGW_LR_COSINE, KGW_LR_STEP = 0, 1, 2, 3    # KgwLrSchedule.kind
+LR_KINDS = {'constant': KGW_LR_CONSTANT, 'linear': KGW_LR_LINEAR, 'cosine': KGW_LR_COSINE, 'step': KGW_LR_STEP}
+GRAD_NORM_UNIT = 1024                                                     # KGW_GRAD_NORM_UNIT
+
+
+class KgwLrSchedule(C.Structure):
+    _fields_ = [('kind', C.c_int32), ('warmup_steps', C.c_int32), ('total_steps', C.c_int32), ('step_size', C.c_int32),
+                ('min_ratio', C.c_float), ('gamma', C.c_float)]
+
+
+class KgwOptimCtl(C.Structure):
+    _fields_ = [('sched', KgwLrSchedule), ('grad_scale_dev', C.c_void_p), ('lr_out_dev', C.c_void_p)]
+
 
 class KgwReadoutFold(C.Structure):
     _fields_ = [('scratch', C.c_void_p), ('terms', C.c_void_p), ('dw_lin', C.c_void_p), ('db_lin', C.c_void_p), ('loss', C.c_void_p),
@@ -205,7 +218,9 @@ EXPORTS = ['kgw_version', 'kgw_status_string', 'kgw_struct_sizes', 'kgw_sample_b
            'kgw_readout_wmse_mt_train', 'kgw_readout_wmse_mtw_fwd', 'kgw_readout_wmse_mtw_bwd', 'kgw_readout_wmse_mtw_train',
            'kgw_accumulate_stats', 'kgw_accumulate_stats_tick', 'kgw_hidden_dropout',
            'kgw_layer_norm_relu_fwd', 'kgw_layer_norm_partial_floats', 'kgw_layer_norm_bwd', 'kgw_layer_norm_fold',
-           'kgw_root_linear_fwd', 'kgw_root_linear_bwd']
+           'kgw_root_linear_fwd', 'kgw_root_linear_bwd',
+           'kgw_adam_ctl', 'kgw_adam_fused_ctl', 'kgw_lr_at', 'kgw_grad_norm_partial', 'kgw_grad_norm_fold',
+           'kgw_grad_norm_workspace_doubles']
 
 _lib = None
 
@@ -380,6 +395,20 @@ def lib():
     if hasattr(L, 'kgw_root_linear_fwd'):           # (absent likewise)
         L.kgw_root_linear_fwd.argtypes = [C.c_int32, C.POINTER(KgwRootJob), C.c_int32, C.c_void_p]
         L.kgw_root_linear_bwd.argtypes = [C.c_int32, C.POINTER(KgwRootBwdJob), C.c_void_p]
+    if hasattr(L, 'kgw_adam_ctl'):                  # (absent likewise)
+        L.kgw_adam_ctl.argtypes = L.kgw_adam.argtypes[:-1] + [C.c_int32, C.POINTER(KgwOptimCtl), C.c_void_p]
+        L.kgw_adam_fused_ctl.argtypes = L.kgw_adam_fused.argtypes[:-1] + [C.POINTER(KgwOptimCtl), C.c_void_p]
+        L.kgw_lr_at.argtypes = [C.POINTER(KgwLrSchedule), C.c_float, C.c_int32]
+        L.kgw_lr_at.restype = C.c_double
+        L.kgw_grad_norm_workspace_doubles.argtypes = [C.c_int32, C.POINTER(C.c_int64)]
+        L.kgw_grad_norm_workspace_doubles.restype = C.c_int64
+        L.kgw_grad_norm_partial.argtypes = [C.c_int32, C.c_void_p, C.POINTER(C.c_int64), C.c_void_p, C.c_int64, C.c_void_p]
+        L.kgw_grad_norm_fold.argtypes = [C.c_void_p, C.c_int64, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]
+        s10 = (C.c_int64 * 10)()
+        L.kgw_struct_sizes(s10, 10)
+        if [s10[8], s10[9]] != [C.sizeof(KgwLrSchedule), C.sizeof(KgwOptimCtl)]:
+            raise KgwasHipError(f'ABI struct size mismatch: KgwLrSchedule / KgwOptimCtl library {[s10[8], s10[9]]} vs binding '
+                                f'{[C.sizeof(KgwLrSchedule), C.sizeof(KgwOptimCtl)]}')
     L.kgw_accumulate_stats.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
     L.kgw_accumulate_stats_tick.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     _lib = L
@@ -433,6 +462,12 @@ def has_root_weight() -> bool:
     """Does the loaded library have the root-weight kernels (kgw_root_linear_fwd / _bwd)?  An older library named by KGW_LIB_PATH
     for an A/B run lacks the symbols."""
     return hasattr(lib(), 'kgw_root_linear_fwd')
+
+
+def has_optim_ctl() -> bool:
+    """Does the loaded library have the optimiser controls (kgw_adam_ctl, kgw_adam_fused_ctl, kgw_grad_norm_partial / _fold:
+    learning-rate schedules and gradient-norm clipping)?  An older library named by KGW_LIB_PATH for an A/B run lacks the symbols."""
+    return hasattr(lib(), 'kgw_adam_ctl')
 
 
 KGW_ORDER_SEEDS, KGW_ORDER_BATCHES = 1, 2     # kgw_epoch_order's modes (include/kgwas_hip.h)

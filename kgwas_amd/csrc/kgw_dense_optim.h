@@ -108,10 +108,32 @@ __device__ __forceinline__ void adam_update(float& p, float g0, float& m, float&
     p = p - step_size * (m / denom);
 }
 
+// The optimiser controls (KgwOptimCtl, CTL instantiations only): the rate of this update from the schedule and the t the kernel
+// loaded anyway (kgwlr_at, a few double operations per thread), the clipping coefficient, and the rate stored for the host by one
+// thread.  Without a coefficient the gradient element is passed on as it is (no product with 1).
+__device__ __forceinline__ float adam_ctl_lr(const KgwOptimCtl& C, float lr, int t_now, float& gscale, bool& scaled) {
+    const float lr_t = kgwlr_at(&C.sched, lr, t_now);
+    scaled = C.grad_scale_dev != nullptr;
+    gscale = scaled ? *C.grad_scale_dev : 1.0f;
+    if (C.lr_out_dev && blockIdx.x == 0 && threadIdx.x == 0) *C.lr_out_dev = lr_t;
+    return lr_t;
+}
+__device__ __forceinline__ float adam_scaled(float g, float gscale) {
+#pragma clang fp contract(off)
+    return g * gscale;
+}
+
 // Work unit = 1024 consecutive elements of ONE tensor (256 threads x float4); the tensor of a unit is found once per
 // unit with wave-uniform (scalar) comparisons, not per element.
-__global__ void __launch_bounds__(256) k_adam(AdamTab T, int32_t* step, float lr, float b1, float b2, float eps, float wd) {
+// (The body is a template on CTL; the kernels keep their names: k_adam is the launch of kgw_adam / kgw_adam_notick, with the
+// arguments it always had, k_adam_ctl the one of kgw_adam_ctl.)
+template <bool CTL>
+__device__ __forceinline__ void adam_body(const AdamTab& T, const int32_t* step, float lr, float b1, float b2, float eps, float wd,
+                                          const KgwOptimCtl& C) {
     const int t_now = *step + 1;                       // every thread reads the same pre-increment value
+    float gscale = 1.0f;
+    bool scaled = false;
+    if constexpr (CTL) lr = adam_ctl_lr(C, lr, t_now, gscale, scaled);
     const float bc1 = 1.0f - powf(b1, (float)t_now);
     const float bc2 = 1.0f - powf(b2, (float)t_now);
     const float step_size = lr / bc1;
@@ -130,6 +152,12 @@ __global__ void __launch_bounds__(256) k_adam(AdamTab T, int32_t* step, float lr
             float4 p = *(float4*)(P + j), m = *(float4*)(M + j), v = *(float4*)(V + j);
             const float4 g0 = *(const float4*)(G + j);
             float pe[4] = {p.x, p.y, p.z, p.w}, ge[4] = {g0.x, g0.y, g0.z, g0.w}, me[4] = {m.x, m.y, m.z, m.w}, ve[4] = {v.x, v.y, v.z, v.w};
+            if constexpr (CTL) {
+                if (scaled) {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) ge[e] = adam_scaled(ge[e], gscale);
+                }
+            }
 #pragma unroll
             for (int e = 0; e < 4; ++e) adam_update(pe[e], ge[e], me[e], ve[e], wd, b1, b2, eps, step_size, bc2_sqrt);
             *(float4*)(M + j) = make_float4(me[0], me[1], me[2], me[3]);
@@ -138,11 +166,23 @@ __global__ void __launch_bounds__(256) k_adam(AdamTab T, int32_t* step, float lr
         } else {
             for (int64_t i = j; i < n && i < j + 4; ++i) {
                 float p = P[i], m = M[i], v = V[i];
-                adam_update(p, G[i], m, v, wd, b1, b2, eps, step_size, bc2_sqrt);
+                float g0 = G[i];
+                if constexpr (CTL) {
+                    if (scaled) g0 = adam_scaled(g0, gscale);
+                }
+                adam_update(p, g0, m, v, wd, b1, b2, eps, step_size, bc2_sqrt);
                 M[i] = m; V[i] = v; P[i] = p;
             }
         }
     }
+}
+
+__global__ void __launch_bounds__(256) k_adam(AdamTab T, int32_t* step, float lr, float b1, float b2, float eps, float wd) {
+    adam_body<false>(T, step, lr, b1, b2, eps, wd, KgwOptimCtl{});
+}
+__global__ void __launch_bounds__(256) k_adam_ctl(AdamTab T, int32_t* step, float lr, float b1, float b2, float eps, float wd,
+                                                  KgwOptimCtl C) {
+    adam_body<true>(T, step, lr, b1, b2, eps, wd, C);
 }
 
 __global__ void k_adam_tick(int32_t* step) { if (threadIdx.x == 0 && blockIdx.x == 0) *step += 1; }
@@ -151,7 +191,8 @@ __global__ void k_adam_tick(int32_t* step) { if (threadIdx.x == 0 && blockIdx.x 
 
 static int adam_launch(int32_t n_tensors, float* const* params, const float* const* grads, float* const* exp_avg,
                        float* const* exp_avg_sq, const int64_t* numel, int32_t* step_dev, float lr, float beta1,
-                       float beta2, float eps, float weight_decay, bool tick, kgw_stream_t stream_) {
+                       float beta2, float eps, float weight_decay, bool tick, const KgwOptimCtl* ctl, kgw_stream_t stream_) {
+    if (ctl && !kgwlr_valid(&ctl->sched)) return KGW_E_RANGE;
     if (n_tensors == 0) return KGW_OK;
     if (!params || !grads || !exp_avg || !exp_avg_sq || !numel || !step_dev) return KGW_E_NULL;
     if (n_tensors < 0 || n_tensors > ADAM_MAX) return KGW_E_RANGE;
@@ -170,7 +211,8 @@ static int adam_launch(int32_t n_tensors, float* const* params, const float* con
     int64_t g = T.coff[n_tensors];
     if (g > 4 * KGW_GRID) g = 4 * KGW_GRID;
     if (g < 1) g = 1;
-    k_adam<<<(int)g, 256, 0, st>>>(T, step_dev, lr, beta1, beta2, eps, weight_decay);
+    if (ctl) k_adam_ctl<<<(int)g, 256, 0, st>>>(T, step_dev, lr, beta1, beta2, eps, weight_decay, *ctl);
+    else k_adam<<<(int)g, 256, 0, st>>>(T, step_dev, lr, beta1, beta2, eps, weight_decay);
     KGW_LAUNCH_CHECK();
     if (tick) {
         k_adam_tick<<<1, 64, 0, st>>>(step_dev);
@@ -183,7 +225,7 @@ extern "C" int kgw_adam(int32_t n_tensors, float* const* params, const float* co
                         float* const* exp_avg_sq, const int64_t* numel, int32_t* step_dev, float lr, float beta1,
                         float beta2, float eps, float weight_decay, kgw_stream_t stream_) {
     return adam_launch(n_tensors, params, grads, exp_avg, exp_avg_sq, numel, step_dev, lr, beta1, beta2, eps, weight_decay, true,
-                       stream_);
+                       nullptr, stream_);
 }
 
 // the same without the launch that advances *step_dev: the caller does that later in the step (kgw_accumulate_stats_tick)
@@ -191,7 +233,20 @@ extern "C" int kgw_adam_notick(int32_t n_tensors, float* const* params, const fl
                                float* const* exp_avg_sq, const int64_t* numel, int32_t* step_dev, float lr, float beta1,
                                float beta2, float eps, float weight_decay, kgw_stream_t stream_) {
     return adam_launch(n_tensors, params, grads, exp_avg, exp_avg_sq, numel, step_dev, lr, beta1, beta2, eps, weight_decay, false,
-                       stream_);
+                       nullptr, stream_);
+}
+
+// ... with the optimiser controls (k_adam_ctl); ctl == NULL: the call above, or kgw_adam when ``tick`` is set
+extern "C" int kgw_adam_ctl(int32_t n_tensors, float* const* params, const float* const* grads, float* const* exp_avg,
+                            float* const* exp_avg_sq, const int64_t* numel, int32_t* step_dev, float lr, float beta1,
+                            float beta2, float eps, float weight_decay, int32_t tick, const KgwOptimCtl* ctl, kgw_stream_t stream_) {
+    return adam_launch(n_tensors, params, grads, exp_avg, exp_avg_sq, numel, step_dev, lr, beta1, beta2, eps, weight_decay, tick != 0,
+                       ctl, stream_);
+}
+
+extern "C" double kgw_lr_at(const KgwLrSchedule* sched, float lr, int32_t t) {
+    if (!sched || !kgwlr_valid(sched)) return (double)NAN;
+    return (double)kgwlr_at(sched, lr, t);
 }
 
 // ======================================================================================================
@@ -303,11 +358,18 @@ __device__ __forceinline__ float adam_src_sum(const KgwGradSrc& S, int64_t i, bo
 
 // UPD = false (kgw_grad_finish): no update -- the finished gradient goes to T.p[i], here the tensor's slot in a flat all-reduce
 // bucket (and into the gradient tensor itself where it was a sum of partial records); no counters, nothing read from ``step``.
-template <bool UPD>
-__global__ void __launch_bounds__(256) k_adam_fused(AdamFTab T, AdamTail Z, int32_t* step, float lr, float b1, float b2, float eps,
-                                                    float wd) {
+// CTL (kgw_adam_fused_ctl): the rate of this update from the schedule, as in k_adam_ctl; no clipping coefficient here.  The body is
+// a template on CTL; k_adam_fused<UPD> keeps its name and arguments, k_adam_fused_ctl is the launch with the controls.
+template <bool UPD, bool CTL>
+__device__ __forceinline__ void adam_fused_body(const AdamFTab& T, const AdamTail& Z, int32_t* step, float lr, float b1, float b2,
+                                                float eps, float wd, const KgwOptimCtl& C) {
     __shared__ float sm[32 * 33];                       // 16 x 64 partial sums of a sourced unit / one 32 x 33 tile (G3T)
     const int t_now = UPD ? *step + 1 : 1;             // (the counter moves only after every block has arrived at the end)
+    if constexpr (CTL) {
+        float gscale;
+        bool scaled;
+        lr = adam_ctl_lr(C, lr, t_now, gscale, scaled);
+    }
     const float bc1 = 1.0f - powf(b1, (float)t_now);
     const float bc2 = 1.0f - powf(b2, (float)t_now);
     const float step_size = lr / bc1;
@@ -474,15 +536,28 @@ __global__ void __launch_bounds__(256) k_adam_fused(AdamFTab T, AdamTail Z, int3
     }
 }
 
+template <bool UPD>
+__global__ void __launch_bounds__(256) k_adam_fused(AdamFTab T, AdamTail Z, int32_t* step, float lr, float b1, float b2, float eps,
+                                                    float wd) {
+    adam_fused_body<UPD, false>(T, Z, step, lr, b1, b2, eps, wd, KgwOptimCtl{});
+}
+__global__ void __launch_bounds__(256) k_adam_fused_ctl(AdamFTab T, AdamTail Z, int32_t* step, float lr, float b1, float b2, float eps,
+                                                        float wd, KgwOptimCtl C) {
+    adam_fused_body<true, true>(T, Z, step, lr, b1, b2, eps, wd, C);
+}
+
 }  // namespace
 
 static int adam_fused_table(AdamFTab& T, int32_t n_tensors, float* const* params, float* const* grads, float* const* exp_avg,
                             float* const* exp_avg_sq, const int64_t* numel, const KgwGradSrc* src);
 
-extern "C" int kgw_adam_fused(int32_t n_tensors, float* const* params, float* const* grads, float* const* exp_avg,
-                              float* const* exp_avg_sq, const int64_t* numel, const KgwGradSrc* src, int32_t* step_dev, float lr,
-                              float beta1, float beta2, float eps, float weight_decay, const KgwBatchMeta* meta_dev,
-                              int32_t n_layers, int32_t n_hops, int64_t* stats, int32_t* done_counter, kgw_stream_t stream_) {
+static int adam_fused_launch(int32_t n_tensors, float* const* params, float* const* grads, float* const* exp_avg,
+                             float* const* exp_avg_sq, const int64_t* numel, const KgwGradSrc* src, int32_t* step_dev, float lr,
+                             float beta1, float beta2, float eps, float weight_decay, const KgwBatchMeta* meta_dev,
+                             int32_t n_layers, int32_t n_hops, int64_t* stats, int32_t* done_counter, const KgwOptimCtl* ctl,
+                             kgw_stream_t stream_) {
+    if (ctl && !kgwlr_valid(&ctl->sched)) return KGW_E_RANGE;
+    if (ctl && ctl->grad_scale_dev) return KGW_E_UNSUPPORTED;          // (no norm of a gradient that is finished in this launch)
     if (n_tensors < 0 || n_tensors > KGW_ADAM_FUSED_MAX) return KGW_E_RANGE;
     if (!step_dev || !done_counter) return KGW_E_NULL;
     if (n_tensors > 0 && (!params || !grads || !exp_avg || !exp_avg_sq || !numel)) return KGW_E_NULL;
@@ -494,9 +569,28 @@ extern "C" int kgw_adam_fused(int32_t n_tensors, float* const* params, float* co
     int64_t g = T.coff[n_tensors];
     if (g > 4 * KGW_GRID) g = 4 * KGW_GRID;
     if (g < 1) g = 1;
-    k_adam_fused<true><<<(int)g, 256, 0, (hipStream_t)stream_>>>(T, Z, step_dev, lr, beta1, beta2, eps, weight_decay);
+    if (ctl) k_adam_fused_ctl<<<(int)g, 256, 0, (hipStream_t)stream_>>>(T, Z, step_dev, lr, beta1, beta2, eps, weight_decay, *ctl);
+    else k_adam_fused<true><<<(int)g, 256, 0, (hipStream_t)stream_>>>(T, Z, step_dev, lr, beta1, beta2, eps, weight_decay);
     KGW_LAUNCH_CHECK();
     return KGW_OK;
+}
+
+extern "C" int kgw_adam_fused(int32_t n_tensors, float* const* params, float* const* grads, float* const* exp_avg,
+                              float* const* exp_avg_sq, const int64_t* numel, const KgwGradSrc* src, int32_t* step_dev, float lr,
+                              float beta1, float beta2, float eps, float weight_decay, const KgwBatchMeta* meta_dev,
+                              int32_t n_layers, int32_t n_hops, int64_t* stats, int32_t* done_counter, kgw_stream_t stream_) {
+    return adam_fused_launch(n_tensors, params, grads, exp_avg, exp_avg_sq, numel, src, step_dev, lr, beta1, beta2, eps, weight_decay,
+                             meta_dev, n_layers, n_hops, stats, done_counter, nullptr, stream_);
+}
+
+// ... with the optimiser controls (k_adam_fused_ctl); ctl == NULL: the call above
+extern "C" int kgw_adam_fused_ctl(int32_t n_tensors, float* const* params, float* const* grads, float* const* exp_avg,
+                                  float* const* exp_avg_sq, const int64_t* numel, const KgwGradSrc* src, int32_t* step_dev, float lr,
+                                  float beta1, float beta2, float eps, float weight_decay, const KgwBatchMeta* meta_dev,
+                                  int32_t n_layers, int32_t n_hops, int64_t* stats, int32_t* done_counter, const KgwOptimCtl* ctl,
+                                  kgw_stream_t stream_) {
+    return adam_fused_launch(n_tensors, params, grads, exp_avg, exp_avg_sq, numel, src, step_dev, lr, beta1, beta2, eps, weight_decay,
+                             meta_dev, n_layers, n_hops, stats, done_counter, ctl, stream_);
 }
 
 // The gradients of a multi-GPU step on their way into the all-reduce bucket: dst[i] = the finished gradient of tensor i -- a copy of
@@ -558,5 +652,127 @@ static int adam_fused_table(AdamFTab& T, int32_t n_tensors, float* const* params
         T.coff[i + 1] = T.coff[i] + (numel[i] + per - 1) / per;
         T.vec[i] = (((uintptr_t)params[i] | (uintptr_t)grads[i] | (uintptr_t)exp_avg[i] | (uintptr_t)exp_avg_sq[i]) & 15) == 0;
     }
+    return KGW_OK;
+}
+
+// ======================================================================================================
+// kgw_grad_norm_partial / kgw_grad_norm_fold: the global 2-norm of up to 64 gradient tensors and torch's clip_grad_norm_
+// coefficient, for kgw_adam_ctl's grad_scale_dev.  Work unit = k_adam's (1024 consecutive elements of ONE tensor, 256 threads x 4):
+// a unit's float64 sum of squares is formed from its elements alone -- four squares per thread added pairwise, the threads' sums in
+// a binary tree through LDS -- so it does not depend on the grid, on the other tensors or on which of the two load paths ran.  The
+// fold is one block: the units staged through LDS 1024 at a time and added by one thread in index order.  No atomics.
+// ======================================================================================================
+namespace {
+
+struct NormTab {
+    const float* g[ADAM_MAX];
+    int64_t off[ADAM_MAX + 1];      // prefix sums of element counts
+    int64_t coff[ADAM_MAX + 1];     // prefix sums of work units
+    unsigned char vec[ADAM_MAX];    // 16-byte aligned: float4 path
+    int n;
+};
+
+__global__ void __launch_bounds__(256) k_grad_norm_partial(NormTab T, double* __restrict__ partial) {
+    __shared__ double sm[256];
+    const int64_t units = T.coff[T.n];
+    for (int64_t c = blockIdx.x; c < units; c += gridDim.x) {
+        int lo = 0, hi = T.n;
+        while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (T.coff[mid] <= c) lo = mid; else hi = mid; }
+        const int64_t n = T.off[lo + 1] - T.off[lo];
+        const int64_t j = (c - T.coff[lo]) * KGW_GRAD_NORM_UNIT + (int64_t)threadIdx.x * 4;
+        const float* __restrict__ G = T.g[lo];
+        float x[4] = {0.f, 0.f, 0.f, 0.f};
+        if (j + 4 <= n && T.vec[lo]) {
+            const float4 g4 = *(const float4*)(G + j);
+            x[0] = g4.x; x[1] = g4.y; x[2] = g4.z; x[3] = g4.w;
+        } else {
+            for (int e = 0; e < 4; ++e)
+                if (j + e < n) x[e] = G[j + e];
+        }
+        const double d0 = (double)x[0], d1 = (double)x[1], d2 = (double)x[2], d3 = (double)x[3];
+        sm[threadIdx.x] = (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3);     // (a product of two floats is exact in double)
+        __syncthreads();
+#pragma unroll
+        for (int s = 128; s > 0; s >>= 1) {
+            if ((int)threadIdx.x < s) sm[threadIdx.x] += sm[threadIdx.x + s];
+            __syncthreads();
+        }
+        if (threadIdx.x == 0) partial[c] = sm[0];
+        __syncthreads();                                               // (sm is reused by the block's next unit)
+    }
+}
+
+// (1024 threads: a model's ~1 600 units are two rounds of one global load per thread; the chain is thread 0's additions)
+__global__ void __launch_bounds__(1024) k_grad_norm_fold(const double* __restrict__ partial, int64_t count, double max_norm,
+                                                         float* __restrict__ norm_out, float* __restrict__ scale_out) {
+    __shared__ double sm[1024];
+    double sum = 0.0;
+    for (int64_t b = 0; b < count; b += 1024) {
+        const int64_t i = b + threadIdx.x;
+        sm[threadIdx.x] = i < count ? partial[i] : 0.0;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            const int m = count - b < 1024 ? (int)(count - b) : 1024;
+            int k = 0;
+            for (; k + 16 <= m; k += 16) {                              // (sixteen LDS reads in flight, added in index order)
+                double x[16];
+#pragma unroll
+                for (int q = 0; q < 16; ++q) x[q] = sm[k + q];
+#pragma unroll
+                for (int q = 0; q < 16; ++q) sum += x[q];
+            }
+            for (; k < m; ++k) sum += sm[k];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        const double norm = sqrt(sum);
+        const double c = max_norm / (norm + 1e-6);
+        if (norm_out) *norm_out = (float)norm;
+        *scale_out = (float)(c >= 1.0 ? 1.0 : c);                       // (a NaN stays a NaN)
+    }
+}
+
+}  // namespace
+
+extern "C" int64_t kgw_grad_norm_workspace_doubles(int32_t n_tensors, const int64_t* numel) {
+    if (n_tensors < 0 || (n_tensors > 0 && !numel)) return 0;
+    int64_t u = 0;
+    for (int i = 0; i < n_tensors; ++i)
+        if (numel[i] > 0) u += (numel[i] + KGW_GRAD_NORM_UNIT - 1) / KGW_GRAD_NORM_UNIT;
+    return u;
+}
+
+extern "C" int kgw_grad_norm_partial(int32_t n_tensors, const float* const* grads, const int64_t* numel, double* partial,
+                                     int64_t partial_offset, kgw_stream_t stream_) {
+    if (n_tensors < 0 || n_tensors > ADAM_MAX || partial_offset < 0) return KGW_E_RANGE;
+    if (n_tensors == 0) return KGW_OK;
+    if (!grads || !numel || !partial) return KGW_E_NULL;
+    NormTab T;
+    T.n = n_tensors;
+    T.off[0] = 0;
+    T.coff[0] = 0;
+    for (int i = 0; i < n_tensors; ++i) {
+        if (numel[i] < 0) return KGW_E_RANGE;
+        if (!grads[i] && numel[i] > 0) return KGW_E_NULL;
+        T.g[i] = grads[i];
+        T.off[i + 1] = T.off[i] + numel[i];
+        T.coff[i + 1] = T.coff[i] + (numel[i] + KGW_GRAD_NORM_UNIT - 1) / KGW_GRAD_NORM_UNIT;
+        T.vec[i] = ((uintptr_t)grads[i] & 15) == 0;
+    }
+    int64_t g = T.coff[n_tensors];
+    if (g < 1) return KGW_OK;                                          // (empty tensors only: no unit, nothing to write)
+    if (g > 4 * KGW_GRID) g = 4 * KGW_GRID;
+    k_grad_norm_partial<<<(int)g, 256, 0, (hipStream_t)stream_>>>(T, partial + partial_offset);
+    KGW_LAUNCH_CHECK();
+    return KGW_OK;
+}
+
+extern "C" int kgw_grad_norm_fold(const double* partial, int64_t count, double max_norm, float* norm_out_dev, float* scale_out_dev,
+                                  kgw_stream_t stream_) {
+    if (!partial || !scale_out_dev) return KGW_E_NULL;
+    if (count < 1 || !(max_norm > 0.0) || !(max_norm <= 1.7976931348623157e308)) return KGW_E_RANGE;
+    k_grad_norm_fold<<<1, 1024, 0, (hipStream_t)stream_>>>(partial, count, max_norm, norm_out_dev, scale_out_dev);
+    KGW_LAUNCH_CHECK();
     return KGW_OK;
 }

@@ -233,7 +233,8 @@ class BatchCache:
 class GraphTrainStep:
     def __init__(self, run, input_nodes, batch_size: int, lr: float = 1e-4, weight_decay: float = 5e-4,
                  margin: float = 1.03, shard_gene_layer: bool = None, cache_batches: bool = False, num_neighbors=None,
-                 sample_seed: int = 0, epoch_order: str = 'fixed', epochs: int = None, rank: int = 0, world: int = 1):
+                 sample_seed: int = 0, epoch_order: str = 'fixed', epochs: int = None, rank: int = 0, world: int = 1,
+                 lr_schedule=None, grad_clip_norm=None):
         """``num_neighbors`` (None = the reference's [-1] * L): PyG's list form of per-hop fan-outs.  With a finite fan-out the
         batches are redrawn every epoch from (``sample_seed``, epoch, batch index) -- ``set_epoch`` names the epoch, a step past
         the last batch moves on to the next one by itself -- the capacities of the static layout are bounds that hold for every
@@ -257,7 +258,15 @@ class GraphTrainStep:
         of epoch ``epochs``, sampled ahead and never trained on) -- an epoch outside that range is a ValueError -- and no batch is
         kept (BatchCache off).  'batches': the fixed order's batches in another order; the cache stays on, its slot the SOURCE batch
         of a step, while the fan-out and dropout words stay functions of the step's position i.  Several ranks that shuffle
-        (``rank`` of ``world``): ``input_nodes`` are the GLOBAL ids, ``batch_size`` this rank's share of the global batch."""
+        (``rank`` of ``world``): ``input_nodes`` are the GLOBAL ids, ``batch_size`` this rank's share of the global batch.
+        ``lr_schedule`` (None | a kind | a dict | a _lib.KgwLrSchedule: optim.parse_lr_schedule; ``total_steps`` defaults to the
+        batches of ``epochs`` epochs, one without ``epochs``): the optimiser launch forms the rate of its update from the device
+        step counter, so the captured step replays with a moving rate.  Nothing else about the route changes: ``fused_adam``,
+        ``duv_pieces``, the riders and the launches are the default step's, only the entry point called differs.
+        ``grad_clip_norm`` (None | finite > 0): torch's clip_grad_norm_ coefficient from the global norm of the finished gradients,
+        two launches ahead of Adam inside the captured graph.  Every gradient must be a finished tensor for that, so the step takes
+        the unfused optimiser route (``fused_adam = duv_pieces = False``, as several heads do).  Several ranks: the norm is taken
+        over the all-reduced buckets, the same coefficient everywhere (run on one rank only so far)."""
         self.run = run
         self.model = run.model
         self.batch_size = int(batch_size)
@@ -278,6 +287,9 @@ class GraphTrainStep:
         self.n_batches = len(probe)
         if self.n_batches == 0:
             raise ValueError('no full batch in input_nodes')
+        from .optim import check_grad_clip_norm, parse_lr_schedule
+        self.lr_schedule = parse_lr_schedule(lr_schedule, lr, self.n_batches * max(1, int(epochs) if epochs is not None else 1))
+        self.grad_clip_norm = check_grad_clip_norm(grad_clip_norm)
         self.caps = probe.measure_caps(margin, epochs=self.epochs or 1)
         self.dg = probe.dg.with_static_caps(self.caps)
         self.seed_type = probe.seed_type
@@ -317,8 +329,10 @@ class GraphTrainStep:
         self.capture_optimizer = not self._multi
         # single GPU, optimiser inside the graph: the partial-sum folds of the weight gradients, Adam and the statistics as one launch
         # (several heads: the transform's weight gradient passes through element-wise ops -- the head masks -- before it reaches its
-        #  parameter, so no product may leave its last sums to the optimiser's launch)
+        #  parameter, so no product may leave its last sums to the optimiser's launch; gradient clipping: the global norm needs
+        #  every gradient finished BEFORE the optimiser's launch)
         self.fused_adam = (ops._FUSED_ADAM and not self._multi and getattr(self.model, 'heads', 1) == 1 and
+                           self.grad_clip_norm is None and
                            sum(1 for p in self.model.parameters() if p.requires_grad) <= _lib.ADAM_FUSED_MAX)
         self.deferred_gradients = 0
         self._images, self._image_params, self._image_version, self._pack_probe = {}, [], {}, None
@@ -346,7 +360,8 @@ class GraphTrainStep:
         self._cut = [None, None]
         self.graphs_b = [None, None]
         from .optim import FusedAdam
-        self.opt = FusedAdam(self.model.parameters(), lr=lr, weight_decay=weight_decay)   # one launch, capturable
+        self.opt = FusedAdam(self.model.parameters(), lr=lr, weight_decay=weight_decay,   # one launch, capturable
+                             lr_schedule=self.lr_schedule, grad_clip_norm=self.grad_clip_norm)
         # device-side statistics accumulated inside the graph: [edges layer 1..L, sampled edges, error mask]
         self.stats = torch.zeros(L + 2, dtype=torch.int64, device=dev)
         self.loss = [None, None]

@@ -185,11 +185,15 @@ class KGWAS:
         optimizer.step()
         return loss
 
-    def _train_sharded(self, batch_size, lr, weight_decay, total_epoch, save_best_model, save_name, use_graph=True):
+    def _train_sharded(self, batch_size, lr, weight_decay, total_epoch, save_best_model, save_name, use_graph=True,
+                       lr_schedule=None, grad_clip_norm=None):
         """kgwas/kgwas.py:85-212 in the SNP-sharded multi-GPU mode (kgwas_amd/shard.py): every rank works on the SAME
         batches of the reference's order and owns the SNPs of one id range; validation / test / inference predictions are
         computed shard-wise and summed, so every rank sees the same metrics and keeps the same best model."""
         from .shard import ShardedTrainer
+        if lr_schedule is not None or grad_clip_norm is not None:
+            raise NotImplementedError("lr_schedule / grad_clip_norm are not available with parallelism='shard': the sharded step "
+                                      "calls the optimiser without its controls; use parallelism='seed'")
         if getattr(self.model, 'heads', 1) > 1:
             raise NotImplementedError("gat_num_head > 1 is not available with parallelism='shard': the partial softmax states of "
                                       "the SNP-sharded exchange are single-head; use parallelism='seed'")
@@ -255,7 +259,8 @@ class KGWAS:
         self.shard_bytes_moved = st.xchg.bytes_moved
 
     def train(self, batch_size=512, num_workers=0, lr=1e-4, weight_decay=5e-4, epoch=10, save_best_model=True,
-              save_name=None, data_to_cuda=False, use_graph=True, parallelism='seed', num_neighbors=None, shuffle=False):
+              save_name=None, data_to_cuda=False, use_graph=True, parallelism='seed', num_neighbors=None, shuffle=False,
+              lr_schedule=None, grad_clip_norm=None):
         """Same signature and defaults as kgwas/kgwas.py:85-87.  ``use_graph`` (extra, default on): run the
         training step as one captured HIP graph (kgwas_amd/graph_step.py); off = eager launches, same math.
         ``parallelism`` (extra; matters under torch.distributed): 'seed' = every rank trains on its slice of each batch
@@ -269,8 +274,19 @@ class KGWAS:
         NeighborLoader(epoch_order='seeds')), 'batches' = the fixed order's genome-contiguous batches, visited in another order
         every epoch.  The order is a pure function of (the run's seed, epoch), the same on every rank.  An argument of the run,
         not of the model: nothing enters config.pkl.  Validation, test and inference keep their order.  Not available with
-        parallelism='shard'."""
+        parallelism='shard'.
+        ``lr_schedule`` (extra, default None = the reference's one rate): a kind ('constant', 'linear', 'cosine', 'step') or a dict
+        with ``kind``, ``warmup_steps``, ``min_lr``, ``step_size``, ``gamma``, ``total_steps`` (optim.parse_lr_schedule; the rule:
+        include/kgwas_hip.h); ``total_steps`` defaults to ``epoch`` x the batches of an epoch.  The rate of every update is formed
+        inside the optimiser's kernel from the device step counter.  ``grad_clip_norm`` (extra, default None): finite and > 0, the
+        max_norm of torch.nn.utils.clip_grad_norm_ over all gradients, applied inside the update (the gradient tensors stay
+        unscaled).  With either set the eager loop (``use_graph=False``) runs FusedAdam too -- both loops the same kernels -- and
+        ``self.last_lr`` holds the rate of the epoch's last update, read at the validation point (wandb: ``lr``).  Arguments of the
+        run: nothing enters config.pkl.  Not available with parallelism='shard'."""
         total_epoch = epoch
+        from .optim import check_grad_clip_norm, parse_lr_schedule
+        grad_clip_norm = check_grad_clip_norm(grad_clip_norm)
+        controlled = lr_schedule is not None or grad_clip_norm is not None
         if isinstance(shuffle, (bool, np.bool_)):
             epoch_order = 'seeds' if shuffle else 'fixed'
         elif isinstance(shuffle, str) and shuffle == 'batches':
@@ -296,7 +312,8 @@ class KGWAS:
             save_name = self.exp_name
         self.save_name = save_name
         if parallelism == 'shard':
-            return self._train_sharded(batch_size, lr, weight_decay, total_epoch, save_best_model, save_name, use_graph)
+            return self._train_sharded(batch_size, lr, weight_decay, total_epoch, save_best_model, save_name, use_graph,
+                                       **({'lr_schedule': lr_schedule, 'grad_clip_norm': grad_clip_norm} if controlled else {}))
         if parallelism != 'seed':
             raise ValueError(f"parallelism {parallelism!r}: 'seed' or 'shard'")
         print_sys('Creating data loader...')
@@ -304,6 +321,11 @@ class KGWAS:
         rank, world = kdist.rank_world()
         if world > 1:
             kdist.broadcast_params(self.model)
+        controls = {}
+        if controlled:
+            if lr_schedule is not None:
+                lr_schedule = parse_lr_schedule(lr_schedule, lr, max(1, total_epoch * len(self.train_loader)))
+            controls = {'lr_schedule': lr_schedule, 'grad_clip_norm': grad_clip_norm}
         graph_step = None
         if use_graph and len(self.train_loader) > 0:
             from .graph_step import GraphTrainStep
@@ -312,11 +334,14 @@ class KGWAS:
             shuffled = {} if epoch_order == 'fixed' else {'epoch_order': epoch_order, 'epochs': total_epoch, 'rank': rank, 'world': world}
             graph_step = GraphTrainStep(self, (self.train_loader.input_type, self.train_loader.ids.cpu().numpy()),
                                         self.train_loader.batch_size, lr=lr, weight_decay=weight_decay,
-                                        shard_gene_layer=None, **shuffled,
+                                        shard_gene_layer=None, **shuffled, **controls,
                                         # (the loader's batch order is fixed, kgwas.py:93-101: the batches sampled in epoch 1 are
                                         #  kept in HBM and put back in later epochs -- graph_step.BatchCache)
                                         cache_batches=total_epoch > 1, num_neighbors=num_neighbors, sample_seed=self.seed)
             optimizer = graph_step.opt
+        elif controlled:
+            from .optim import FusedAdam
+            optimizer = FusedAdam(self.model.parameters(), lr=lr, weight_decay=weight_decay, **controls)     # (the captured step's kernels)
         else:
             optimizer = torch.optim.Adam(self.model.parameters(), lr=lr, weight_decay=weight_decay)   # kgwas.py:116
         ld_w = self._ld_weight_vector()
@@ -347,6 +372,10 @@ class KGWAS:
                     print_sys('Epoch {} Step {} Train Loss: {:.4f}'.format(ep + 1, step + 1, loss.item()))
             if graph_step is not None:
                 graph_step.check()
+            if controlled:                                           # (the stream is synchronised here anyway)
+                self.last_lr = float(optimizer.last_lr)
+                if self.wandb:
+                    self.wandb.log({'lr': self.last_lr})
             val_res = evaluate_minibatch_clean(self.val_loader, self.model, self.device)
             val_metrics = self._metrics(val_res, self._observed_rows(self.val_loader, len(val_res['pred'])))
             print_sys('Epoch {}: Validation MSE: {:.4f} Validation Pearson: {:.4f}. '.format(

@@ -1,16 +1,92 @@
 """FusedAdam: torch.optim.Adam(lr, betas, eps, weight_decay) semantics (kgwas/kgwas.py:116) in ONE launch over all
-parameter tensors (kgw_adam), with the step counter on the device so it can sit inside a captured HIP graph."""
+parameter tensors (kgw_adam), with the step counter on the device so it can sit inside a captured HIP graph.
+
+Two extensions, off by default (the reference trains at one rate and bounds no step): a learning-rate schedule evaluated INSIDE the
+Adam kernels from the device step counter (include/kgwas_hip.h: KgwLrSchedule, kgwlr_at), so that a captured step replays with a
+moving rate, and torch.nn.utils.clip_grad_norm_'s coefficient from two launches ahead of Adam (kgw_grad_norm_partial / _fold)."""
 from __future__ import annotations
 
 import ctypes as C
+import math
+import numbers
 
 import torch
 
 from . import _lib
 
+_SCHEDULE_KEYS = ('kind', 'warmup_steps', 'min_lr', 'step_size', 'gamma', 'total_steps')
+
+
+def _steps(name, v, least):
+    if isinstance(v, bool) or not isinstance(v, numbers.Real) or not math.isfinite(v) or v != int(v):
+        raise ValueError(f'lr_schedule: {name} = {v!r} is not a whole number of steps')
+    if int(v) < least or int(v) >= 2 ** 31:
+        raise ValueError(f'lr_schedule: {name} = {v!r} must be at least {least} (and fit 31 bits)')
+    return int(v)
+
+
+def parse_lr_schedule(spec, lr, total_steps=None):
+    """``spec`` -> _lib.KgwLrSchedule (the rule: include/kgwas_hip.h), or None for None.  ``spec``: a kind ('constant', 'linear',
+    'cosine', 'step') or a dict with ``kind`` and any of ``warmup_steps`` (0), ``min_lr`` (0.0: where 'linear' / 'cosine' end;
+    the schedule keeps min_lr / lr), ``step_size`` ('step': required), ``gamma`` ('step': 0.1, torch's StepLR default) and
+    ``total_steps`` (else the argument: the update at which the decay ends).  Anything else is a ValueError; no device is needed."""
+    if spec is None:
+        return None
+    if isinstance(spec, _lib.KgwLrSchedule):      # (built by an earlier call, or by hand: only checked)
+        out = spec
+    else:
+        if isinstance(spec, str):
+            spec = {'kind': spec}
+        if not isinstance(spec, dict):
+            raise ValueError(f'lr_schedule {spec!r}: None, a kind {sorted(_lib.LR_KINDS)} or a dict with "kind"')
+        unknown = sorted(set(spec) - set(_SCHEDULE_KEYS))
+        if unknown:
+            raise ValueError(f'lr_schedule: unknown key(s) {unknown}; known: {list(_SCHEDULE_KEYS)}')
+        d = spec
+        if not isinstance(d.get('kind'), str) or d['kind'] not in _lib.LR_KINDS:
+            raise ValueError(f'lr_schedule: kind {d.get("kind")!r}; one of {sorted(_lib.LR_KINDS)}')
+        kind = _lib.LR_KINDS[d['kind']]
+        lr = float(lr)
+        if not math.isfinite(lr) or lr < 0:
+            raise ValueError(f'lr_schedule: lr = {lr!r} must be finite and >= 0')
+        total = d.get('total_steps', total_steps)
+        if total is None:
+            raise ValueError('lr_schedule: total_steps is needed (the update at which the decay ends)')
+        min_lr = d.get('min_lr', 0.0)
+        if isinstance(min_lr, bool) or not isinstance(min_lr, numbers.Real) or not math.isfinite(min_lr) or min_lr < 0 or min_lr > lr:
+            raise ValueError(f'lr_schedule: min_lr = {min_lr!r} must lie in [0, lr = {lr}]')
+        gamma = d.get('gamma', 0.1)
+        if isinstance(gamma, bool) or not isinstance(gamma, numbers.Real) or not math.isfinite(gamma) or gamma <= 0:
+            raise ValueError(f'lr_schedule: gamma = {gamma!r} must be finite and > 0')
+        if kind == _lib.KGW_LR_STEP and d.get('step_size') is None:
+            raise ValueError("lr_schedule: kind 'step' needs step_size")
+        out = _lib.KgwLrSchedule(kind, _steps('warmup_steps', d.get('warmup_steps', 0), 0), _steps('total_steps', total, 1),
+                                 _steps('step_size', d['step_size'], 1) if d.get('step_size') is not None else 1,
+                                 float(min_lr) / lr if lr > 0 else 0.0, float(gamma))
+    ok = (0 <= out.kind <= 3 and out.warmup_steps >= 0 and out.total_steps >= 1 and (out.kind != _lib.KGW_LR_STEP or out.step_size >= 1)
+          and 0.0 <= out.min_ratio <= 1.0 and math.isfinite(out.gamma) and out.gamma > 0)
+    if not ok:
+        raise ValueError('lr_schedule: a KgwLrSchedule outside the rule\'s ranges (include/kgwas_hip.h: kgwlr_valid)')
+    return out
+
+
+def check_grad_clip_norm(v):
+    """``grad_clip_norm`` -> float or None; a ValueError unless it is None or finite and > 0."""
+    if v is None:
+        return None
+    if isinstance(v, bool) or not isinstance(v, numbers.Real) or not math.isfinite(v) or v <= 0:
+        raise ValueError(f'grad_clip_norm = {v!r} must be finite and > 0')
+    return float(v)
+
 
 class FusedAdam:
-    def __init__(self, params, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
+    def __init__(self, params, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, lr_schedule=None, grad_clip_norm=None):
+        """``lr_schedule`` (None: one rate): a _lib.KgwLrSchedule, or a spec for parse_lr_schedule that names its own total_steps; the
+        rate of update t is formed in the kernels from ``step_dev``.  ``grad_clip_norm`` (None: off): ``step`` takes the global 2-norm
+        of the gradients it is about to use and scales them by min(1, max_norm / (norm + 1e-6)) INSIDE the update -- the gradient
+        tensors themselves stay unscaled, unlike after torch's in-place clip_grad_norm_.  With either set the calls go to the
+        ``_ctl`` entry points and ``last_lr`` (a device float) holds the rate of the latest update; ``last_grad_norm`` and
+        ``last_clip_scale`` (device floats) the latest norm and coefficient."""
         self.params = [p for p in params]
         self.lr, self.betas, self.eps, self.weight_decay = float(lr), (float(betas[0]), float(betas[1])), float(eps), float(weight_decay)
         self.state = {}
@@ -18,6 +94,21 @@ class FusedAdam:
         self.step_dev = torch.zeros(1, dtype=torch.int32, device=dev)
         self.packed_images = {}        # parameter -> persistent kgw_gemm3 operand image its fused update keeps current (step_fused)
         self.param_groups = [{'params': self.params, 'lr': lr, 'betas': betas, 'eps': eps, 'weight_decay': weight_decay}]
+        self.lr_schedule = parse_lr_schedule(lr_schedule, self.lr)
+        self.grad_clip_norm = check_grad_clip_norm(grad_clip_norm)
+        self._ctl = None
+        if self.lr_schedule is not None or self.grad_clip_norm is not None:
+            if not _lib.has_optim_ctl():
+                raise _lib.KgwasHipError('the loaded library has no optimiser controls (kgw_adam_ctl): lr_schedule / grad_clip_norm '
+                                         'need them')
+            self.last_lr = torch.full((1,), self.lr, dtype=torch.float32, device=dev)
+            self.last_grad_norm = torch.zeros(1, dtype=torch.float32, device=dev)
+            self.last_clip_scale = torch.ones(1, dtype=torch.float32, device=dev)
+            self._norm_ws = None
+            # (clipping alone: the constant schedule, whose rate is ``lr`` to the bit)
+            sched = self.lr_schedule if self.lr_schedule is not None else _lib.KgwLrSchedule(_lib.KGW_LR_CONSTANT, 0, 1, 1, 0.0, 1.0)
+            self._ctl = _lib.KgwOptimCtl(sched, self.last_clip_scale.data_ptr() if self.grad_clip_norm is not None else None,
+                                         self.last_lr.data_ptr())
 
     def zero_grad(self, set_to_none: bool = True):
         for p in self.params:
@@ -47,6 +138,9 @@ class FusedAdam:
         launch.  Raises ops.GradSinkMismatch (nothing launched) when the fused form does not apply; the caller then runs the
         unfused step."""
         from . import ops
+        if self.grad_clip_norm is not None:
+            raise ops.GradSinkMismatch('grad_clip_norm needs every gradient finished before the optimiser launch: the global norm is '
+                                       'taken over finished tensors, and a deferred gradient is only finished inside kgw_adam_fused')
         live = [p for p in self.params if p.grad is not None]
         # (claim: the deferred weight-gradient products' one launch, just ahead of this one, then the sourced record of every gradient)
         recs = sink.claim({p: p.grad for p in live}) if sink is not None else {}
@@ -77,9 +171,12 @@ class FusedAdam:
                 img = self.packed_images.get(p)
                 if img is not None and S[k].kind == _lib.KGW_GRAD_G3T:               # the updated weight's operand image rides along
                     S[k].packed, S[k].flip = img.data_ptr(), int(_lib.lib().kgw_gemm3_flip())
-        rc = _lib.lib().kgw_adam_fused(n, P, G, M, V, N, S, self.step_dev.data_ptr(), self.lr, self.betas[0], self.betas[1], self.eps,
-                                       self.weight_decay, meta_ptr, n_layers, n_hops, stats.data_ptr() if stats is not None else None,
-                                       self.done_dev.data_ptr(), _lib.stream_ptr())
+        args = (n, P, G, M, V, N, S, self.step_dev.data_ptr(), self.lr, self.betas[0], self.betas[1], self.eps, self.weight_decay,
+                meta_ptr, n_layers, n_hops, stats.data_ptr() if stats is not None else None, self.done_dev.data_ptr())
+        if self._ctl is not None:                  # (a schedule: the same launch, its rate formed in the kernel)
+            rc = _lib.lib().kgw_adam_fused_ctl(*args, C.byref(self._ctl), _lib.stream_ptr())
+        else:
+            rc = _lib.lib().kgw_adam_fused(*args, _lib.stream_ptr())
         _lib.check(rc, 'kgw_adam_fused')
         # (``recs`` -- and with it the partial-sum workspaces -- lives until here: the launch that reads them is enqueued)
 
@@ -120,6 +217,7 @@ class FusedAdam:
             live = [p for p in self.params if p.grad is not None]     # grad None => skipped, exactly like torch
         if not live:
             return
+        tables = []
         for i in range(0, len(live), 64):
             chunk = live[i:i + 64]
             n = len(chunk)
@@ -131,8 +229,29 @@ class FusedAdam:
                     raise _lib.KgwasHipError('FusedAdam needs contiguous fp32 parameters and gradients')
                 st = self._state(p)
                 P[k], G[k], M[k], V[k], N[k] = p.data_ptr(), g.data_ptr(), st['exp_avg'].data_ptr(), st['exp_avg_sq'].data_ptr(), p.numel()
+            tables.append((i, n, P, G, M, V, N))
+        if self.grad_clip_norm is not None:
+            # the global norm of exactly the gradients the update below reads (the all-reduced bucket's views when ``grads`` is
+            # given: the same coefficient on every rank): one sum of squares per work unit, then one block for the rest
+            L = _lib.lib()
+            units = [int(L.kgw_grad_norm_workspace_doubles(n, N)) for _, n, _, _, _, _, N in tables]
+            if sum(units) > 0:
+                if self._norm_ws is None or self._norm_ws.numel() < sum(units):
+                    self._norm_ws = torch.empty(sum(units), dtype=torch.float64, device=self.step_dev.device)
+                off = 0
+                for (_, n, _, G, _, _, N), u in zip(tables, units):
+                    _lib.check(L.kgw_grad_norm_partial(n, G, N, self._norm_ws.data_ptr(), off, _lib.stream_ptr()), 'kgw_grad_norm_partial')
+                    off += u
+                _lib.check(L.kgw_grad_norm_fold(self._norm_ws.data_ptr(), off, self.grad_clip_norm, self.last_grad_norm.data_ptr(),
+                                                self.last_clip_scale.data_ptr(), _lib.stream_ptr()), 'kgw_grad_norm_fold')
+        for i, n, P, G, M, V, N in tables:
             # chunks > 0 must not advance the step counter again: only the last call ticks it
             last = i + 64 >= len(live)
+            if self._ctl is not None:
+                rc = _lib.lib().kgw_adam_ctl(n, P, G, M, V, N, self.step_dev.data_ptr(), self.lr, self.betas[0], self.betas[1],
+                                             self.eps, self.weight_decay, int(tick and last), C.byref(self._ctl), _lib.stream_ptr())
+                _lib.check(rc, 'kgw_adam_ctl')
+                continue
             fn = _lib.lib().kgw_adam if (tick and last) else _lib.lib().kgw_adam_notick      # only the last chunk ticks
             rc = fn(n, P, G, M, V, N, self.step_dev.data_ptr(), self.lr, self.betas[0], self.betas[1],
                     self.eps, self.weight_decay, _lib.stream_ptr())
