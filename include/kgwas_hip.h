@@ -430,6 +430,43 @@ KGWFAN_INLINE float kgwlr_at(const KgwLrSchedule* S, float lr, int32_t t) {     
     return (float)((double)lr * kgwlr_warm(S, s) * kgwlr_decay(S, s));
 }
 
+/* Weight averaging: a shadow copy s of every parameter p, updated on the device after the optimiser's update -- the reference
+ * evaluates, selects and saves the raw weights (kgwas/kgwas.py:153-173), so like the schedules this is an EXTENSION, off by default.
+ * n = the optimiser's device step counter AFTER its tick = the number of updates done, n >= 1.  With start_step >= 1, every >= 1:
+ *      event(n) = n >= start_step && (n - start_step) % every == 0
+ *      k        = (n - start_step) / every                                (the number of events before this one)
+ *      alpha    = KGW_AVG_EMA: k == 0 ? 1 : 1.0f - d,   d = warmup ? fminf(decay, (float)(1 + k) / (float)(10 + k)) : decay
+ *                 KGW_AVG_SWA: 1.0f / (float)(k + 1)
+ *      s        = fmaf(alpha, p - s, s)                                   (float32; alpha == 1: the bits of p are stored, a copy)
+ * EMA: s <- d s + (1 - d) p, d capped from below by TF's (1 + k) / (10 + k) warm-up; SWA: the equal-weight mean of the parameters at
+ * the events so far (torch.optim.swa_utils).  On a non-event s is not written.  n is READ FROM DEVICE MEMORY when the kernel runs:
+ * a captured step replays with a moving alpha.  kgwavg_alpha returns event(n) and, on an event, stores alpha.                     */
+enum { KGW_AVG_EMA = 0, KGW_AVG_SWA = 1 };
+typedef struct KgwWeightAvg {
+    int32_t kind, start_step, every, warmup;                /* warmup (0 | 1), decay: read by KGW_AVG_EMA only                    */
+    float decay;                                            /* 0 < decay < 1                                                      */
+} KgwWeightAvg;
+/* 1: a configuration the rule above defines.  Otherwise (an unknown kind, start_step < 1, every < 1, on EMA a warmup other than
+ * 0 / 1 or a decay outside (0, 1) or NaN) every entry point that takes it returns KGW_E_RANGE before any launch.                 */
+KGWFAN_INLINE int kgwavg_valid(const KgwWeightAvg* A) {
+    if (A->kind < KGW_AVG_EMA || A->kind > KGW_AVG_SWA || A->start_step < 1 || A->every < 1) return 0;
+    if (A->kind == KGW_AVG_EMA && (A->warmup < 0 || A->warmup > 1 || !(A->decay > 0.0f && A->decay < 1.0f))) return 0;
+    return 1;
+}
+KGWFAN_INLINE int kgwavg_alpha(const KgwWeightAvg* A, int32_t n, float* alpha) {
+    if (n < A->start_step || (n - A->start_step) % A->every != 0) return 0;
+    const int32_t k = (n - A->start_step) / A->every;
+    if (A->kind == KGW_AVG_SWA) {
+        *alpha = 1.0f / (float)(k + 1);
+    } else if (k == 0) {
+        *alpha = 1.0f;
+    } else {
+        const float d = A->warmup ? fminf(A->decay, (float)(1 + k) / (float)(10 + k)) : A->decay;
+        *alpha = 1.0f - d;
+    }
+    return 1;
+}
+
 /* Hidden-state dropout: x = F.dropout(x, p, training) on the OUTPUT of message-passing layer l, 1 <= l <= L - 1 (after its ReLU,
  * kgwas/model.py:75; never on the feature MLPs' output, never on the last layer).  The reference's HeteroGNN has no such line:
  * like the attention dropout an EXTENSION, off by default.  For stored column c (0 .. 127) of the node with LOCAL index row within
@@ -1049,6 +1086,23 @@ int kgw_grad_norm_partial(int32_t n_tensors, const float* const* grads, const in
                           int64_t partial_offset, kgw_stream_t stream);
 int kgw_grad_norm_fold(const double* partial, int64_t count, double max_norm, float* norm_out_dev, float* scale_out_dev,
                        kgw_stream_t stream);
+
+/* Weight averaging (an EXTENSION, the rule: KgwWeightAvg above): shadow[i] of up to KGW_WEIGHT_AVG_MAX tensors moves towards
+ * params[i] in ONE launch that follows the optimiser's -- after the launch that advanced *step_dev, which this one never does.
+ * Every wavefront loads n = *step_dev once (a wave-uniform load) and evaluates kgwavg_alpha: a non-event ends it there, so the
+ * launch stays in a captured graph and touches nothing but the counter.  On an event a work unit is KGW_WEIGHT_AVG_UNIT consecutive
+ * elements of ONE tensor (float4 where both pointers are 16-byte aligned, the tensor's tail and unaligned tensors element by
+ * element); s = fmaf(alpha, p - s, s), with alpha == 1 the bits of p.  Element-wise, no LDS, no atomics: every mapping gives the
+ * same bits.  More tensors: further calls.  shadow[i] and params[i] must not overlap.  Refused before any launch: a NULL table,
+ * tensor, counter or cfg: KGW_E_NULL; n_tensors outside [0, 64] or a negative numel: KGW_E_RANGE; a cfg kgwavg_valid refuses:
+ * KGW_E_RANGE.  The feature is detected by symbol (the version stays).
+ * kgw_weight_avg_alpha: host evaluation of the rule (bindings, tests): *event (nullable) = kgwavg_alpha's result, the return value
+ * its alpha (0 on a non-event); NaN and *event = 0 for a NULL or refused cfg or n < 1.                                             */
+#define KGW_WEIGHT_AVG_MAX 64
+#define KGW_WEIGHT_AVG_UNIT 1024
+int kgw_weight_avg_update(int32_t n_tensors, float* const* shadow, const float* const* params, const int64_t* numel,
+                          const int32_t* step_dev, const KgwWeightAvg* cfg, kgw_stream_t stream);
+float kgw_weight_avg_alpha(const KgwWeightAvg* cfg, int32_t n, int32_t* event);
 
 /* Attention vectors of all relations of a layer (kgwas/conv.py:138-151 reduced to what the path consumes):
  * U_full[r] = W_src^T att_src for every relation id r the layer computes (live_of_rel[r] = its index i in the

@@ -147,6 +147,15 @@ class KgwOptimCtl(C.Structure):
     _fields_ = [('sched', KgwLrSchedule), ('grad_scale_dev', C.c_void_p), ('lr_out_dev', C.c_void_p)]
 
 
+KGW_AVG_EMA, KGW_AVG_SWA = 0, 1                                           # KgwWeightAvg.kind (include/kgwas_hip.h)
+AVG_KINDS = {'ema': KGW_AVG_EMA, 'swa': KGW_AVG_SWA}
+WEIGHT_AVG_MAX, WEIGHT_AVG_UNIT = 64, 1024                                # KGW_WEIGHT_AVG_MAX, KGW_WEIGHT_AVG_UNIT
+
+
+class KgwWeightAvg(C.Structure):
+    _fields_ = [('kind', C.c_int32), ('start_step', C.c_int32), ('every', C.c_int32), ('warmup', C.c_int32), ('decay', C.c_float)]
+
+
 class KgwReadoutFold(C.Structure):
     _fields_ = [('scratch', C.c_void_p), ('terms', C.c_void_p), ('dw_lin', C.c_void_p), ('db_lin', C.c_void_p), ('loss', C.c_void_p),
                 ('nb', C.c_int32), ('n', C.c_int32)]
@@ -220,7 +229,7 @@ EXPORTS = ['kgw_version', 'kgw_status_string', 'kgw_struct_sizes', 'kgw_sample_b
            'kgw_layer_norm_relu_fwd', 'kgw_layer_norm_partial_floats', 'kgw_layer_norm_bwd', 'kgw_layer_norm_fold',
            'kgw_root_linear_fwd', 'kgw_root_linear_bwd',
            'kgw_adam_ctl', 'kgw_adam_fused_ctl', 'kgw_lr_at', 'kgw_grad_norm_partial', 'kgw_grad_norm_fold',
-           'kgw_grad_norm_workspace_doubles']
+           'kgw_grad_norm_workspace_doubles', 'kgw_weight_avg_update', 'kgw_weight_avg_alpha']
 
 _lib = None
 
@@ -409,6 +418,15 @@ def lib():
         if [s10[8], s10[9]] != [C.sizeof(KgwLrSchedule), C.sizeof(KgwOptimCtl)]:
             raise KgwasHipError(f'ABI struct size mismatch: KgwLrSchedule / KgwOptimCtl library {[s10[8], s10[9]]} vs binding '
                                 f'{[C.sizeof(KgwLrSchedule), C.sizeof(KgwOptimCtl)]}')
+    if hasattr(L, 'kgw_weight_avg_update'):         # (absent likewise)
+        L.kgw_weight_avg_update.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.c_void_p,
+                                            C.POINTER(KgwWeightAvg), C.c_void_p]
+        L.kgw_weight_avg_alpha.argtypes = [C.POINTER(KgwWeightAvg), C.c_int32, C.POINTER(C.c_int32)]
+        L.kgw_weight_avg_alpha.restype = C.c_float
+        s11 = (C.c_int64 * 11)()
+        L.kgw_struct_sizes(s11, 11)
+        if s11[10] != C.sizeof(KgwWeightAvg):
+            raise KgwasHipError(f'ABI struct size mismatch: KgwWeightAvg library {s11[10]} vs binding {C.sizeof(KgwWeightAvg)}')
     L.kgw_accumulate_stats.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
     L.kgw_accumulate_stats_tick.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     _lib = L
@@ -468,6 +486,12 @@ def has_optim_ctl() -> bool:
     """Does the loaded library have the optimiser controls (kgw_adam_ctl, kgw_adam_fused_ctl, kgw_grad_norm_partial / _fold:
     learning-rate schedules and gradient-norm clipping)?  An older library named by KGW_LIB_PATH for an A/B run lacks the symbols."""
     return hasattr(lib(), 'kgw_adam_ctl')
+
+
+def has_weight_avg() -> bool:
+    """Does the loaded library have kgw_weight_avg_update (the EMA / SWA shadow weights)?  An older library named by KGW_LIB_PATH
+    for an A/B run lacks the symbol."""
+    return hasattr(lib(), 'kgw_weight_avg_update')
 
 
 KGW_ORDER_SEEDS, KGW_ORDER_BATCHES = 1, 2     # kgw_epoch_order's modes (include/kgwas_hip.h)

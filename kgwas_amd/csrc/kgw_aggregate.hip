@@ -1752,11 +1752,11 @@ extern "C" const char* kgw_status_string(int status) {
 
 extern "C" int kgw_struct_sizes(int64_t* out, int n) {
     if (!out) return KGW_E_NULL;
-    const int64_t v[10] = {(int64_t)sizeof(KgwGraph), (int64_t)sizeof(KgwBatchMeta), (int64_t)sizeof(KgwChunk),
+    const int64_t v[11] = {(int64_t)sizeof(KgwGraph), (int64_t)sizeof(KgwBatchMeta), (int64_t)sizeof(KgwChunk),
                            (int64_t)sizeof(KgwBatchBuf), (int64_t)sizeof(KgwLayerArgs), (int64_t)sizeof(KgwTnJob),
                            (int64_t)sizeof(KgwGradSrc), (int64_t)sizeof(KgwEdgeAttr), (int64_t)sizeof(KgwLrSchedule),
-                           (int64_t)sizeof(KgwOptimCtl)};
-    for (int i = 0; i < n && i < 10; ++i) out[i] = v[i];
+                           (int64_t)sizeof(KgwOptimCtl), (int64_t)sizeof(KgwWeightAvg)};
+    for (int i = 0; i < n && i < 11; ++i) out[i] = v[i];
     return KGW_OK;
 }
 

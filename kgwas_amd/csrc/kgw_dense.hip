@@ -13,6 +13,7 @@
 //   kgw_dense_hdrop.h       hidden-state dropout between the layers (an extension: HeteroGNN(gnn_dropout=p)), forward and backward
 //   kgw_dense_lnorm.h       layer normalisation + ReLU between the layers (an extension: HeteroGNN(gnn_norm='layer')), forward, backward, fold
 //   kgw_dense_root.h        the root weight of a layer, dst = act(y + x W^T) per node type (an extension: HeteroGNN(gnn_root_weight=True)), forward and dx
+//   kgw_dense_wavg.h        weight averaging: the EMA / SWA shadow of every parameter, one launch behind the optimiser's (an extension: train(weight_average=...))
 //
 // Mapping of the tall TN product (gfx950): v_mfma_f32_32x32x2_f32.  The MFMA operand layout IS the memory layout:
 // lane l supplies A[row k = l>>5][column i = l&31] -- a wave-instruction reads two contiguous 128-float rows.
@@ -35,3 +36,4 @@
 #include "kgw_dense_hdrop.h"
 #include "kgw_dense_lnorm.h"
 #include "kgw_dense_root.h"
+#include "kgw_dense_wavg.h"

@@ -63,12 +63,12 @@ class SideSampler:
             self.pending[w] = False
 
 
-def keep_training_state(model, opt, stats):
+def keep_training_state(model, opt, stats, avg=None):
     """Snapshot of what real training steps move -- parameters, the optimiser's state tensors, its step counter, the running
-    totals -- for a caller that runs such steps without meaning them (capture warm-up, a timing measurement).  Returns the
-    function that puts it back: tensors that existed are copied back, optimiser state created since is zeroed (Adam's initial
-    state).  The caller synchronises before it restores."""
-    params = [p for p in model.parameters()]
+    totals and, with ``avg`` (optim.WeightAverage), the shadow weights -- for a caller that runs such steps without meaning them
+    (capture warm-up, a timing measurement).  Returns the function that puts it back: tensors that existed are copied back,
+    optimiser state created since is zeroed (Adam's initial state).  The caller synchronises before it restores."""
+    params = [p for p in model.parameters()] + (avg.parameters() if avg is not None else [])
     snap = [p.detach().clone() for p in params]
     ostate = {p: {k: v.clone() for k, v in st.items() if torch.is_tensor(v)} for p, st in opt.state.items()}
     step0, stats0 = opt.step_dev.clone(), stats.clone()
@@ -234,7 +234,7 @@ class GraphTrainStep:
     def __init__(self, run, input_nodes, batch_size: int, lr: float = 1e-4, weight_decay: float = 5e-4,
                  margin: float = 1.03, shard_gene_layer: bool = None, cache_batches: bool = False, num_neighbors=None,
                  sample_seed: int = 0, epoch_order: str = 'fixed', epochs: int = None, rank: int = 0, world: int = 1,
-                 lr_schedule=None, grad_clip_norm=None):
+                 lr_schedule=None, grad_clip_norm=None, weight_average=None):
         """``num_neighbors`` (None = the reference's [-1] * L): PyG's list form of per-hop fan-outs.  With a finite fan-out the
         batches are redrawn every epoch from (``sample_seed``, epoch, batch index) -- ``set_epoch`` names the epoch, a step past
         the last batch moves on to the next one by itself -- the capacities of the static layout are bounds that hold for every
@@ -266,7 +266,12 @@ class GraphTrainStep:
         ``grad_clip_norm`` (None | finite > 0): torch's clip_grad_norm_ coefficient from the global norm of the finished gradients,
         two launches ahead of Adam inside the captured graph.  Every gradient must be a finished tensor for that, so the step takes
         the unfused optimiser route (``fused_adam = duv_pieces = False``, as several heads do).  Several ranks: the norm is taken
-        over the all-reduced buckets, the same coefficient everywhere (run on one rank only so far)."""
+        over the all-reduced buckets, the same coefficient everywhere (run on one rank only so far).
+        ``weight_average`` (None | 'ema' | 'swa' | a decay | a dict | a _lib.KgwWeightAvg: optim.parse_weight_average; ``every`` =
+        'epoch' is this trainer's batches): ``self.avg_model`` is an EMA / SWA shadow of the model, moved by ONE launch at the very end
+        of the captured step (kgw_weight_avg_update, behind the launch that advanced the step counter it reads); whether an update
+        is an averaging event, and its alpha, are decided on the device, so the step replays.  Nothing else about the route changes.
+        Several ranks: the launch follows the eager Adam launch, the same update everywhere (run on one rank only so far)."""
         self.run = run
         self.model = run.model
         self.batch_size = int(batch_size)
@@ -287,9 +292,10 @@ class GraphTrainStep:
         self.n_batches = len(probe)
         if self.n_batches == 0:
             raise ValueError('no full batch in input_nodes')
-        from .optim import check_grad_clip_norm, parse_lr_schedule
+        from .optim import check_grad_clip_norm, parse_lr_schedule, parse_weight_average
         self.lr_schedule = parse_lr_schedule(lr_schedule, lr, self.n_batches * max(1, int(epochs) if epochs is not None else 1))
         self.grad_clip_norm = check_grad_clip_norm(grad_clip_norm)
+        self.weight_average = parse_weight_average(weight_average, self.n_batches)
         self.caps = probe.measure_caps(margin, epochs=self.epochs or 1)
         self.dg = probe.dg.with_static_caps(self.caps)
         self.seed_type = probe.seed_type
@@ -362,6 +368,12 @@ class GraphTrainStep:
         from .optim import FusedAdam
         self.opt = FusedAdam(self.model.parameters(), lr=lr, weight_decay=weight_decay,   # one launch, capturable
                              lr_schedule=self.lr_schedule, grad_clip_norm=self.grad_clip_norm)
+        # the averaged weights: a copy of the model as it is now, moved by the last launch of every step
+        self.wavg = self.avg_model = None
+        if self.weight_average is not None:
+            from .optim import WeightAverage
+            self.wavg = WeightAverage(self.model, self.opt, self.weight_average)
+            self.avg_model = self.wavg.avg_model
         # device-side statistics accumulated inside the graph: [edges layer 1..L, sampled edges, error mask]
         self.stats = torch.zeros(L + 2, dtype=torch.int64, device=dev)
         self.loss = [None, None]
@@ -451,9 +463,13 @@ class GraphTrainStep:
         if sink is None:
             self.opt.step(tick=False)                              # (the counter advances in the statistics launch)
             self._stats_tick(cur, self.opt.step_dev.data_ptr())
+            if self.wavg is not None:
+                self.wavg.update()                                 # (the last launch: it reads the counter the tick advanced)
             return loss
         self.deferred_gradients = sink.deferred_gradients            # (gradients whose last sums the optimiser launch takes)
         self.opt.step_fused(sink, self.bufs[cur].meta.data_ptr(), self.run.gnn_num_layers, self.dg.n_hops, self.stats)
+        if self.wavg is not None:
+            self.wavg.update()                                     # (the last launch: it reads the counter step_fused advanced)
         # (launches of the step that carried its parameter-only forward work as rider blocks: the gene layer's kgw_gemm3)
         self.riders_taken = getattr(self.model, 'last_riders_taken', 0)
         self.reduces_ridden = sink.reduces_ridden    # (second launches of product groups that rode in a later launch)
@@ -616,7 +632,7 @@ class GraphTrainStep:
 
     def _capture(self):
         # warm-up on a side stream (allocator pools, one-time kernel attributes, Adam state), then undo its effect
-        restore = keep_training_state(self.model, self.opt, self.stats)
+        restore = keep_training_state(self.model, self.opt, self.stats, self.wavg)
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s):
@@ -751,6 +767,8 @@ class GraphTrainStep:
             kdist.allreduce_flat(self._flat_b, self.world, 'gradients of the feature MLPs')        # second bucket: the MLPs' own gradients
             main.wait_event(self._ev_ca)
             self.opt.step(self._flat_grads)
+            if self.wavg is not None:
+                self.wavg.update()
         return self.loss[cur]
 
     def measure_overlap(self, n: int = 20) -> dict:
@@ -761,7 +779,7 @@ class GraphTrainStep:
         next step() samples its batch itself) and the model, the optimiser state and the running totals as it found them."""
         # the measurement runs real training steps (half of them on stale batches): parameters, optimiser state, step counter and
         # the running totals are put back afterwards -- a measurement must not move the trajectory (ADVICE r4)
-        restore = keep_training_state(self.model, self.opt, self.stats)
+        restore = keep_training_state(self.model, self.opt, self.stats, self.wavg)
         k, keep = [0], self._skip_resample
 
         def step(_):

@@ -186,7 +186,7 @@ class KGWAS:
         return loss
 
     def _train_sharded(self, batch_size, lr, weight_decay, total_epoch, save_best_model, save_name, use_graph=True,
-                       lr_schedule=None, grad_clip_norm=None):
+                       lr_schedule=None, grad_clip_norm=None, weight_average=None):
         """kgwas/kgwas.py:85-212 in the SNP-sharded multi-GPU mode (kgwas_amd/shard.py): every rank works on the SAME
         batches of the reference's order and owns the SNPs of one id range; validation / test / inference predictions are
         computed shard-wise and summed, so every rank sees the same metrics and keeps the same best model."""
@@ -194,6 +194,9 @@ class KGWAS:
         if lr_schedule is not None or grad_clip_norm is not None:
             raise NotImplementedError("lr_schedule / grad_clip_norm are not available with parallelism='shard': the sharded step "
                                       "calls the optimiser without its controls; use parallelism='seed'")
+        if weight_average is not None:
+            raise NotImplementedError("weight_average is not available with parallelism='shard': the sharded step does not run "
+                                      "the weight-averaging launch; use parallelism='seed'")
         if getattr(self.model, 'heads', 1) > 1:
             raise NotImplementedError("gat_num_head > 1 is not available with parallelism='shard': the partial softmax states of "
                                       "the SNP-sharded exchange are single-head; use parallelism='seed'")
@@ -260,7 +263,7 @@ class KGWAS:
 
     def train(self, batch_size=512, num_workers=0, lr=1e-4, weight_decay=5e-4, epoch=10, save_best_model=True,
               save_name=None, data_to_cuda=False, use_graph=True, parallelism='seed', num_neighbors=None, shuffle=False,
-              lr_schedule=None, grad_clip_norm=None):
+              lr_schedule=None, grad_clip_norm=None, weight_average=None):
         """Same signature and defaults as kgwas/kgwas.py:85-87.  ``use_graph`` (extra, default on): run the
         training step as one captured HIP graph (kgwas_amd/graph_step.py); off = eager launches, same math.
         ``parallelism`` (extra; matters under torch.distributed): 'seed' = every rank trains on its slice of each batch
@@ -282,11 +285,21 @@ class KGWAS:
         max_norm of torch.nn.utils.clip_grad_norm_ over all gradients, applied inside the update (the gradient tensors stay
         unscaled).  With either set the eager loop (``use_graph=False``) runs FusedAdam too -- both loops the same kernels -- and
         ``self.last_lr`` holds the rate of the epoch's last update, read at the validation point (wandb: ``lr``).  Arguments of the
-        run: nothing enters config.pkl.  Not available with parallelism='shard'."""
+        run: nothing enters config.pkl.  Not available with parallelism='shard'.
+        ``weight_average`` (extra, default None = the reference, which evaluates, selects and saves the raw weights): 'ema' | 'swa' |
+        a float (EMA with that decay) | a dict with ``kind``, ``decay`` (0.999), ``warmup`` (True), ``start_step`` (1), ``every``
+        (1, or 'epoch') (optim.parse_weight_average; the rule: include/kgwas_hip.h, KgwWeightAvg).  ``self.avg_model`` is an averaged
+        copy of the weights, moved on the device by one launch behind the optimiser's; ``self.model`` stays the raw model.  An epoch
+        that ends after the first averaging event validates ``avg_model``, and ``best_model`` -- what test, inference and model.pt
+        go through -- is a copy of it when its Pearson is the best so far; an epoch that ends before the first event does what the
+        default run does.  The eager loop (``use_graph=False``) runs FusedAdam too: both loops the same kernels and the same
+        counter.  An argument of the run: nothing enters config.pkl.  Not available with parallelism='shard'; with several ranks
+        every rank applies the same update, so the shadows agree (run on one rank only so far)."""
         total_epoch = epoch
-        from .optim import check_grad_clip_norm, parse_lr_schedule
+        from .optim import check_grad_clip_norm, parse_lr_schedule, parse_weight_average
         grad_clip_norm = check_grad_clip_norm(grad_clip_norm)
         controlled = lr_schedule is not None or grad_clip_norm is not None
+        parse_weight_average(weight_average, 1)                      # (a ValueError before anything is built; 'epoch' is resolved below)
         if isinstance(shuffle, (bool, np.bool_)):
             epoch_order = 'seeds' if shuffle else 'fixed'
         elif isinstance(shuffle, str) and shuffle == 'batches':
@@ -313,7 +326,8 @@ class KGWAS:
         self.save_name = save_name
         if parallelism == 'shard':
             return self._train_sharded(batch_size, lr, weight_decay, total_epoch, save_best_model, save_name, use_graph,
-                                       **({'lr_schedule': lr_schedule, 'grad_clip_norm': grad_clip_norm} if controlled else {}))
+                                       **({'lr_schedule': lr_schedule, 'grad_clip_norm': grad_clip_norm} if controlled else {}),
+                                       **({'weight_average': weight_average} if weight_average is not None else {}))
         if parallelism != 'seed':
             raise ValueError(f"parallelism {parallelism!r}: 'seed' or 'shard'")
         print_sys('Creating data loader...')
@@ -326,7 +340,10 @@ class KGWAS:
             if lr_schedule is not None:
                 lr_schedule = parse_lr_schedule(lr_schedule, lr, max(1, total_epoch * len(self.train_loader)))
             controls = {'lr_schedule': lr_schedule, 'grad_clip_norm': grad_clip_norm}
-        graph_step = None
+        weight_average = parse_weight_average(weight_average, max(1, len(self.train_loader)))
+        if weight_average is not None:
+            controls['weight_average'] = weight_average
+        graph_step = wavg = None
         if use_graph and len(self.train_loader) > 0:
             from .graph_step import GraphTrainStep
             # (multi-GPU: a 512-seed batch split over the ranks = strong scaling; from 4 ranks on the batch-independent first gene
@@ -338,15 +355,20 @@ class KGWAS:
                                         # (the loader's batch order is fixed, kgwas.py:93-101: the batches sampled in epoch 1 are
                                         #  kept in HBM and put back in later epochs -- graph_step.BatchCache)
                                         cache_batches=total_epoch > 1, num_neighbors=num_neighbors, sample_seed=self.seed)
-            optimizer = graph_step.opt
-        elif controlled:
-            from .optim import FusedAdam
-            optimizer = FusedAdam(self.model.parameters(), lr=lr, weight_decay=weight_decay, **controls)     # (the captured step's kernels)
+            optimizer, wavg = graph_step.opt, graph_step.wavg
+        elif controls:
+            from .optim import FusedAdam, WeightAverage
+            optimizer = FusedAdam(self.model.parameters(), lr=lr, weight_decay=weight_decay,                 # (the captured step's kernels)
+                                  **{k: v for k, v in controls.items() if k != 'weight_average'})
+            if weight_average is not None:
+                wavg = WeightAverage(self.model, optimizer, weight_average)
         else:
             optimizer = torch.optim.Adam(self.model.parameters(), lr=lr, weight_decay=weight_decay)   # kgwas.py:116
         ld_w = self._ld_weight_vector()
         min_val = -1000
         self.best_model = deepcopy(self.model).to(self.device)
+        self.avg_model = wavg.avg_model if wavg is not None else None
+        batches = graph_step.n_batches if graph_step is not None else len(self.train_loader)
         dropout = getattr(self.model, 'gat_dropout', 0.0) > 0 or getattr(self.model, 'gnn_dropout', 0.0) > 0
         print_sys('Start Training...')
         for ep in range(total_epoch):
@@ -366,6 +388,8 @@ class KGWAS:
                     if dropout:                              # (the word the captured step copies in: the same masks either way)
                         self.model.set_dropout_word(dropout_word(self.seed, ep, step))
                     loss = self.train_step(batch, optimizer, ld_w, world)
+                    if wavg is not None:
+                        wavg.update()                        # (behind the launch that advanced the counter, as in the captured step)
                 if self.wandb:
                     self.wandb.log({'training_loss': loss.item()})
                 if (step % 500 == 0) and (step >= 500):
@@ -376,7 +400,9 @@ class KGWAS:
                 self.last_lr = float(optimizer.last_lr)
                 if self.wandb:
                     self.wandb.log({'lr': self.last_lr})
-            val_res = evaluate_minibatch_clean(self.val_loader, self.model, self.device)
+            # (the averaged weights from the first averaging event on: host arithmetic on the updates done, nothing is read back)
+            shown = self.avg_model if wavg is not None and wavg.started((ep + 1) * batches) else self.model
+            val_res = evaluate_minibatch_clean(self.val_loader, shown, self.device)
             val_metrics = self._metrics(val_res, self._observed_rows(self.val_loader, len(val_res['pred'])))
             print_sys('Epoch {}: Validation MSE: {:.4f} Validation Pearson: {:.4f}. '.format(
                 ep + 1, val_metrics['mse'], val_metrics['pearsonr']))
@@ -387,7 +413,7 @@ class KGWAS:
                         self.wandb.log({'val_' + i: j})
             if val_metrics['pearsonr'] > min_val:                    # kgwas.py:170-173
                 min_val = val_metrics['pearsonr']
-                self.best_model = deepcopy(self.model)
+                self.best_model = deepcopy(shown)
         if save_best_model and rank == 0:
             save_model_path = os.path.join(self.data_path, 'model')
             print_sys('Saving models to ' + os.path.join(save_model_path, save_name))

@@ -3,13 +3,17 @@ parameter tensors (kgw_adam), with the step counter on the device so it can sit 
 
 Two extensions, off by default (the reference trains at one rate and bounds no step): a learning-rate schedule evaluated INSIDE the
 Adam kernels from the device step counter (include/kgwas_hip.h: KgwLrSchedule, kgwlr_at), so that a captured step replays with a
-moving rate, and torch.nn.utils.clip_grad_norm_'s coefficient from two launches ahead of Adam (kgw_grad_norm_partial / _fold)."""
+moving rate, and torch.nn.utils.clip_grad_norm_'s coefficient from two launches ahead of Adam (kgw_grad_norm_partial / _fold).
+
+A third, off by default too: WeightAverage, an EMA or SWA shadow of the weights updated by one launch behind the optimiser's
+(kgw_weight_avg_update), driven by the same device counter."""
 from __future__ import annotations
 
 import ctypes as C
 import math
 import numbers
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -17,11 +21,11 @@ from . import _lib
 _SCHEDULE_KEYS = ('kind', 'warmup_steps', 'min_lr', 'step_size', 'gamma', 'total_steps')
 
 
-def _steps(name, v, least):
+def _steps(name, v, least, what='lr_schedule'):
     if isinstance(v, bool) or not isinstance(v, numbers.Real) or not math.isfinite(v) or v != int(v):
-        raise ValueError(f'lr_schedule: {name} = {v!r} is not a whole number of steps')
+        raise ValueError(f'{what}: {name} = {v!r} is not a whole number of steps')
     if int(v) < least or int(v) >= 2 ** 31:
-        raise ValueError(f'lr_schedule: {name} = {v!r} must be at least {least} (and fit 31 bits)')
+        raise ValueError(f'{what}: {name} = {v!r} must be at least {least} (and fit 31 bits)')
     return int(v)
 
 
@@ -77,6 +81,99 @@ def check_grad_clip_norm(v):
     if isinstance(v, bool) or not isinstance(v, numbers.Real) or not math.isfinite(v) or v <= 0:
         raise ValueError(f'grad_clip_norm = {v!r} must be finite and > 0')
     return float(v)
+
+
+_AVERAGE_KEYS = ('kind', 'decay', 'warmup', 'start_step', 'every')
+
+
+def parse_weight_average(spec, batches_per_epoch=None):
+    """``spec`` -> _lib.KgwWeightAvg (the rule: include/kgwas_hip.h), or None for None.  ``spec``: 'ema' | 'swa' | a float (EMA with
+    that decay) | a dict with ``kind`` and any of ``decay`` (EMA: 0.999, in (0, 1)), ``warmup`` (EMA: True, the cap
+    (1 + k) / (10 + k) on the decay of event k), ``start_step`` (1: the update that is the first event) and ``every`` (1, or 'epoch'
+    = ``batches_per_epoch``: updates between events).  Anything else is a ValueError; no device is needed."""
+    if spec is None:
+        return None
+    if isinstance(spec, _lib.KgwWeightAvg):       # (built by an earlier call, or by hand: only checked)
+        out = spec
+    else:
+        if isinstance(spec, str):
+            spec = {'kind': spec}
+        elif not isinstance(spec, (bool, dict)) and isinstance(spec, numbers.Real):
+            spec = {'kind': 'ema', 'decay': spec}
+        if not isinstance(spec, dict):
+            raise ValueError(f'weight_average {spec!r}: None, a kind {sorted(_lib.AVG_KINDS)}, a decay or a dict with "kind"')
+        unknown = sorted(set(spec) - set(_AVERAGE_KEYS))
+        if unknown:
+            raise ValueError(f'weight_average: unknown key(s) {unknown}; known: {list(_AVERAGE_KEYS)}')
+        d = spec
+        if not isinstance(d.get('kind'), str) or d['kind'] not in _lib.AVG_KINDS:
+            raise ValueError(f'weight_average: kind {d.get("kind")!r}; one of {sorted(_lib.AVG_KINDS)}')
+        kind = _lib.AVG_KINDS[d['kind']]
+        if kind == _lib.KGW_AVG_SWA and ('decay' in d or 'warmup' in d):
+            raise ValueError("weight_average: decay / warmup belong to kind 'ema'; 'swa' weighs its events equally")
+        decay = d.get('decay', 0.999)
+        if isinstance(decay, bool) or not isinstance(decay, numbers.Real) or not 0.0 < C.c_float(decay).value < 1.0:
+            raise ValueError(f'weight_average: decay = {decay!r} must lie in (0, 1) as a float32')
+        warmup = d.get('warmup', True)
+        if not isinstance(warmup, (bool, np.bool_)):
+            raise ValueError(f'weight_average: warmup = {warmup!r} must be True or False')
+        every = d.get('every', 1)
+        if isinstance(every, str):
+            if every != 'epoch':
+                raise ValueError(f"weight_average: every = {every!r}; a number of updates or 'epoch'")
+            if batches_per_epoch is None:
+                raise ValueError("weight_average: every = 'epoch' needs the batches of an epoch")
+            every = batches_per_epoch
+        out = _lib.KgwWeightAvg(kind, _steps('start_step', d.get('start_step', 1), 1, 'weight_average'),
+                                _steps('every', every, 1, 'weight_average'), int(bool(warmup)), float(decay))
+    ok = (out.kind in (_lib.KGW_AVG_EMA, _lib.KGW_AVG_SWA) and out.start_step >= 1 and out.every >= 1 and
+          (out.kind != _lib.KGW_AVG_EMA or (out.warmup in (0, 1) and 0.0 < out.decay < 1.0)))
+    if not ok:
+        raise ValueError('weight_average: a KgwWeightAvg outside the rule\'s ranges (include/kgwas_hip.h: kgwavg_valid)')
+    return out
+
+
+class WeightAverage:
+    """The averaged copy of a model's weights (EMA or SWA; the rule: include/kgwas_hip.h, KgwWeightAvg): ``avg_model``, a deep copy
+    in evaluation mode whose parameters ARE the shadow.  ``update()`` is one launch per 64 tensors (kgw_weight_avg_update) that reads
+    the optimiser's device step counter ``opt.step_dev`` -- after the launch that advanced it -- and decides on the device whether
+    this update is an event: it can sit inside a captured step and replays with a moving alpha.  The tables cover every parameter,
+    those that never get a gradient included (the first event copies them, the later ones leave them where they are)."""
+
+    def __init__(self, model, opt, cfg):
+        from copy import deepcopy
+        self.cfg = parse_weight_average(cfg)
+        if self.cfg is None:
+            raise ValueError('WeightAverage needs a configuration (optim.parse_weight_average)')
+        if not _lib.has_weight_avg():
+            raise _lib.KgwasHipError('the loaded library has no weight averaging (kgw_weight_avg_update): weight_average needs it')
+        self.model, self.opt = model, opt
+        self.avg_model = deepcopy(model).eval()
+        self._tables = []
+        pairs = list(zip(self.avg_model.parameters(), model.parameters()))
+        for i in range(0, len(pairs), _lib.WEIGHT_AVG_MAX):
+            chunk = pairs[i:i + _lib.WEIGHT_AVG_MAX]
+            n = len(chunk)
+            S = (C.c_void_p * n)(); P = (C.c_void_p * n)(); N = (C.c_int64 * n)()
+            for k, (s, p) in enumerate(chunk):
+                if not (s.is_contiguous() and p.is_contiguous() and s.dtype == p.dtype == torch.float32 and s.shape == p.shape and
+                        s.device == p.device == opt.step_dev.device and s.data_ptr() != p.data_ptr()):
+                    raise _lib.KgwasHipError('WeightAverage needs contiguous fp32 parameters on the optimiser\'s device')
+                S[k], P[k], N[k] = s.data_ptr(), p.data_ptr(), p.numel()
+            self._tables.append((n, S, P, N))
+
+    def started(self, n_updates: int) -> bool:
+        """Has the first event happened once ``n_updates`` updates are done?  Host arithmetic; nothing is read back."""
+        return int(n_updates) >= self.cfg.start_step
+
+    def parameters(self):
+        return list(self.avg_model.parameters())
+
+    @torch.no_grad()
+    def update(self):
+        for n, S, P, N in self._tables:
+            _lib.check(_lib.lib().kgw_weight_avg_update(n, S, P, N, self.opt.step_dev.data_ptr(), C.byref(self.cfg), _lib.stream_ptr()),
+                       'kgw_weight_avg_update')
 
 
 class FusedAdam:
