@@ -1284,6 +1284,72 @@ int kgw_readout_wmse_mtw_train(const float* H, const float* W, const float* b, c
                                const double* w /* [N_SNP][T] */, int32_t n, int64_t rows, int32_t T, int32_t relu, float* pred,
                                double* loss, float* dH, float* dW, float* db, double* terms, float* scratch, kgw_stream_t stream);
 
+/* The read-out node with a choice of loss (an EXTENSION: the reference knows the weighted MSE only).  THE RULE, for seed i, column t,
+ * global id g = n_id[i], residual r = pred[i][t] - y[g][t], weight w = w[g] or w[g][t], N = n T and one knee delta[t] per column:
+ *     rho_delta(r)  = r^2                      if |r| <= delta
+ *                   = delta (2 |r| - delta)    otherwise              ( = 2 * torch.nn.functional.huber_loss(delta = delta) )
+ *     rho_delta'(r) = 2 clamp(r, -delta, delta)
+ *     loss          = 1 / N * sum_i sum_t w * rho_delta[t](r)
+ *     d loss / d pred[i][t] = grad_loss / N * w * rho_delta[t]'(r)         (0 where the read-out ReLU is off)
+ * The loss is C1: both branches give delta^2 and +-2 delta at the knee.  delta[t] is finite and > 0, or +inf; delta = +inf IS the
+ * weighted MSE above and gives its bits (|r| <= delta is evaluated as !(|r| > delta): a NaN residual stays on the quadratic branch
+ * and propagates as it does today).  A pair whose weight w[g][t] is exactly 0 has its residual taken as 0 before the label is
+ * touched, as in kgw_readout_wmse_mtw_*: an exact 0 in the loss and in every gradient whatever bits its label holds.  (As there,
+ * this is the weight MATRIX's convention, T > 1 with w_cols; the shared-weight and single-column kernels multiply the residual by
+ * the weight as they always did, so a zero weight wants a finite label.)
+ * Arithmetic, that of the kernels the loss is compiled into (a compile-time loss kind of k_readout_1 / k_readout_mt: the MSE
+ * instantiations are the expressions they were, the Huber ones replace d * d and 2 d):
+ *   T = 1 (k_readout_1):  float32 residual; the quadratic branch is its float32 square; weight and sum float64; the clamp on the
+ *                         float32 residual.
+ *   T > 1 (k_readout_mt): float64 dot product, residual and term; the gradient from the residual rounded to float32, the clamp
+ *                         applied to that float32 value (the term's branch is decided on the float64 residual).
+ *   The linear branch's term delta (2 |r| - delta) is formed in float64 in both.
+ * delta travels BY VALUE in the kernel argument (lane t holds delta[t], a readlane picks column t's): no device array, and every
+ * value is checked before any launch.  The second launch (k_readout_fold), the per-seed terms, the [T][129] partials, their
+ * order and the workspaces are those of the calls above: no float atomics, a rerun is bit-identical.
+ *
+ * ONE argument record for the three families above (single column, _mt_, _mtw_) instead of a twin per entry point:
+ *   T == 1           k_readout_1, the kgw_readout_wmse_* calls (w_cols is irrelevant: [N][1] is [N]);
+ *   T > 1, w_cols 0  k_readout_mt, w [N]: kgw_readout_wmse_mt_*;    w_cols != 0: w [N][T], kgw_readout_wmse_mtw_*.
+ * With loss_kind = KGW_LOSS_MSE (delta is not read) the outputs are those calls' outputs bit for bit.
+ *   kgw_readout_loss_fwd    pred, loss (needs H W b n_id y w pred loss terms; `rows` is not read; relu: bit 0)
+ *   kgw_readout_loss_bwd    dH dW db for any *grad_loss from the forward's predictions pred_in (needs H W pred_in n_id y w grad_loss
+ *                           dH dW db scratch)
+ *   kgw_readout_loss_train  both for a loss gradient of exactly 1 (needs H W b n_id y w pred loss dH dW db terms scratch).
+ *                           fold_out != NULL with T == 1: kgw_readout_wmse_train_parts' form -- the first launch only, *fold_out
+ *                           describes the second (kgw_readout_train_fold, or a later launch's fold_in);  with T > 1:
+ *                           KGW_E_UNSUPPORTED.
+ * Workspaces: terms [n] doubles, scratch [ceil(n / 4) * T * 129] floats (only a block that holds seeds leaves a partial).  Two
+ * launches each.
+ * Refused before any launch: a needed pointer NULL: KGW_E_NULL;  n < 1, rows < n, T outside [1, 32], a loss_kind other than the two,
+ * and with KGW_LOSS_HUBER any of delta[0 .. T-1] that is NaN, <= 0 or -inf: KGW_E_RANGE.
+ * KGW_VERSION stays: the feature is detected by symbol.                                                                          */
+#define KGW_LOSS_MSE   0
+#define KGW_LOSS_HUBER 1
+#define KGW_READOUT_LOSS_ARGS_BYTES 288        /* sizeof(KgwReadoutLossArgs): asserted where the library is built and by the bindings */
+typedef struct KgwReadoutLossArgs {
+    const float* H;            /* [rows][128] */
+    const float* W;            /* [T][128] (w_lin) */
+    const float* b;            /* [T] */
+    const int32_t* n_id;       /* [n] global ids of the seeds */
+    const float* y;            /* [N][T] labels by global id */
+    const double* w;           /* [N], or [N][T] with w_cols */
+    const float* pred_in;      /* _bwd: the forward's predictions [n][T] */
+    const double* grad_loss;   /* _bwd */
+    float* pred; double* loss; float* dH; float* dW; float* db;
+    double* terms; float* scratch;
+    KgwReadoutFold* fold_out;  /* _train, optional */
+    int64_t rows;
+    int32_t n, T, relu;
+    int32_t w_cols;            /* 0: w [N];  != 0: w [N][T], a weight of exactly 0 = unobserved pair */
+    int32_t loss_kind;         /* KGW_LOSS_* */
+    int32_t reserved;
+    float delta[32];           /* KGW_LOSS_HUBER: the first T are read */
+} KgwReadoutLossArgs;
+int kgw_readout_loss_fwd(const KgwReadoutLossArgs* args, kgw_stream_t stream);
+int kgw_readout_loss_bwd(const KgwReadoutLossArgs* args, kgw_stream_t stream);
+int kgw_readout_loss_train(const KgwReadoutLossArgs* args, kgw_stream_t stream);
+
 /* Self-test of the cross-lane reductions used by the aggregate kernels (one wavefront):
  * out_half[l] = sum over l's 32-lane half, out_wave[l] = sum over the wavefront,
  * out_steps[4][64] = the four intra-row DPP butterfly stages.                                  */

@@ -161,6 +161,19 @@ class KgwReadoutFold(C.Structure):
                 ('nb', C.c_int32), ('n', C.c_int32)]
 
 
+KGW_LOSS_MSE, KGW_LOSS_HUBER = 0, 1                                       # KgwReadoutLossArgs.loss_kind (include/kgwas_hip.h)
+LOSS_KINDS = {'mse': KGW_LOSS_MSE, 'huber': KGW_LOSS_HUBER}
+READOUT_LOSS_ARGS_BYTES = 288                                             # KGW_READOUT_LOSS_ARGS_BYTES
+
+
+class KgwReadoutLossArgs(C.Structure):
+    _fields_ = [('H', C.c_void_p), ('W', C.c_void_p), ('b', C.c_void_p), ('n_id', C.c_void_p), ('y', C.c_void_p), ('w', C.c_void_p),
+                ('pred_in', C.c_void_p), ('grad_loss', C.c_void_p), ('pred', C.c_void_p), ('loss', C.c_void_p), ('dH', C.c_void_p),
+                ('dW', C.c_void_p), ('db', C.c_void_p), ('terms', C.c_void_p), ('scratch', C.c_void_p),
+                ('fold_out', C.POINTER(KgwReadoutFold)), ('rows', C.c_int64), ('n', C.c_int32), ('T', C.c_int32), ('relu', C.c_int32),
+                ('w_cols', C.c_int32), ('loss_kind', C.c_int32), ('reserved', C.c_int32), ('delta', C.c_float * 32)]
+
+
 class KgwTnReducePlan(C.Structure):
     _fields_ = [('valid', C.c_int32), ('blocks', C.c_int32), ('reserved', C.c_int32 * 2), ('opaque', C.c_int64 * 96)]
 
@@ -229,7 +242,8 @@ EXPORTS = ['kgw_version', 'kgw_status_string', 'kgw_struct_sizes', 'kgw_sample_b
            'kgw_layer_norm_relu_fwd', 'kgw_layer_norm_partial_floats', 'kgw_layer_norm_bwd', 'kgw_layer_norm_fold',
            'kgw_root_linear_fwd', 'kgw_root_linear_bwd',
            'kgw_adam_ctl', 'kgw_adam_fused_ctl', 'kgw_lr_at', 'kgw_grad_norm_partial', 'kgw_grad_norm_fold',
-           'kgw_grad_norm_workspace_doubles', 'kgw_weight_avg_update', 'kgw_weight_avg_alpha']
+           'kgw_grad_norm_workspace_doubles', 'kgw_weight_avg_update', 'kgw_weight_avg_alpha',
+           'kgw_readout_loss_fwd', 'kgw_readout_loss_bwd', 'kgw_readout_loss_train']
 
 _lib = None
 
@@ -427,6 +441,13 @@ def lib():
         L.kgw_struct_sizes(s11, 11)
         if s11[10] != C.sizeof(KgwWeightAvg):
             raise KgwasHipError(f'ABI struct size mismatch: KgwWeightAvg library {s11[10]} vs binding {C.sizeof(KgwWeightAvg)}')
+    if hasattr(L, 'kgw_readout_loss_train'):        # (absent likewise)
+        for name in ('kgw_readout_loss_fwd', 'kgw_readout_loss_bwd', 'kgw_readout_loss_train'):
+            getattr(L, name).argtypes = [C.POINTER(KgwReadoutLossArgs), C.c_void_p]
+        # (the library asserts the same constant where it is built: kgw_struct_sizes' list is closed at eleven entries)
+        if C.sizeof(KgwReadoutLossArgs) != READOUT_LOSS_ARGS_BYTES:
+            raise KgwasHipError(f'ABI struct size mismatch: KgwReadoutLossArgs header {READOUT_LOSS_ARGS_BYTES} vs binding '
+                                f'{C.sizeof(KgwReadoutLossArgs)}')
     L.kgw_accumulate_stats.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
     L.kgw_accumulate_stats_tick.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     _lib = L
@@ -494,7 +515,13 @@ def has_weight_avg() -> bool:
     return hasattr(lib(), 'kgw_weight_avg_update')
 
 
-KGW_ORDER_SEEDS, KGW_ORDER_BATCHES = 1, 2     # kgw_epoch_order's modes (include/kgwas_hip.h)
+def has_readout_loss() -> bool:
+    """Does the loaded library have the read-out node with a loss kind (kgw_readout_loss_fwd / _bwd / _train: the Huber loss)?  An
+    older library named by KGW_LIB_PATH for an A/B run lacks the symbols."""
+    return hasattr(lib(), 'kgw_readout_loss_train')
+
+
+KGW_ORDER_SEEDS, KGW_ORDER_BATCHES = 1, 2    # kgw_epoch_order's modes (include/kgwas_hip.h)
 EPOCH_ORDER_BLOCK, EPOCH_ORDER_GRID = 256, 2048   # its launch: threads per block, most blocks (KGW_BLK, KGW_GRID of csrc/kgw_common.h)
 
 

@@ -63,16 +63,38 @@ extern "C" int kgw_wmse_bwd(const float* pred, const int32_t* n_id, const float*
 namespace {
 
 enum { KGW_MT_FWD = 0, KGW_MT_TRAIN = 1, KGW_MT_BWD = 2, KGW_MT_BWD_PRED = 3 };    // (the last: k_readout_mt only)
+// The kernels' one mode argument also carries the loss kind: bit 3 set = the Huber instantiation of that mode.  The MSE
+// instantiations therefore keep their names (k_readout_1<1>, k_readout_mt<1, true>: launch fixtures and profiles know them).
+enum { KGW_MT_HUBER = 8, KGW_MT_MODE_MASK = 7 };
+constexpr int kgw_mt_loss(int mode_l) { return (mode_l & KGW_MT_HUBER) ? KGW_LOSS_HUBER : KGW_LOSS_MSE; }
+constexpr int kgw_mt_mode_l(int mode, int loss) { return mode | (loss == KGW_LOSS_HUBER ? KGW_MT_HUBER : 0); }
+
+// The loss kind of the read-out kernels is a compile-time argument (LOSS = KGW_LOSS_MSE | KGW_LOSS_HUBER, include/kgwas_hip.h): the MSE
+// instantiations compile from the expressions they had, the Huber ones put rho_delta / rho_delta' in the place of d * d / 2 d.  The knees
+// delta[t] travel BY VALUE in the kernel argument (an empty record for MSE), so the C call has checked them before any launch.
+template <int LOSS> struct KgwKnees { float v[32]; };
+template <> struct KgwKnees<KGW_LOSS_MSE> {};
+
+// |d| <= delta as !(|d| > delta): a NaN residual stays on the quadratic branch and propagates as it does under MSE, and delta = +inf
+// never leaves that branch, whatever d holds -- the MSE bits.
+__device__ __forceinline__ bool kgw_huber_quadratic(float d, float delta) { return !(fabsf(d) > delta); }
+__device__ __forceinline__ bool kgw_huber_quadratic(double d, double delta) { return !(fabs(d) > delta); }
+// rho_delta'(d) / 2 = clamp(d, -delta, delta)
+__device__ __forceinline__ float kgw_huber_clamp(float d, float delta) { return kgw_huber_quadratic(d, delta) ? d : copysignf(delta, d); }
+// the linear branch's term delta (2 |d| - delta), in float64
+__device__ __forceinline__ double kgw_huber_linear(double d, double delta) { return delta * (2.0 * fabs(d) - delta); }
 
 // _FWD: prediction and loss term of seed i.  _TRAIN (a unit loss gradient: loss.backward()): forward and backward in ONE launch --
 // prediction, loss term, d prediction, the dH row and the block's weight-gradient partial.  _BWD: the same from the forward's
 // predictions and the loss gradient gloss[0].
-template <int MODE>
+template <int MODE_L>
 __global__ void __launch_bounds__(256) k_readout_1(const float* __restrict__ H, const float* __restrict__ wl, const float* __restrict__ bl,
                                                    const float* __restrict__ pred_in, const int32_t* __restrict__ n_id,
                                                    const float* __restrict__ y, const double* __restrict__ w, int n, int64_t rows,
                                                    int relu, const double* __restrict__ gloss, float* __restrict__ pred,
-                                                   double* __restrict__ terms, float* __restrict__ dH, float* __restrict__ part) {
+                                                   double* __restrict__ terms, float* __restrict__ dH, float* __restrict__ part,
+                                                   const KgwKnees<kgw_mt_loss(MODE_L)> knees) {
+    constexpr int MODE = MODE_L & KGW_MT_MODE_MASK, LOSS = kgw_mt_loss(MODE_L);
     __shared__ float sw[4][KGW_C + 1];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int64_t i = (int64_t)blockIdx.x * 4 + wave;
@@ -90,12 +112,19 @@ __global__ void __launch_bounds__(256) k_readout_1(const float* __restrict__ H, 
         }
         const int g = n_id[i];
         const float d = p - y[g];
+        double rho = (double)(d * d);                      // MSE: the float32 square;  dc: rho' / 2
+        float dc = d;
+        if constexpr (LOSS == KGW_LOSS_HUBER) {
+            const float delta = knees.v[0];
+            if (!kgw_huber_quadratic(d, delta)) rho = kgw_huber_linear((double)d, (double)delta);
+            dc = kgw_huber_clamp(d, delta);
+        }
         if (MODE != KGW_MT_BWD && lane == 0) {
             pred[i] = p;
-            terms[i] = w[g] * (double)(d * d);
+            terms[i] = w[g] * rho;
         }
         if (MODE == KGW_MT_FWD) return;
-        dp = (float)((MODE == KGW_MT_BWD ? gloss[0] : 1.0) / (double)n * w[g]) * (2.0f * d);
+        dp = (float)((MODE == KGW_MT_BWD ? gloss[0] : 1.0) / (double)n * w[g]) * (2.0f * dc);
         if ((relu & 1) && !(p > 0.f)) dp = 0.f;
         // (bit 1 of `relu`: H itself is the output of a ReLU whose backward the caller folds in here: dH *= (H > 0))
         const bool mk = (relu & 2) != 0;
@@ -148,13 +177,13 @@ inline int kgw_readout_fold_launch(const float* part, int nb, int T, const doubl
 }
 
 // the first launch of the single-column entries: _FWD covers the seeds, the others every row of dH
-template <int MODE>
+template <int MODE, int LOSS = KGW_LOSS_MSE>
 int kgw_readout_1_launch(const float* H, const float* w_lin, const float* b_lin, const float* pred_in, const int32_t* n_id, const float* y,
                          const double* w, int32_t n, int64_t rows, int32_t relu, const double* gloss, float* pred, double* terms, float* dH,
-                         float* part, hipStream_t st) {
+                         float* part, hipStream_t st, const KgwKnees<LOSS> knees = KgwKnees<LOSS>{}) {
     if (n <= 0 || rows < n) return KGW_E_RANGE;
-    k_readout_1<MODE><<<(unsigned)(((MODE == KGW_MT_FWD ? n : rows) + 3) / 4), 256, 0, st>>>(H, w_lin, b_lin, pred_in, n_id, y, w, n, rows, relu,
-                                                                                            gloss, pred, terms, dH, part);
+    k_readout_1<kgw_mt_mode_l(MODE, LOSS)><<<(unsigned)(((MODE == KGW_MT_FWD ? n : rows) + 3) / 4), 256, 0, st>>>(H, w_lin, b_lin, pred_in, n_id, y, w, n, rows,
+                                                                                                  relu, gloss, pred, terms, dH, part, knees);
     KGW_LAUNCH_CHECK();
     return KGW_OK;
 }
@@ -268,8 +297,9 @@ __device__ __forceinline__ double kgw_wave_allsum_f64(double v) {
 }
 
 // W_COLS: a.w is [N_SNP][T] (one weight per SNP and column, 0.0 = unobserved) instead of [N_SNP]
-template <int MODE, bool W_COLS = false>
-__global__ void __launch_bounds__(256) k_readout_mt(const KgwMtArgs a) {
+template <int MODE_L, bool W_COLS = false>
+__global__ void __launch_bounds__(256) k_readout_mt(const KgwMtArgs a, const KgwKnees<kgw_mt_loss(MODE_L)> knees = KgwKnees<kgw_mt_loss(MODE_L)>{}) {
+    constexpr int MODE = MODE_L & KGW_MT_MODE_MASK, LOSS = kgw_mt_loss(MODE_L);
     __shared__ float sW[KGW_MT_MAX * KGW_C];
     __shared__ float sH[4][KGW_C + 1];
     __shared__ float sG[4][KGW_MT_MAX];
@@ -297,6 +327,8 @@ __global__ void __launch_bounds__(256) k_readout_mt(const KgwMtArgs a) {
             if (mine) y_mine = a.y[(int64_t)g * T + lane];
         }
         if ((MODE == KGW_MT_FWD || MODE == KGW_MT_TRAIN) && mine) b_mine = a.b[lane];
+        float knee_mine = 0.f;                             // (Huber: lane t holds delta[t]; iteration t reads it with a readlane)
+        if constexpr (LOSS == KGW_LOSS_HUBER) knee_mine = knees.v[lane & (KGW_MT_MAX - 1)];
         if ((MODE == KGW_MT_BWD || MODE == KGW_MT_BWD_PRED) && mine) in_mine = a.pred_in[i * T + lane];
         if (W_COLS) {
             if (MODE == KGW_MT_TRAIN) base = 1.0 / ((double)n * (double)T);
@@ -333,9 +365,16 @@ __global__ void __launch_bounds__(256) k_readout_mt(const KgwMtArgs a) {
                     d64 = p64 - (double)kgw_lane_value(y_mine, t);
                 }
                 const float d = (float)d64;
-                if (MODE != KGW_MT_BWD) term += wg * (d64 * d64);
+                double rho = d64 * d64;                    // MSE: the float64 square;  dc: rho' / 2 of the float32 residual
+                float dc = d;
+                if constexpr (LOSS == KGW_LOSS_HUBER) {    // (the term from the float64 residual, the gradient from the clamped float32 one)
+                    const float delta = kgw_lane_value(knee_mine, t);
+                    if (!kgw_huber_quadratic(d64, (double)delta)) rho = kgw_huber_linear(d64, (double)delta);
+                    dc = kgw_huber_clamp(d, delta);
+                }
+                if (MODE != KGW_MT_BWD) term += wg * rho;
                 if (MODE != KGW_MT_FWD) {
-                    dp = scale * (2.0f * d);
+                    dp = scale * (2.0f * dc);
                     if ((a.relu & 1) && !(p > 0.f)) dp = 0.f;
                 }
             }
@@ -482,4 +521,90 @@ extern "C" int kgw_readout_wmse_mtw_train(const float* H, const float* W, const 
                                           double* loss, float* dH, float* dW, float* db, double* terms, float* scratch,
                                           kgw_stream_t stream_) {
     return kgw_mt_wmse_train<true>(H, W, b, n_id, y, w, n, rows, T, relu, pred, loss, dH, dW, db, terms, scratch, stream_);
+}
+
+// ======================================================================================================
+// kgw_readout_loss_*: the three read-out families above behind ONE argument record with a loss kind (the rule: include/kgwas_hip.h,
+// KgwReadoutLossArgs).  T == 1: k_readout_1; T > 1: k_readout_mt, the weight form chosen by w_cols.  KGW_LOSS_MSE launches the very
+// instantiations of the calls above; KGW_LOSS_HUBER theirs with the knees in the kernel argument.  Same grids, folds and workspaces.
+// ======================================================================================================
+namespace {
+
+enum { KGW_RL_FWD = 0, KGW_RL_BWD = 1, KGW_RL_TRAIN = 2 };
+
+// every refusal of the three calls: nothing is launched unless this returns KGW_OK
+inline int kgw_readout_loss_check(const KgwReadoutLossArgs* a, int form) {
+    if (!a || !a->H || !a->W || !a->n_id || !a->y || !a->w) return KGW_E_NULL;
+    if (form != KGW_RL_BWD && (!a->b || !a->pred || !a->loss || !a->terms)) return KGW_E_NULL;
+    if (form == KGW_RL_BWD && (!a->pred_in || !a->grad_loss)) return KGW_E_NULL;
+    if (form != KGW_RL_FWD && (!a->dH || !a->dW || !a->db || !a->scratch)) return KGW_E_NULL;
+    if (kgw_mt_range(a->n, form == KGW_RL_FWD ? (int64_t)a->n : a->rows, a->T)) return KGW_E_RANGE;
+    if (a->loss_kind != KGW_LOSS_MSE && a->loss_kind != KGW_LOSS_HUBER) return KGW_E_RANGE;
+    if (a->loss_kind == KGW_LOSS_HUBER)
+        for (int t = 0; t < a->T; ++t)
+            if (!(a->delta[t] > 0.f)) return KGW_E_RANGE;                  // NaN, 0, negative, -inf (+inf passes: the MSE)
+    if (form == KGW_RL_TRAIN && a->fold_out != nullptr && a->T > 1) return KGW_E_UNSUPPORTED;
+    return KGW_OK;
+}
+
+template <int MODE, bool W_COLS, int LOSS>
+int kgw_readout_loss_mt(const KgwReadoutLossArgs* r, const KgwKnees<LOSS> knees, hipStream_t st) {
+    KgwMtArgs a{};
+    a.H = r->H; a.W = r->W; a.n_id = r->n_id; a.y = r->y; a.w = r->w; a.n = r->n; a.T = r->T; a.relu = r->relu;
+    a.rows = MODE == KGW_MT_FWD ? (int64_t)r->n : r->rows;
+    if (MODE != KGW_MT_BWD) { a.b = r->b; a.pred = r->pred; a.terms = r->terms; }
+    if (MODE == KGW_MT_BWD) { a.pred_in = r->pred_in; a.gloss = r->grad_loss; }
+    if (MODE != KGW_MT_FWD) { a.dH = r->dH; a.part = r->scratch; }
+    k_readout_mt<kgw_mt_mode_l(MODE, LOSS), W_COLS><<<(unsigned)((a.rows + 3) / 4), 256, 0, st>>>(a, knees);
+    KGW_LAUNCH_CHECK();
+    if (MODE == KGW_MT_FWD) return kgw_readout_fold_launch(nullptr, 0, r->T, r->terms, r->n, nullptr, nullptr, r->loss, st);
+    return kgw_readout_fold_launch(r->scratch, (r->n + 3) / 4, r->T, MODE == KGW_MT_TRAIN ? r->terms : nullptr, r->n, r->dW, r->db,
+                                   MODE == KGW_MT_TRAIN ? r->loss : nullptr, st);
+}
+
+template <int MODE, int LOSS>
+int kgw_readout_loss_run(const KgwReadoutLossArgs* r, const KgwKnees<LOSS> knees, hipStream_t st) {
+    if (r->T > 1) return r->w_cols ? kgw_readout_loss_mt<MODE, true, LOSS>(r, knees, st) : kgw_readout_loss_mt<MODE, false, LOSS>(r, knees, st);
+    const int nb = (r->n + 3) / 4;
+    if (MODE == KGW_MT_FWD) {
+        const int rc = kgw_readout_1_launch<MODE, LOSS>(r->H, r->W, r->b, nullptr, r->n_id, r->y, r->w, r->n, r->n, r->relu & 1, nullptr,
+                                                        r->pred, r->terms, nullptr, nullptr, st, knees);
+        return rc != KGW_OK ? rc : kgw_readout_fold_launch(nullptr, 0, 1, r->terms, r->n, nullptr, nullptr, r->loss, st);
+    }
+    if (MODE == KGW_MT_BWD) {
+        const int rc = kgw_readout_1_launch<MODE, LOSS>(r->H, r->W, nullptr, r->pred_in, r->n_id, r->y, r->w, r->n, r->rows, r->relu,
+                                                        r->grad_loss, nullptr, nullptr, r->dH, r->scratch, st, knees);
+        return rc != KGW_OK ? rc : kgw_readout_fold_launch(r->scratch, nb, 1, nullptr, r->n, r->dW, r->db, nullptr, st);
+    }
+    const int rc = kgw_readout_1_launch<MODE, LOSS>(r->H, r->W, r->b, nullptr, r->n_id, r->y, r->w, r->n, r->rows, r->relu, nullptr, r->pred,
+                                                    r->terms, r->dH, r->scratch, st, knees);
+    if (rc != KGW_OK) return rc;
+    const KgwReadoutFold f{r->scratch, r->terms, r->dW, r->db, r->loss, nb, r->n};
+    if (r->fold_out != nullptr) { *r->fold_out = f; return KGW_OK; }           // (kgw_readout_wmse_train_parts' form)
+    return kgw_readout_train_fold(&f, (kgw_stream_t)st);
+}
+
+template <int MODE>
+int kgw_readout_loss_entry(const KgwReadoutLossArgs* r, int form, kgw_stream_t stream_) {
+    static_assert(sizeof(KgwReadoutLossArgs) == KGW_READOUT_LOSS_ARGS_BYTES, "KgwReadoutLossArgs: the size the bindings assert");
+    const int rc = kgw_readout_loss_check(r, form);
+    if (rc != KGW_OK) return rc;
+    if (r->loss_kind == KGW_LOSS_MSE) return kgw_readout_loss_run<MODE, KGW_LOSS_MSE>(r, KgwKnees<KGW_LOSS_MSE>{}, (hipStream_t)stream_);
+    KgwKnees<KGW_LOSS_HUBER> knees;
+    for (int t = 0; t < KGW_MT_MAX; ++t) knees.v[t] = r->delta[t];
+    return kgw_readout_loss_run<MODE, KGW_LOSS_HUBER>(r, knees, (hipStream_t)stream_);
+}
+
+}  // namespace
+
+extern "C" int kgw_readout_loss_fwd(const KgwReadoutLossArgs* args, kgw_stream_t stream_) {
+    return kgw_readout_loss_entry<KGW_MT_FWD>(args, KGW_RL_FWD, stream_);
+}
+
+extern "C" int kgw_readout_loss_bwd(const KgwReadoutLossArgs* args, kgw_stream_t stream_) {
+    return kgw_readout_loss_entry<KGW_MT_BWD>(args, KGW_RL_BWD, stream_);
+}
+
+extern "C" int kgw_readout_loss_train(const KgwReadoutLossArgs* args, kgw_stream_t stream_) {
+    return kgw_readout_loss_entry<KGW_MT_TRAIN>(args, KGW_RL_TRAIN, stream_);
 }

@@ -234,7 +234,7 @@ class GraphTrainStep:
     def __init__(self, run, input_nodes, batch_size: int, lr: float = 1e-4, weight_decay: float = 5e-4,
                  margin: float = 1.03, shard_gene_layer: bool = None, cache_batches: bool = False, num_neighbors=None,
                  sample_seed: int = 0, epoch_order: str = 'fixed', epochs: int = None, rank: int = 0, world: int = 1,
-                 lr_schedule=None, grad_clip_norm=None, weight_average=None):
+                 lr_schedule=None, grad_clip_norm=None, weight_average=None, loss=None):
         """``num_neighbors`` (None = the reference's [-1] * L): PyG's list form of per-hop fan-outs.  With a finite fan-out the
         batches are redrawn every epoch from (``sample_seed``, epoch, batch index) -- ``set_epoch`` names the epoch, a step past
         the last batch moves on to the next one by itself -- the capacities of the static layout are bounds that hold for every
@@ -271,9 +271,14 @@ class GraphTrainStep:
         'epoch' is this trainer's batches): ``self.avg_model`` is an EMA / SWA shadow of the model, moved by ONE launch at the very end
         of the captured step (kgw_weight_avg_update, behind the launch that advanced the step counter it reads); whether an update
         is an averaging event, and its alpha, are decided on the device, so the step replays.  Nothing else about the route changes.
-        Several ranks: the launch follows the eager Adam launch, the same update everywhere (run on one rank only so far)."""
+        Several ranks: the launch follows the eager Adam launch, the same update everywhere (run on one rank only so far).
+        ``loss`` (None | 'mse' | 'huber' | a delta | a dict | an optim.LossRule: optim.parse_loss): the read-out node's loss.  A Huber
+        rule takes the node's kgw_readout_loss_* entry -- the same two launches, the deferred fold and the fused optimiser launch
+        included -- so nothing else about the route changes."""
         self.run = run
         self.model = run.model
+        from .optim import parse_loss
+        self.loss_rule = parse_loss(loss, self.model.lin.out_features)
         self.batch_size = int(batch_size)
         dev = torch.device(run.device)
         self.input_type, ids = input_nodes
@@ -451,7 +456,8 @@ class GraphTrainStep:
         self.opt.zero_grad(set_to_none=True)
         with ops.readout_fold_deferred():                          # (the backward pass below always runs)
             loss, _ = self.model.forward_loss(batch.x_dict, batch.edge_index_dict, bs, batch.n_id(self.input_type),
-                                              self.dg.y[self.input_type], self.ld_w, unit_grad=True)      # kgwas.py:137-145
+                                              self.dg.y[self.input_type], self.ld_w, unit_grad=True,
+                                              loss_rule=self.loss_rule)                                   # kgwas.py:137-145
         # fused optimiser launch: the weight-gradient products that feed only Adam stop after their first launch, their last
         # sums, the update, the step counter and the running totals are ONE launch (ops.GradSink, kgw_adam_fused)
         sink = ops.GradSink() if self.fused_adam else None
@@ -484,7 +490,8 @@ class GraphTrainStep:
         mlp_out = []
         with ops.readout_fold_deferred():
             loss, _ = self.model.forward_loss(batch.x_dict, batch.edge_index_dict, bs, batch.n_id(self.input_type),
-                                              self.dg.y[self.input_type], self.ld_w, mlp_out=mlp_out, unit_grad=True)
+                                              self.dg.y[self.input_type], self.ld_w, mlp_out=mlp_out, unit_grad=True,
+                                              loss_rule=self.loss_rule)
         hs = [h for h in mlp_out if h.requires_grad]
         late = self._late_params()
         early = [p for p in self.model.parameters() if p.requires_grad and id(p) not in late]

@@ -172,13 +172,14 @@ class KGWAS:
         self.infer_loader = NeighborLoader(self.data.data, num_neighbors=[-1] * L,
                                            input_nodes=('SNP', infer_idx), **eval_kwargs)     # :112-113
 
-    def train_step(self, batch, optimizer, ld_w, world: int = 1):
-        """kgwas.py:130-151 for one batch; returns the (float64) loss tensor, no host sync."""
+    def train_step(self, batch, optimizer, ld_w, world: int = 1, loss_rule=None):
+        """kgwas.py:130-151 for one batch; returns the (float64) loss tensor, no host sync.  ``loss_rule`` (optim.parse_loss; None =
+        the reference's weighted MSE): the read-out node's loss."""
         optimizer.zero_grad(set_to_none=True)
         bs = batch['SNP'].batch_size
         # forward + mean(ld_weight * (pred - y)**2) in float64 (kgwas.py:137-145); labels / weights by the seeds' ids
         loss, _ = self.model.forward_loss(batch.x_dict, batch.edge_index_dict, bs, batch.n_id('SNP'), batch.dg.y['SNP'], ld_w,
-                                          unit_grad=True)
+                                          unit_grad=True, loss_rule=loss_rule)
         loss.backward(gradient=ops.unit_gradient(loss.device))      # (the resident 1.0: no ones_like fill, see readout_weighted_mse)
         if world > 1:
             kdist.allreduce_grads(self.model, world)
@@ -186,7 +187,7 @@ class KGWAS:
         return loss
 
     def _train_sharded(self, batch_size, lr, weight_decay, total_epoch, save_best_model, save_name, use_graph=True,
-                       lr_schedule=None, grad_clip_norm=None, weight_average=None):
+                       lr_schedule=None, grad_clip_norm=None, weight_average=None, loss=None):
         """kgwas/kgwas.py:85-212 in the SNP-sharded multi-GPU mode (kgwas_amd/shard.py): every rank works on the SAME
         batches of the reference's order and owns the SNPs of one id range; validation / test / inference predictions are
         computed shard-wise and summed, so every rank sees the same metrics and keeps the same best model."""
@@ -197,6 +198,9 @@ class KGWAS:
         if weight_average is not None:
             raise NotImplementedError("weight_average is not available with parallelism='shard': the sharded step does not run "
                                       "the weight-averaging launch; use parallelism='seed'")
+        if loss is not None:
+            raise NotImplementedError("loss is not available with parallelism='shard': the sharded step has its own read-out and "
+                                      "loss; use parallelism='seed'")
         if getattr(self.model, 'heads', 1) > 1:
             raise NotImplementedError("gat_num_head > 1 is not available with parallelism='shard': the partial softmax states of "
                                       "the SNP-sharded exchange are single-head; use parallelism='seed'")
@@ -263,7 +267,7 @@ class KGWAS:
 
     def train(self, batch_size=512, num_workers=0, lr=1e-4, weight_decay=5e-4, epoch=10, save_best_model=True,
               save_name=None, data_to_cuda=False, use_graph=True, parallelism='seed', num_neighbors=None, shuffle=False,
-              lr_schedule=None, grad_clip_norm=None, weight_average=None):
+              lr_schedule=None, grad_clip_norm=None, weight_average=None, loss=None):
         """Same signature and defaults as kgwas/kgwas.py:85-87.  ``use_graph`` (extra, default on): run the
         training step as one captured HIP graph (kgwas_amd/graph_step.py); off = eager launches, same math.
         ``parallelism`` (extra; matters under torch.distributed): 'seed' = every rank trains on its slice of each batch
@@ -294,10 +298,20 @@ class KGWAS:
         go through -- is a copy of it when its Pearson is the best so far; an epoch that ends before the first event does what the
         default run does.  The eager loop (``use_graph=False``) runs FusedAdam too: both loops the same kernels and the same
         counter.  An argument of the run: nothing enters config.pkl.  Not available with parallelism='shard'; with several ranks
-        every rank applies the same update, so the shadows agree (run on one rank only so far)."""
+        every rank applies the same update, so the shadows agree (run on one rank only so far).
+        ``loss`` (extra, default None = the reference's LD-weighted MSE, kgwas/kgwas.py:139-145): 'mse' | 'huber' (delta 1.0) | a
+        float (Huber with that delta) | a dict with ``kind`` and ``delta`` -- a float > 0 or one per label column (traits have their
+        own scales); optim.parse_loss, the rule: include/kgwas_hip.h, KgwReadoutLossArgs.  The TRAINING loss becomes the weighted
+        Huber loss 1/N sum w rho_delta(pred - y), rho = r^2 up to |r| = delta and delta (2 |r| - delta) beyond: a residual's pull
+        on the gradient is bounded by 2 delta w / N, so the SNPs of a top locus no longer decide a batch.  It is computed inside the
+        read-out node's own kernels (single trait, T traits, per-trait weights with unobserved pairs), so the captured step keeps its
+        route, its launches and its fused optimiser launch, and the eager loop runs the same kernels.  delta = +inf is the MSE, to
+        the bit.  Validation, test and model selection keep MSE / Pearson.  An argument of the run: nothing enters config.pkl.  Not
+        available with parallelism='shard'; parallelism='seed' needs nothing new (run on one rank only so far)."""
         total_epoch = epoch
-        from .optim import check_grad_clip_norm, parse_lr_schedule, parse_weight_average
+        from .optim import check_grad_clip_norm, parse_lr_schedule, parse_weight_average, parse_loss
         grad_clip_norm = check_grad_clip_norm(grad_clip_norm)
+        loss_rule = parse_loss(loss, self.model.lin.out_features)    # (a ValueError before anything is built; 'mse' is the default route)
         controlled = lr_schedule is not None or grad_clip_norm is not None
         parse_weight_average(weight_average, 1)                      # (a ValueError before anything is built; 'epoch' is resolved below)
         if isinstance(shuffle, (bool, np.bool_)):
@@ -327,7 +341,8 @@ class KGWAS:
         if parallelism == 'shard':
             return self._train_sharded(batch_size, lr, weight_decay, total_epoch, save_best_model, save_name, use_graph,
                                        **({'lr_schedule': lr_schedule, 'grad_clip_norm': grad_clip_norm} if controlled else {}),
-                                       **({'weight_average': weight_average} if weight_average is not None else {}))
+                                       **({'weight_average': weight_average} if weight_average is not None else {}),
+                                       **({'loss': loss_rule} if loss_rule is not None else {}))
         if parallelism != 'seed':
             raise ValueError(f"parallelism {parallelism!r}: 'seed' or 'shard'")
         print_sys('Creating data loader...')
@@ -351,7 +366,7 @@ class KGWAS:
             shuffled = {} if epoch_order == 'fixed' else {'epoch_order': epoch_order, 'epochs': total_epoch, 'rank': rank, 'world': world}
             graph_step = GraphTrainStep(self, (self.train_loader.input_type, self.train_loader.ids.cpu().numpy()),
                                         self.train_loader.batch_size, lr=lr, weight_decay=weight_decay,
-                                        shard_gene_layer=None, **shuffled, **controls,
+                                        shard_gene_layer=None, **shuffled, **controls, loss=loss_rule,
                                         # (the loader's batch order is fixed, kgwas.py:93-101: the batches sampled in epoch 1 are
                                         #  kept in HBM and put back in later epochs -- graph_step.BatchCache)
                                         cache_batches=total_epoch > 1, num_neighbors=num_neighbors, sample_seed=self.seed)
@@ -387,7 +402,7 @@ class KGWAS:
                     step, batch = item
                     if dropout:                              # (the word the captured step copies in: the same masks either way)
                         self.model.set_dropout_word(dropout_word(self.seed, ep, step))
-                    loss = self.train_step(batch, optimizer, ld_w, world)
+                    loss = self.train_step(batch, optimizer, ld_w, world, loss_rule)
                     if wavg is not None:
                         wavg.update()                        # (behind the launch that advanced the counter, as in the captured step)
                 if self.wandb:

@@ -1086,7 +1086,7 @@ class HeteroGNN(nn.Module):
         return attn
 
     def forward_loss(self, x_dict, edge_index_dict, batch_size, n_id, y_all, w_all, mlp_out=None, unit_grad=False,
-                     edge_attr_dict=None):
+                     edge_attr_dict=None, loss_rule=None):
         """The training step's forward (kgwas/kgwas.py:137-145): HeteroGNN.forward followed by
         mean(w_all[n_id] * (pred - y_all[n_id])**2), with the read-out Linear + ReLU (model.py:86) and the loss fused
         into one node.  Returns (loss [float64 scalar], pred [batch_size]) -- with ``out_channels = T > 1`` (a shared trunk read out
@@ -1094,7 +1094,9 @@ class HeteroGNN(nn.Module):
         (one weight per SNP) or [N,T] (per-trait weights, 0 = unobserved pair: ops.readout_weighted_mse).  ``mlp_out`` (list): receives the feature MLPs'
         output tensors -- the cut between the two halves of a backward pass whose first half's gradients are all-reduced
         while the second half runs (multi-GPU GraphTrainStep).  ``unit_grad``: the caller will backpropagate exactly
-        ``loss.backward()`` (gradient 1): the read-out node then does its forward and backward in two launches."""
+        ``loss.backward()`` (gradient 1): the read-out node then does its forward and backward in two launches.  ``loss_rule``
+        (optim.parse_loss; None = the MSE above): a weighted Huber loss in the place of the square, in the same node
+        (ops.readout_weighted_mse)."""
         batch: Optional[SampledBatch] = getattr(x_dict, 'kgw_batch', None) or getattr(edge_index_dict, 'kgw_batch', None)
         if batch is None:
             batch = self._block_from_coo(x_dict, edge_index_dict, edge_attr_dict)
@@ -1120,7 +1122,7 @@ class HeteroGNN(nn.Module):
         h, _ = self._fused_layers(batch, h, hbuf=hbuf, last_premasked=gat, folded=fold, prep=prep, dropout=drop,
                                   hdrop=self._hidden_dropout())
         return ops.readout_weighted_mse(h['SNP'], self.lin.weight, self.lin.bias, n_id, y_all, w_all, batch_size,
-                                        relu=not self.no_relu, h_is_relu=gat, unit_grad=unit_grad)
+                                        relu=not self.no_relu, h_is_relu=gat, unit_grad=unit_grad, loss_rule=loss_rule)
 
     # ------------------------------------------------------------------------------------------
     @torch.no_grad()

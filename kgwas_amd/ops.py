@@ -2938,12 +2938,38 @@ def _for_gradient(gloss, grads):
     return tuple(g * k for g in grads)
 
 
+def _readout_loss_call(which: str, rule, H, W, n_id, y_all, w_all, n: int, relu_word: int, fold_out=None, **tensors):
+    """One of kgw_readout_loss_fwd / _bwd / _train (``which``) for the loss rule ``rule`` (optim.LossRule): the argument record from
+    the node's tensors (``tensors``: the record's remaining pointer fields by name), the call, its name counted in ROUTES."""
+    if not _lib.has_readout_loss():
+        raise _lib.KgwasHipError('the loaded library has no read-out node with a loss kind (kgw_readout_loss_train): loss= needs it')
+    T = W.shape[0] if W.dim() == 2 else 1
+    if len(rule.delta) != T:
+        raise ValueError(f'a loss rule with {len(rule.delta)} deltas for a read-out of {T} column(s)')
+    a = _lib.KgwReadoutLossArgs()
+    a.H, a.W, a.n_id, a.y, a.w = H.data_ptr(), W.data_ptr(), n_id.data_ptr(), y_all.data_ptr(), w_all.data_ptr()
+    a.rows, a.n, a.T, a.relu = H.shape[0], n, T, relu_word
+    a.w_cols = 1 if w_all.dim() == 2 else 0
+    a.loss_kind = _lib.LOSS_KINDS[rule.kind]
+    for t, d in enumerate(rule.delta):
+        a.delta[t] = d
+    for name, t in tensors.items():
+        setattr(a, name, t.data_ptr())
+    if fold_out is not None:
+        a.fold_out = C.pointer(fold_out)
+    name = 'kgw_readout_loss_' + which
+    _lib.check(getattr(_lib.lib(), name)(C.byref(a), _lib.stream_ptr()), name)
+    _route(name)
+
+
 class _ReadoutWeightedMSE(torch.autograd.Function):
     """loss = mean(w[n_id] * ([relu](H[:n] @ w_lin^T + b_lin) - y[n_id])**2): the read-out Linear(128 -> 1) of the seed
-    rows (kgwas/model.py:86) and the weighted MSE (kgwas/kgwas.py:139-145) as one node, two launches per step."""
+    rows (kgwas/model.py:86) and the weighted MSE (kgwas/kgwas.py:139-145) as one node, two launches per step.
+    ``loss_rule`` (optim.LossRule, None = the MSE and exactly the calls above): the same node, launches and fold protocol on
+    kgw_readout_loss_*, the rule's loss in the place of the square."""
 
     @staticmethod
-    def forward(ctx, H, w_lin, b_lin, n_id, y_all, w_all, n, relu, h_is_relu=False, unit_grad=False):
+    def forward(ctx, H, w_lin, b_lin, n_id, y_all, w_all, n, relu, h_is_relu=False, unit_grad=False, loss_rule=None):
         H = H.contiguous()
         assert H.dtype == torch.float32 and H.shape[1] == KGW_C and H.shape[0] >= n and w_lin.numel() == KGW_C
         assert n_id.dtype == torch.int32 and y_all.dtype == torch.float32 and w_all.dtype == torch.float64
@@ -2951,7 +2977,7 @@ class _ReadoutWeightedMSE(torch.autograd.Function):
         pred = torch.empty(n, device=dev)
         loss = torch.empty((), dtype=torch.float64, device=dev)
         terms = torch.empty(n, dtype=torch.float64, device=dev)
-        ctx.n, ctx.relu, ctx.h_is_relu = n, relu, h_is_relu
+        ctx.n, ctx.relu, ctx.h_is_relu, ctx.loss_rule = n, relu, h_is_relu, loss_rule
         ctx.mark_non_differentiable(pred)
         ctx.set_materialize_grads(False)
         ctx.ready = None
@@ -2960,7 +2986,14 @@ class _ReadoutWeightedMSE(torch.autograd.Function):
             dH, dw, db = torch.empty_like(H), torch.empty_like(w_lin), torch.empty(1, device=dev)
             part = _readout_part(H.shape[0], 1, dev)
             ctx.fold = None
-            if _DEFER_READOUT_FOLD and READOUT_FOLD_DEFERRED:
+            defer = _DEFER_READOUT_FOLD and READOUT_FOLD_DEFERRED
+            if loss_rule is not None:              # (the same two forms: fold_out = kgw_readout_wmse_train_parts' protocol)
+                f = _lib.KgwReadoutFold() if defer else None
+                _readout_loss_call('train', loss_rule, H, w_lin, n_id, y_all, w_all, n, _relu_word(relu, h_is_relu), fold_out=f,
+                                   b=b_lin, pred=pred, loss=loss, dH=dH, dW=dw, db=db, terms=terms, scratch=part)
+                if defer:
+                    ctx.fold = (f, (part, terms, loss))
+            elif defer:
                 # first launch only: the fold of the partial sums waits for the backward pass, where it rides in the next launch
                 # of a captured step (GradSink.pending_fold) or is launched first thing otherwise.  The loss is NOT written until
                 # then -- only a caller that always runs the backward takes this form (``readout_fold_deferred``)
@@ -2977,16 +3010,19 @@ class _ReadoutWeightedMSE(torch.autograd.Function):
                            'kgw_readout_wmse_train')
             ctx.ready = (dH, dw, db)
             return loss, pred
-        _lib.check(_lib.lib().kgw_readout_wmse_fwd(_p(H), _p(w_lin), _p(b_lin), _p(n_id), _p(y_all), _p(w_all), n,
-                                                   1 if relu else 0, _p(pred), _p(loss), _p(terms), _lib.stream_ptr()),
-                   'kgw_readout_wmse_fwd')
+        if loss_rule is not None:
+            _readout_loss_call('fwd', loss_rule, H, w_lin, n_id, y_all, w_all, n, 1 if relu else 0, b=b_lin, pred=pred, loss=loss, terms=terms)
+        else:
+            _lib.check(_lib.lib().kgw_readout_wmse_fwd(_p(H), _p(w_lin), _p(b_lin), _p(n_id), _p(y_all), _p(w_all), n,
+                                                       1 if relu else 0, _p(pred), _p(loss), _p(terms), _lib.stream_ptr()),
+                       'kgw_readout_wmse_fwd')
         ctx.save_for_backward(H, w_lin, pred, n_id, y_all, w_all)
         return loss, pred
 
     @staticmethod
     def backward(ctx, gloss, _gpred):
         if gloss is None:
-            return (None,) * 10
+            return (None,) * 11
         if ctx.ready is not None:
             dH, dw, db = ctx.ready
             ctx.ready = None
@@ -2996,18 +3032,22 @@ class _ReadoutWeightedMSE(torch.autograd.Function):
                 sink, (f, fkeep) = GRAD_SINK, fold
                 if not (sink is not None and is_unit and sink.park_readout_fold(f, fkeep, dw, db)):    # (rides in the next launch)
                     _lib.check(_lib.lib().kgw_readout_train_fold(C.byref(f), _lib.stream_ptr()), 'kgw_readout_train_fold')
-            return (*_for_gradient(gloss, (dH, dw, db)), None, None, None, None, None, None, None)
+            return (*_for_gradient(gloss, (dH, dw, db)), None, None, None, None, None, None, None, None)
         H, w_lin, pred, n_id, y_all, w_all = ctx.saved_tensors
         gloss = gloss.contiguous().to(torch.float64)
         dH = torch.empty_like(H)
         dw = torch.empty_like(w_lin)
         db = torch.empty(1, device=H.device)
         part = _readout_part(H.shape[0], 1, H.device)
+        if ctx.loss_rule is not None:
+            _readout_loss_call('bwd', ctx.loss_rule, H, w_lin, n_id, y_all, w_all, ctx.n, _relu_word(ctx.relu, ctx.h_is_relu),
+                               pred_in=pred, grad_loss=gloss, dH=dH, dW=dw, db=db, scratch=part)
+            return dH, dw, db, None, None, None, None, None, None, None, None
         _lib.check(_lib.lib().kgw_readout_wmse_bwd(_p(H), _p(w_lin), _p(pred), _p(n_id), _p(y_all), _p(w_all), ctx.n,
                                                    H.shape[0], _relu_word(ctx.relu, ctx.h_is_relu), _p(gloss),
                                                    _p(dH), _p(dw), _p(db), _p(part), _lib.stream_ptr()),
                    'kgw_readout_wmse_bwd')
-        return dH, dw, db, None, None, None, None, None, None, None
+        return dH, dw, db, None, None, None, None, None, None, None, None
 
 
 class _ReadoutWeightedMSEMulti(torch.autograd.Function):
@@ -3018,7 +3058,7 @@ class _ReadoutWeightedMSEMulti(torch.autograd.Function):
     the same launches, the weight read per column."""
 
     @staticmethod
-    def forward(ctx, H, W, b, n_id, y_all, w_all, n, relu, h_is_relu=False, unit_grad=False):
+    def forward(ctx, H, W, b, n_id, y_all, w_all, n, relu, h_is_relu=False, unit_grad=False, loss_rule=None):
         H, W, b = H.contiguous(), W.contiguous(), b.contiguous()
         T = W.shape[0]
         assert H.dtype == torch.float32 and H.shape[1] == KGW_C and H.shape[0] >= n and W.shape[1] == KGW_C and b.numel() == T
@@ -3033,10 +3073,21 @@ class _ReadoutWeightedMSEMulti(torch.autograd.Function):
         pred = torch.empty(n, T, device=dev)
         loss = torch.empty((), dtype=torch.float64, device=dev)
         terms = torch.empty(n, dtype=torch.float64, device=dev)
-        ctx.n, ctx.relu, ctx.h_is_relu = n, relu, h_is_relu
+        ctx.n, ctx.relu, ctx.h_is_relu, ctx.loss_rule = n, relu, h_is_relu, loss_rule
         ctx.mark_non_differentiable(pred)
         ctx.set_materialize_grads(False)
         ctx.ready = None
+        if loss_rule is not None:                  # (kgw_readout_loss_*: the weight form travels in the record)
+            if unit_grad and ctx.needs_input_grad[0]:
+                dH, dW, db = torch.empty_like(H), torch.empty_like(W), torch.empty_like(b)
+                part = _readout_part(n, T, dev)
+                _readout_loss_call('train', loss_rule, H, W, n_id, y_all, w_all, n, _relu_word(relu, h_is_relu), b=b, pred=pred,
+                                   loss=loss, dH=dH, dW=dW, db=db, terms=terms, scratch=part)
+                ctx.ready = (dH, dW, db)
+                return loss, pred
+            _readout_loss_call('fwd', loss_rule, H, W, n_id, y_all, w_all, n, 1 if relu else 0, b=b, pred=pred, loss=loss, terms=terms)
+            ctx.save_for_backward(H, W, pred, n_id, y_all, w_all)
+            return loss, pred
         if unit_grad and ctx.needs_input_grad[0]:
             dH, dW, db = torch.empty_like(H), torch.empty_like(W), torch.empty_like(b)
             part = _readout_part(n, T, dev)
@@ -3055,20 +3106,24 @@ class _ReadoutWeightedMSEMulti(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gloss, _gpred):
         if gloss is None:
-            return (None,) * 10
+            return (None,) * 11
         if ctx.ready is not None:
             dH, dW, db = ctx.ready
             ctx.ready = None
-            return (*_for_gradient(gloss, (dH, dW, db)), None, None, None, None, None, None, None)
+            return (*_for_gradient(gloss, (dH, dW, db)), None, None, None, None, None, None, None, None)
         H, W, pred, n_id, y_all, w_all = ctx.saved_tensors
         T = W.shape[0]
         gloss = gloss.contiguous().to(torch.float64)
         dH, dW, db = torch.empty_like(H), torch.empty_like(W), torch.empty(T, device=H.device)
         part = _readout_part(ctx.n, T, H.device)
+        if ctx.loss_rule is not None:
+            _readout_loss_call('bwd', ctx.loss_rule, H, W, n_id, y_all, w_all, ctx.n, _relu_word(ctx.relu, ctx.h_is_relu),
+                               pred_in=pred, grad_loss=gloss, dH=dH, dW=dW, db=db, scratch=part)
+            return dH, dW, db, None, None, None, None, None, None, None, None
         _lib.check(getattr(_lib.lib(), ctx.fam + 'bwd')(_p(H), _p(W), _p(pred), _p(n_id), _p(y_all), _p(w_all), ctx.n, H.shape[0], T,
                                                         _relu_word(ctx.relu, ctx.h_is_relu), _p(gloss), _p(dH),
                                                         _p(dW), _p(db), _p(part), _lib.stream_ptr()), ctx.fam + 'bwd')
-        return dH, dW, db, None, None, None, None, None, None, None
+        return dH, dW, db, None, None, None, None, None, None, None, None
 
 
 class _ReadoutLinearMulti(torch.autograd.Function):
@@ -3109,7 +3164,7 @@ def readout_linear(H, W, b):
 
 
 def readout_weighted_mse(H, w_lin, b_lin, n_id, y_all, w_all, n: int, relu: bool = True, h_is_relu: bool = False,
-                         unit_grad: bool = False):
+                         unit_grad: bool = False, loss_rule=None):
     """Returns (loss float64 scalar, pred float32 [n]); ``w_lin`` [1,128] / ``b_lin`` [1] = HeteroGNN.lin.
     ``h_is_relu``: see layer_transform's ``premasked``.  ``unit_grad``: the caller expects to backpropagate a loss gradient of
     exactly 1: forward and backward of this node then share two launches instead of four.  Passing the resident
@@ -3119,7 +3174,13 @@ def readout_weighted_mse(H, w_lin, b_lin, n_id, y_all, w_all, n: int, relu: bool
     mean over seeds and columns and pred [n,T] (kgw_readout_wmse_mt_*: two launches where the node is, nothing deferred).
     Per-trait weights: a 2-D ``w_all`` [N,T] (float64, contiguous) weighs every (SNP, column) pair on its own, and a weight of
     exactly 0 marks a pair as unobserved -- its label, NaN included, reaches neither the loss nor a gradient; the divisor stays
-    n * T (kgw_readout_wmse_mtw_*).  With T == 1 a weight [N,1] is the single-column call's [N]."""
+    n * T (kgw_readout_wmse_mtw_*).  With T == 1 a weight [N,1] is the single-column call's [N].
+    ``loss_rule`` (optim.parse_loss's LossRule; None = the weighted MSE and exactly the calls named above): a weighted Huber loss with
+    one knee per column (the rule: include/kgwas_hip.h, KgwReadoutLossArgs) in the place of the square, on kgw_readout_loss_fwd / _bwd
+    / _train -- the same kernels' Huber instantiations, the same launches, workspaces and (T == 1) deferred-fold protocol."""
+    if loss_rule is not None and len(loss_rule.delta) != (w_lin.shape[0] if w_lin.dim() == 2 else 1):
+        raise ValueError(f'a loss rule with {len(loss_rule.delta)} deltas for a read-out of '
+                         f'{w_lin.shape[0] if w_lin.dim() == 2 else 1} column(s)')
     T = w_lin.shape[0] if w_lin.dim() == 2 else 1
     if w_all.dim() == 2:                # (checked here, before any library call)
         if w_all.dtype != torch.float64:
@@ -3139,10 +3200,11 @@ def readout_weighted_mse(H, w_lin, b_lin, n_id, y_all, w_all, n: int, relu: bool
             if y_all.shape[1] != 1:
                 raise ValueError(f'{y_all.shape[1]} label columns for a read-out of one')
             y_all = y_all.reshape(-1)
-        return _ReadoutWeightedMSE.apply(H, w_lin, b_lin, n_id, y_all, w_all, int(n), bool(relu), bool(h_is_relu), bool(unit_grad))
+        return _ReadoutWeightedMSE.apply(H, w_lin, b_lin, n_id, y_all, w_all, int(n), bool(relu), bool(h_is_relu), bool(unit_grad),
+                                         loss_rule)
     if T > _lib.KGW_MT_MAX:
         raise NotImplementedError(f'the fused read-out + loss takes up to {_lib.KGW_MT_MAX} label columns, not {T}')
     if y_all.dim() != 2 or y_all.shape[1] != T:
         raise ValueError(f'a read-out of {T} columns needs labels [N, {T}], not {tuple(y_all.shape)}')
     return _ReadoutWeightedMSEMulti.apply(H, w_lin, b_lin, n_id, y_all.contiguous(), w_all, int(n), bool(relu), bool(h_is_relu),
-                                          bool(unit_grad))
+                                          bool(unit_grad), loss_rule)

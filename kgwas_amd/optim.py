@@ -12,6 +12,7 @@ from __future__ import annotations
 import ctypes as C
 import math
 import numbers
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -131,6 +132,58 @@ def parse_weight_average(spec, batches_per_epoch=None):
     if not ok:
         raise ValueError('weight_average: a KgwWeightAvg outside the rule\'s ranges (include/kgwas_hip.h: kgwavg_valid)')
     return out
+
+
+LossRule = NamedTuple('LossRule', [('kind', str), ('delta', tuple)])      # what parse_loss returns: immutable, one knee per label column
+_LOSS_KEYS = ('kind', 'delta')
+
+
+def parse_loss(loss, T):
+    """``loss`` -> None (the weighted MSE: the default route, untouched) or a LossRule (kind 'huber', ``delta``: a tuple of T knees; the
+    rule: include/kgwas_hip.h, KgwReadoutLossArgs).  ``loss``: None | 'mse' | 'huber' (delta 1.0, torch's default) | a float (Huber with
+    that delta) | a dict with ``kind`` and, for 'huber', ``delta``: a float > 0 (+inf: the MSE through the Huber kernels) or a
+    sequence of T of them, one per label column.  Anything else is a ValueError; no device is needed."""
+    T = int(T)
+    if T < 1:
+        raise ValueError(f'loss: {T} label columns')
+    if loss is None:
+        return None
+    if isinstance(loss, LossRule):                # (built by an earlier call, or by hand: checked below)
+        spec = {'kind': loss.kind, 'delta': loss.delta}
+    elif isinstance(loss, str):
+        spec = {'kind': loss}
+    elif not isinstance(loss, (bool, np.bool_, dict)) and isinstance(loss, numbers.Real):
+        spec = {'kind': 'huber', 'delta': loss}
+    elif isinstance(loss, dict):
+        spec = loss
+    else:
+        raise ValueError(f'loss {loss!r}: None, a kind {sorted(_lib.LOSS_KINDS)}, a delta or a dict with "kind"')
+    unknown = sorted(set(spec) - set(_LOSS_KEYS))
+    if unknown:
+        raise ValueError(f'loss: unknown key(s) {unknown}; known: {list(_LOSS_KEYS)}')
+    kind = spec.get('kind')
+    if not isinstance(kind, str) or kind not in _lib.LOSS_KINDS:
+        raise ValueError(f'loss: kind {kind!r}; one of {sorted(_lib.LOSS_KINDS)}')
+    if kind == 'mse':
+        if 'delta' in spec:
+            raise ValueError("loss: delta belongs to kind 'huber'")
+        return None
+    delta = spec.get('delta', 1.0)
+    if isinstance(delta, (str, bytes, dict)):
+        raise ValueError(f'loss: delta = {delta!r} must be a float > 0 or a sequence of {T}')
+    if isinstance(delta, numbers.Real):
+        delta = [delta] * T
+    else:
+        try:
+            delta = list(delta)
+        except TypeError:
+            raise ValueError(f'loss: delta = {delta!r} must be a float > 0 or a sequence of {T}') from None
+        if len(delta) != T:
+            raise ValueError(f'loss: {len(delta)} deltas for {T} label column(s)')
+    for d in delta:                               # (NaN fails the comparison; the kernels take the knee as a float32)
+        if isinstance(d, (bool, np.bool_)) or not isinstance(d, numbers.Real) or not C.c_float(d).value > 0.0:
+            raise ValueError(f'loss: delta = {d!r} must be > 0 as a float32 (+inf: the MSE)')
+    return LossRule('huber', tuple(float(C.c_float(d).value) for d in delta))       # (the float32 values the kernels compare against)
 
 
 class WeightAverage:
